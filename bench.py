@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/s (10 s @ 16 kHz) embedding extraction, BEATs-base, on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dtype f16|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dtype f16|bf16] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (wav resident in HBM -> fbank -> BEATs-base encoder ->
 mean-pooled 768-d embedding) over one batch of synthetic clips per GPU; with N > 1 the batch is
@@ -9,9 +9,14 @@ sharded data-parallel (one process per GPU, launched by torch.distributed.run) a
 with one RCCL all-gather of the pooled [B_local, 768] embeddings.  Weak scaling:
 per-GPU batch is fixed, `value` is whole-job clips/s.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times K steps, writes the last step's embeddings if --dump-outputs
+is given, and prints ONE JSON line (rank 0) with the driver's contract fields.  --full adds,
+after the timed region:
   roofline      dominant kernel (the MFMA GEMM): algorithmic FLOPs / HIP-event time on the launch stream
+  parity        live parity of the bench configuration against the reference golden
   cpu_baseline  the CPU oracle (NumPy restatement of the reference, "port") timed on this host
+and the other legs below (host-to-device rate, board power, configs C3 / C5; with N > 1 the
+clip-order check of the gathered matrix and the blocking all-gather time).
 """
 import argparse
 import json
@@ -25,6 +30,19 @@ sys.path.insert(0, ROOT)
 SAMPLES = 160000            # 10 s @ 16 kHz
 FLOP_PER_CLIP = 98.7e9      # SURVEY.md §8d (FFN 56.17, QKV/out 28.09, SDPA 9.07, pos-conv 4.69, ...)
 PEAK_TFLOPS = 2500.0        # dense bf16/f16 MFMA peak, MI355X_MICROARCH.md
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs budget
+
+
+def dump_outputs(out, out_dir: str) -> None:
+    """--dump-outputs: the timed path's last result, as its caller receives it (fp32), so that two builds can be compared output for
+    output on identical inputs.  Rows beyond the budget are dropped by a fixed seeded sample (same rows for the same arguments)."""
+    import numpy as np
+    a = out.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (a.itemsize * a.shape[1])
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pooled.npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline_worker(seconds_budget: float) -> None:
@@ -387,9 +405,15 @@ def main():
     ap.add_argument("--chunk", type=int, default=int(os.environ.get("AVEX_AMD_CHUNK", "256")))
     ap.add_argument("--residual", default=os.environ.get("AVEX_AMD_RESIDUAL", "half"), choices=["f32", "half"],
                     help="inter-kernel residual stream: fp32, or the operand type (default; pooled parity unchanged)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-power", action="store_true", help="skip the post-run board power / clock sample (rocm-smi)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs C3 (EAT) and C5 (EfficientNet-B0) after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: the pooled [N*B, 768] fp32 embeddings in clip order) "
+                         f"to DIR/pooled.npy; above {DUMP_MAX_BYTES >> 20} MB a fixed seeded sample of its rows, in row order")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything beyond the headline: roofline and per-kernel bounds, live "
+                         "parity, host-to-device rate, board power, configs C3 / C5, the CPU baseline; with N > 1 the gathered-matrix checks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-power", action="store_true", help="with --full: skip the post-run board power / clock sample (sysfs hwmon)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip BASELINE configs C3 (EAT) and C5 (EfficientNet-B0) after the timed region")
     ap.add_argument("--cpu-dry-run", action="store_true",
                     help="tests only: run the launch / barrier / timing / all-gather / JSON control flow on the CPU with gloo and a stub "
                          "in place of the encoder (no number it prints is a measurement)")
@@ -512,11 +536,13 @@ def main():
                     "ms_per_step": [round(v, 3) for v in ms],
                     "exposed_gather_ms_per_step_max": round(max(ex), 4), "exposed_gather_ms_per_step_mean": round(sum(ex) / world, 4)}
     assert torch.isfinite(out).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
 
-    # ---- after the timed region: the gathered matrix is in clip order on every rank ----
+    # ---- after the timed region (--full): the gathered matrix is in clip order on every rank ----
     gather_check = None
     all_gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         local = enc.forward(wav, want_features=False, want_pooled=True)["pooled"]
         dist.all_gather_into_tensor(gathered, local)
         piped_ok = torch.equal(out, gathered)                                      # what the timed loop's last (pipelined) gather delivered
@@ -551,7 +577,7 @@ def main():
     roof = None
     stages = None
     others = None
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         enc.set_profiling(True)
         enc.forward(wav, want_features=False, want_pooled=True)
         prof = enc.last_profile()
@@ -662,7 +688,7 @@ def main():
                        "parallelism": f"dp{world}", "world_size": dist.get_world_size() if world > 1 else 1,
                        "backend": (dist.get_backend() if world > 1 else None), "gathered_rows_in_clip_order": gather_check,
                        "all_gather": (None if world == 1 else {"form": "non-blocking, overlapped with the next step's kernels, last one flushed inside the timed region",
-                                                               "blocking_ms": round(all_gather_ms, 4), "bytes_per_rank": B * 768 * 4,
+                                                               "blocking_ms": None if all_gather_ms is None else round(all_gather_ms, 4), "bytes_per_rank": B * 768 * 4,
                                                                "exposed_ms": per_rank["exposed_gather_ms_per_step_max"],
                                                                "exposed_ms_how": "per step, the slowest rank: time its compute stream waited for a gather that had not finished under the next step's kernels (two events around the stream dependency)"}),
                        "per_rank": per_rank,
@@ -676,7 +702,7 @@ def main():
         }
         if dry:
             line["data"] = "cpu dry run (control flow only, not a measurement)"
-        if world > 1:
+        if world > 1 and args.full:
             # The first multi-GPU line checked against DESIGN.md section 5's list, on stderr (stdout stays one JSON line): what a reader of
             # SCALE_rNN.json should see before trusting the per-N values.
             c = line["config"]
@@ -690,15 +716,15 @@ def main():
             print(f"[bench] multi-GPU checklist ({world} ranks): " + ("all 5 hold" if not bad else "FAILED: " + "; ".join(bad))
                   + f" (exposed gather {c['all_gather']['exposed_ms']} ms, spread {100 * spread:.1f} %, slowest rank {per_rank['slowest_rank']})", file=sys.stderr, flush=True)
             line["config"]["checklist"] = {n: bool(ok) for n, ok in checks}
-        if world == 1 and not dry:
+        full = world == 1 and not dry and args.full
+        if full:
             line["parity"] = parity_vs_golden(cfg, sd, args, enc, wav)
-        if world == 1 and not dry:
             line["config"]["h2d_included"] = h2d_inclusive(enc, wav, max(args.steps, 5))
-        if world == 1 and not dry and not args.no_power:
+        if full and not args.no_power:
             line["power"] = board_power(step, sync, local_rank)
-        if world == 1 and not dry and not args.no_other_configs:
+        if full and not args.no_other_configs:
             line["configs"] = other_configs()
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, cfg)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -123,13 +123,53 @@ def test_bench_launches_its_own_ranks_from_a_plain_shell(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3",
-                        "--cpu-dry-run"], capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
+                        "--cpu-dry-run", "--full"], capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["world_size"] == 2 and d["config"]["backend"] == "gloo"
     assert d["config"]["gathered_rows_in_clip_order"] is True and d["config"]["global_batch"] == 6
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path, gpus):
+    """A plain run (no --full) times exactly --steps steps, prints only the headline line, and --dump-outputs writes what the timed path
+    returned at its last step: the stub's closed form of every clip of the job, in clip order (all ranks' rows, gathered)."""
+    import json, subprocess, sys
+    from avex_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--batch", "3",
+                        "--cpu-dry-run", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["roofline"] is None and "checklist" not in d["config"] and d["config"]["gathered_rows_in_clip_order"] is None
+    assert not {"parity", "power", "configs", "cpu_baseline"} & set(d)
+    assert sorted(os.listdir(tmp_path / "dump")) == ["pooled.npy"]
+    got = np.load(tmp_path / "dump" / "pooled.npy")
+    want = synth.noise_clips(gpus * 3, 160000, seed=0)[:, :768] * 2.0
+    assert got.dtype == np.float32 and np.array_equal(got, want)
+
+
+def test_bench_dump_over_budget_is_a_fixed_sample_of_rows(tmp_path, monkeypatch):
+    """--dump-outputs above its byte budget keeps whole rows, in row order, chosen by a fixed seed: two dumps of the same output agree."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 768 * 4)
+    out = torch.arange(40 * 768, dtype=torch.float32).reshape(40, 768)
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "pooled.npy"), np.load(tmp_path / "b" / "pooled.npy")
+    assert a.shape == (10, 768) and a.dtype == np.float32 and np.array_equal(a, b)
+    rows = a[:, 0].astype(np.int64) // 768
+    assert np.array_equal(a, out.numpy()[rows]) and (np.diff(rows) > 0).all()
 
 
 def test_bench_refuses_mismatched_world(tmp_path):
@@ -252,7 +292,7 @@ def test_bench_control_flow_at_eight_ranks(tmp_path):
     clip-order check over all 8 shards, one JSON line."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "2", "--cpu-dry-run"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "2", "--cpu-dry-run", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
