@@ -274,7 +274,7 @@ __global__ __launch_bounds__(1024) void attention_kernel(const T* __restrict__ q
 // the S accumulators START at gate * bias - reference (+ key mask) and the query fragment carries log2(e) / 8, so the S chain delivers
 // the exponent itself: a score costs half a packed FMA (the start), one v_exp_f32, half a packed add and half a convert.
 // A key tile is issued as four stages, each one query tile's MFMA chain with the other tile's vector work between its instructions
-// (ATT_IL, below): an MFMA waiting for the matrix pipe blocks the SIMD's vector issue for the OTHER wave, not for its own.
+// (below): an MFMA waiting for the matrix pipe blocks the SIMD's vector issue for the OTHER wave, not for its own.
 // Instantiations: <T, LONG> (more than 512 tokens: query blocks of 512, bias windows per phase) x <BIAS> (no table: EAT, wav2vec2).
 // ---------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) const void a_gptr_t;
@@ -307,15 +307,6 @@ constexpr float A2_THR = 8.f;
 #if defined(ATT_STAMPS) && ATT_STAMPS
 __device__ unsigned long long g_att_stamps[64 * 8 * 32 * 8];   // [block < 64][wave][phase < 32][7 x s_memtime, s_memrealtime]
 #endif
-#ifndef ATT_STAGGER
-#define ATT_STAGGER 0    // waves 4-7 enter each phase's key tiles this many 64-cycle sleeps after waves 0-3 (SIMD partners out of lockstep)
-#endif
-#ifndef ATT_PRIO
-#define ATT_PRIO 1       // 1: waves 4-7 run at s_setprio 1
-#endif
-#ifndef ATT_IL
-#define ATT_IL 1         // 1: the key tile's MFMAs and vector work interleaved instruction by instruction in every wave (below); 0: in segments
-#endif
 #ifndef ATT_STAMPS
 #define ATT_STAMPS 0     // diagnostic build: -DATT_STAMPS=1 prints one tile's cycle stamps (AVEX_AMD_ATT_DEBUG=4)
 #endif                             // deferred-max threshold, log2 units (p <= 256)
@@ -329,9 +320,6 @@ static __device__ __forceinline__ void a2_dma16(const void* src, const char* lds
     asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds) : "memory");
 }
 
-#ifndef ATT_BIAS_REUSE
-#define ATT_BIAS_REUSE 1      // 0: A/B build, each query tile reads its bias vectors from LDS (round 2's form; tiles 256 rows apart)
-#endif
 // XT (long clips without a bias table only): a LAST key block of 257 .. 288 keys runs as one phase of NINE key tiles instead of a ninth
 // tile's worth of keys getting a phase of their own (EAT: 513 keys = 256 + 257).  The buffers grow to 288 keys; the LDS the bias windows
 // would take is free without a table.
@@ -348,7 +336,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
     typedef typename Half<T>::v8 v8;
     typedef typename Half<T>::v4 v4;
     constexpr int NQ = 2, NW = 8, NT = 512;              // 8 waves, two 32-query tiles each (tile wave + 8 u)
-    static_assert(!XT || (LONG && !BIAS && ATT_IL), "the nine-tile last phase is built for long clips without a bias table (whose windows' LDS it takes)");
+    static_assert(!XT || (LONG && !BIAS), "the nine-tile last phase is built for long clips without a bias table (whose windows' LDS it takes)");
     constexpr int NKT = XT ? 9 : 8;                      // key tiles a phase buffer holds
     constexpr int KBUF = XT ? A2X_KBUF : A2_KBUF;        // bytes of K per buffer (V follows)
     constexpr int HALF = XT ? A2X_HALF : A2_HALF;        // bytes per buffer
@@ -380,10 +368,10 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
     auto set_qblock = [&](int qb) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
-            qi[u] = qb * 512 + (ATT_BIAS_REUSE ? (NQ * wave + u) : (wave + NW * u)) * 32 + r32;   // ADJACENT tiles: tile 1's bias values at key tile k are tile 0's at key tile k - 1 (below)
+            qi[u] = qb * 512 + (NQ * wave + u) * 32 + r32;   // ADJACENT tiles: tile 1's bias values at key tile k are tile 0's at key tile k - 1 (below)
             iq[u] = qi[u] < Tn ? qi[u] : Tn - 1;         // clamped for loads; stores are masked
         }
-        has_q = qb * 512 + (ATT_BIAS_REUSE ? NQ * wave : wave) * 32 < Tn;
+        has_q = qb * 512 + NQ * wave * 32 < Tn;
     };
     set_qblock(qb0);
 
@@ -429,7 +417,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
     auto write_window = [&](int ph) __attribute__((always_inline)) {
         float* win = tab + (ph & 1) * (4 * A2_WLD);
         const int r0 = half_ld * 256 - qb_ld * 512 - 511 + (Tn - 1);     // bias-row index of window entry 0
-        for (int r = tid; r < A2_WLD && (BIAS || !ATT_IL); r += NT) {   // (the interleaved tile body does not read the window without a table)
+        for (int r = tid; r < A2_WLD && BIAS; r += NT) {   // (the tile body does not read the window without a table)
             const int g = r0 + r;
             float v = 0.f;
             if (bias_tab && g >= 0 && g < 2 * Tn - 1) v = bias_tab[(int64_t)h_ld * (2 * Tn - 1) + g] * 1.4426950408889634f;
@@ -460,7 +448,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
 #pragma unroll
             for (int s = 0; s < 4; ++s) qf[u][s] = *(const v8*)(base + (int64_t)iq[u] * ld + 16 * s + 8 * hh);
     };
-    if (ATT_PRIO && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);   // the second-dispatched half loses every VALU arbitration otherwise (one static raise, no per-segment flips)
+    if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);   // the second-dispatched half loses every VALU arbitration otherwise (one static raise, no per-segment flips)
     load_q(h_cur, b_cur);                                // older than the DMA below: waiting for it never waits for the DMA
     if (LONG) write_window(0);
     issue_next(0);
@@ -655,8 +643,6 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
             v8 kf[4];
 #pragma unroll
             for (int s = 0; s < 4; ++s) kf[s] = *(const v8*)(kp[s]);
-            if (ATT_STAGGER > 0 && wave >= NW / 2) __builtin_amdgcn_s_sleep(ATT_STAGGER);
-#if ATT_IL
             // A wave issues in order, and an MFMA that finds the matrix pipe busy holds the SIMD's vector issue port until it is
             // accepted (scripts/micro/seg_cost.hip: a vector wave beside a wave of back-to-back MFMAs runs at an eighth of its rate).
             // So the overlap of matrix and vector work is made INSIDE each wave: every stage below is one MFMA chain of one query
@@ -676,8 +662,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
                 const f32x2 eb = __builtin_elementwise_fma(g2, (f32x2){t4[2], t4[3]}, nm2);
                 Sq[u][4 * g4] = ea[0]; Sq[u][4 * g4 + 1] = ea[1]; Sq[u][4 * g4 + 2] = eb[0]; Sq[u][4 * g4 + 3] = eb[1];
             };
-            // without a bias table (EAT, wav2vec2) the start is -m alone: no table reads, no FMAs (workgroup-uniform branch)
-            constexpr bool has_bias = BIAS || !ATT_IL;
+            // without a bias table (EAT, wav2vec2) the start is -m alone: no table reads, no FMAs
             auto acc_plain = [&](int u) __attribute__((always_inline)) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) Sq[u][r] = -m_run[u];
@@ -687,7 +672,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
             // second time.  The kernel is LDS-bandwidth-bound (scripts/micro/att_lds16.hip: 2 449 cycles per key tile with its LDS reads,
             // 1 498 without), and the bias vectors were half of a wave's 16 KB per key tile; now 12 KB.
             f32x4 tcur[4];
-            if (has_bias) {
+            if (BIAS) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) { tcur[g4] = *(const f32x4*)(tp[0] + 8 * g4); acc_start(0, g4, tcur[g4]); }
 #pragma unroll
@@ -718,7 +703,9 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
                         pf[u][r >> 3][(r & 7) + 1] = (T)pp[1];
                     }
                 };
-                // (see the segment form below for the deferred reference: a half-row sum below 2^12 proves the tile's p are f16-safe)
+                // The running reference is checked AFTER the exponentials, on the half-row sums that are needed anyway: a sum below 2^12
+                // proves every p of this lane is below 2^12 (f16-safe), so the common path has no maximum at all; !(sum < 2^12) also
+                // catches the overflowed (inf) and the invalid (NaN) sum.  redo_u moves tile u's reference and recomputes its p.
                 auto redo_u = [&](int u) __attribute__((always_inline)) {
                     float mx = Sq[u][0];
 #pragma unroll
@@ -778,7 +765,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
                 if (ktl + 1 < NKT) {
 #pragma unroll
                     for (int s = 0; s < 4; ++s) kf[s] = *(const v8*)(kp[s] + (ktl + 1) * 4096);
-                    if (has_bias) {
+                    if (BIAS) {
 #pragma unroll
                         for (int g4 = 0; g4 < 4; ++g4) t4n[g4] = *(const f32x4*)(tp[0] + (ktl + 1) * 32 + 8 * g4);
                     }
@@ -804,7 +791,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
                 AVX_FENCE();
                 AVX_TS(5)
                 // stage 4
-                if (has_bias) {
+                if (BIAS) {
                     o0[1] = mfma32(vf[0][0], pf[1][0], o0[1]);
                     if (ktl + 1 < NKT) { acc_start(0, 0, t4n[0]); acc_start(0, 1, t4n[1]); }
                     AVX_FENCE();
@@ -812,19 +799,13 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
                     if (ktl + 1 < NKT) { acc_start(0, 2, t4n[2]); acc_start(0, 3, t4n[3]); }
                     AVX_FENCE();
                     o0[1] = mfma32(vf[1][0], pf[1][1], o0[1]);
-                    if (!ATT_BIAS_REUSE && ktl + 1 < NKT) {
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4) tcur[g4] = *(const f32x4*)(tp[1] + (ktl + 1) * 32 + 8 * g4);      // A/B build: tile 1's values from LDS as before
-                    }
                     if (ktl + 1 < NKT) { acc_start(1, 0, tcur[0]); acc_start(1, 1, tcur[1]); }       // tile 1 at key tile k + 1 = tile 0's values at key tile k
                     AVX_FENCE();
                     o1[1] = mfma32(vf[1][1], pf[1][1], o1[1]);
                     if (ktl + 1 < NKT) {
                         acc_start(1, 2, tcur[2]); acc_start(1, 3, tcur[3]);
-                        if (ATT_BIAS_REUSE) {
 #pragma unroll
-                            for (int g4 = 0; g4 < 4; ++g4) tcur[g4] = t4n[g4];
-                        }
+                        for (int g4 = 0; g4 < 4; ++g4) tcur[g4] = t4n[g4];
                     }
                     AVX_FENCE();
                 } else {
@@ -848,124 +829,6 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
 #undef AVX_TS
             };
 #undef AVX_FENCE
-#else
-            auto tile = [&](auto KT) __attribute__((always_inline)) {
-                constexpr int ktl = decltype(KT)::value;
-                const int kt = half * 8 + ktl;
-                const int jb = kt * 32 + 4 * hh;
-                const bool masked_tile = key_pad != nullptr || kt * 32 + 32 > Tn;   // wave-uniform
-                // V fragments of this key tile, transposed by the LDS: issued now, waited for after the softmax
-                a_i32x2 vt[2][2][2];
-#define AVX_TR(dst, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(vaddr), "n"(OFF))
-                AVX_TR(vt[0][0][0], 1024 * (ktl * 4 + 0) + 0);   AVX_TR(vt[0][0][1], 1024 * (ktl * 4 + 1) + 0);
-                AVX_TR(vt[0][1][0], 1024 * (ktl * 4 + 0) + 512); AVX_TR(vt[0][1][1], 1024 * (ktl * 4 + 1) + 512);
-                AVX_TR(vt[1][0][0], 1024 * (ktl * 4 + 2) + 0);   AVX_TR(vt[1][0][1], 1024 * (ktl * 4 + 3) + 0);
-                AVX_TR(vt[1][1][0], 1024 * (ktl * 4 + 2) + 512); AVX_TR(vt[1][1][1], 1024 * (ktl * 4 + 3) + 512);
-#undef AVX_TR
-                // Both query tiles in one straight-line block.  The MFMA accumulators START at the additive part of the score,
-                // gate * bias - m_run (+ the key mask), in log2 units, and the query fragment is pre-multiplied by log2(e) / 8 (once per
-                // item, below): the S chain then delivers  score - m_run  ready for the exponential -- no VALU between the matrix
-                // pipe and v_exp_f32, and the bias FMAs sit in front of the chain where they overlap the partner wave's MFMAs.
-                // The running reference is checked AFTER the exponentials, on the half-row sums that are needed anyway: a sum below
-                // 2^12 proves every p of this lane is below 2^12 (f16-safe), so the common path has no maximum at all.
-                v8 pf[NQ][2];
-                f32x2 ls[NQ];
-                f32x16 Sq[NQ];
-                auto init_acc = [&](int u) __attribute__((always_inline)) {
-                    const f32x2 g2 = {gate[u], gate[u]}, nm2 = {-m_run[u], -m_run[u]};
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const f32x4 t4 = (dbg & 512) ? (f32x4){0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(tp[u] + ktl * 32 + 8 * g4);
-                        const f32x2 ea = __builtin_elementwise_fma(g2, (f32x2){t4[0], t4[1]}, nm2);
-                        const f32x2 eb = __builtin_elementwise_fma(g2, (f32x2){t4[2], t4[3]}, nm2);
-                        Sq[u][4 * g4] = ea[0]; Sq[u][4 * g4 + 1] = ea[1]; Sq[u][4 * g4 + 2] = eb[0]; Sq[u][4 * g4 + 3] = eb[1];
-                    }
-                    if (masked_tile) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) Sq[u][r] += kad[jb + (r & 3) + 8 * (r >> 2)];
-                    }
-                };
-                // exponentials of tile u -> P fragment + half-row sums; true if the running reference has to move
-                auto softmax_u = [&](int u) __attribute__((always_inline)) -> bool {
-                    ls[u] = (f32x2){0.f, 0.f};
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        const f32x2 pp = (dbg & 128) ? (f32x2){Sq[u][r], Sq[u][r + 1]} : (f32x2){__builtin_amdgcn_exp2f(Sq[u][r]), __builtin_amdgcn_exp2f(Sq[u][r + 1])};
-                        ls[u] += pp;
-                        pf[u][r >> 3][r & 7] = (T)pp[0];
-                        pf[u][r >> 3][(r & 7) + 1] = (T)pp[1];
-                    }
-                    // !(sum < 2^12) also catches the overflowed (inf) and the invalid (NaN) sum
-                    return !ref_set[u] || !(hsum2(ls[u]) < 4096.f);
-                };
-                // a row's first unmasked tile sets its reference to the row maximum; later it moves when a tile has grown past it.
-                // The exponentials of this tile are redone against the new reference.
-                auto redo_u = [&](int u) __attribute__((always_inline)) {
-                    float mx = Sq[u][0];
-#pragma unroll
-                    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, Sq[u][r]);
-                    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                    const bool need = ref_set[u] ? mx > A2_THR : mx != NEG_INF;
-                    const float d = need ? mx : 0.f;
-                    const float alpha = (need && ref_set[u]) ? __builtin_amdgcn_exp2f(-d) : 1.f;
-                    ref_set[u] = ref_set[u] || need;
-                    m_run[u] += d;
-                    l_run[u] *= alpha;
-                    ls[u] = (f32x2){0.f, 0.f};
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { o0[u][r] *= alpha; o1[u][r] *= alpha; }
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        const f32x2 pp = {__builtin_amdgcn_exp2f(Sq[u][r] - d), __builtin_amdgcn_exp2f(Sq[u][r + 1] - d)};
-                        ls[u] += pp;
-                        pf[u][r >> 3][r & 7] = (T)pp[0];
-                        pf[u][r >> 3][(r & 7) + 1] = (T)pp[1];
-                    }
-                };
-                v8 vf[2][2];
-                auto wait_v = [&]() __attribute__((always_inline)) {
-                    asm volatile("s_waitcnt lgkmcnt(0)"
-                                 : "+v"(vt[0][0][0]), "+v"(vt[0][0][1]), "+v"(vt[0][1][0]), "+v"(vt[0][1][1]),
-                                   "+v"(vt[1][0][0]), "+v"(vt[1][0][1]), "+v"(vt[1][1][0]), "+v"(vt[1][1][1]));
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                        for (int dh = 0; dh < 2; ++dh) {
-                            const v4 lo = __builtin_bit_cast(v4, vt[s2][dh][0]), hi = __builtin_bit_cast(v4, vt[s2][dh][1]);
-                            vf[s2][dh] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                        }
-                };
-                auto next_k = [&]() __attribute__((always_inline)) {
-                    // the K fragment is dead once both chains are issued: the next tile's goes into the same registers now
-                    if (ktl + 1 < NKT) {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) kf[s] = *(const v8*)(kp[s] + (ktl + 1) * 4096);
-                    }
-                };
-                init_acc(0); init_acc(1);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {            // the two tiles' chains interleaved: consecutive MFMAs never share an accumulator
-#pragma unroll
-                    for (int u = 0; u < NQ; ++u) if (!(dbg & 64)) Sq[u] = mfma32(kf[s], qf[u][s], Sq[u]);
-                }
-                next_k();
-                bool moves = softmax_u(0);
-                moves = softmax_u(1) || moves;
-                if (__any(moves)) { redo_u(0); redo_u(1); }
-                l_run[0] += hsum2(ls[0]); l_run[1] += hsum2(ls[1]);
-                wait_v();
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int dh = 0; dh < 2; ++dh)
-#pragma unroll
-                        for (int u = 0; u < NQ; ++u) {
-                            if (dbg & 256) continue;
-                            if (dh == 0) o0[u] = mfma32(vf[s2][0], pf[u][s2], o0[u]);
-                            else o1[u] = mfma32(vf[s2][1], pf[u][s2], o1[u]);
-                        }
-            };
-#endif
             if (0 < kt_end) tile(a_ic<0>{});
             if (1 < kt_end) tile(a_ic<1>{});
             if (2 < kt_end) tile(a_ic<2>{});
@@ -989,7 +852,7 @@ __global__ __launch_bounds__(512) void attention2_kernel(const T* __restrict__ q
                     const T* nbase = qkv + (int64_t)bn * Tn * ld + hn * 64;
 #pragma unroll
                     for (int u = 0; u < NQ; ++u) {
-                        int qin = qn * 512 + (ATT_BIAS_REUSE ? (NQ * wave + u) : (wave + NW * u)) * 32 + r32;
+                        int qin = qn * 512 + (NQ * wave + u) * 32 + r32;
                         qin = qin < Tn ? qin : Tn - 1;
 #pragma unroll
                         for (int s4 = 0; s4 < 4; ++s4) qf[u][s4] = *(const v8*)(nbase + (int64_t)qin * ld + 16 * s4 + 8 * hh);

@@ -59,21 +59,6 @@ constexpr float A3_THR = 8.f;                             // deferred reference:
 constexpr float A3_SUM_HI = 4096.f;                       // a half-row sum below 2^12 proves every numerator of the lane is below 2^12
 constexpr float A3_SUM_LO = 0.015625f;                    // first tile: a sum above 2^-6 means the row's numerators are not all deep in the subnormals
 
-#ifndef ATT3_DMA_NT
-#define ATT3_DMA_NT 0    // 1: the K / V LDS-DMA with the nt policy (every byte is read by one workgroup, once).  MEASURED: level (256-clip step 24.910 vs 24.903 ms in one process)
-#endif
-#ifndef ATT3_PRIO
-#define ATT3_PRIO 1      // 1: waves 4-7 at s_setprio 1 (one static raise); 2: waves 0-3 instead; 0: none
-#endif
-#ifndef ATT3_WG_STAGGER
-#define ATT3_WG_STAGGER 0   // workgroup w starts ((w >> 3) & 7) x this many 64-cycle sleeps late: the CUs' item ends (64 KiB of stores each) stop coinciding (A/B builds)
-#endif
-#ifndef ATT3_FULL_LINES
-#define ATT3_FULL_LINES 0   // 1: output stores as whole 128-byte lines (see store_item; measured level with the default: 285.2 vs 285.1 us, profiles/r05a_attention16.txt)
-#endif
-#ifndef ATT3_STAGGER
-#define ATT3_STAGGER 0   // waves 4-7 enter each phase's key tiles this many 64-cycle sleeps late (A/B builds)
-#endif
 // Diagnostics of the standalone harness (scripts/micro/att16_bench.hip); the library is built with both at 0, which compiles them out.
 #ifndef A3_KO
 #define A3_KO 0          // knock-outs: 1 no range checks, 2 no exponentials, 4 no S MFMAs, 8 no P V MFMAs, 16 no accumulator starts, 32 no scheduling fences
@@ -105,12 +90,10 @@ static __device__ __forceinline__ float a3_rows_max(float x) {
 
 static __device__ __forceinline__ void a3_dma16(const void* src, const char* lds_dst) {
     // (inline assembly on purpose: see a2_dma16 in attention.hip -- behind the builtin the compiler drains vmcnt in front of every LDS read)
+    // (the default cache policy: with the nt bit -- every byte is read by one workgroup, once -- the 256-clip step measured level, 24.910 vs
+    // 24.903 ms in one process)
     const unsigned lds = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) const char*)lds_dst;
-#if ATT3_DMA_NT
-    asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(src), "s"(lds) : "memory");
-#else
     asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds) : "memory");
-#endif
 }
 
 template <typename T, bool BIAS, bool XT = false>
@@ -210,8 +193,7 @@ __global__ __launch_bounds__(512) void attention3_kernel(const T* __restrict__ q
             asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:64" : "=&v"(qf[nb][0]), "=&v"(qf[nb][1]) : "v"(src) : "memory");
         }
     };
-    if (ATT3_WG_STAGGER > 0) { for (int i = 0; i < (int)((blockIdx.x >> 3) & 7); ++i) __builtin_amdgcn_s_sleep(ATT3_WG_STAGGER); }
-    if ((ATT3_PRIO == 1 && wave >= NW / 2) || (ATT3_PRIO == 2 && wave < NW / 2)) __builtin_amdgcn_s_setprio(1);
+    if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);      // waves 4-7 at priority 1 (one static raise)
     load_q(h_cur, b_cur);                                // older than the DMA below: waiting for it never waits for the DMA
 #pragma unroll
     for (int u = 0; u < 4; ++u) dma_piece(0, u);
@@ -290,23 +272,8 @@ __global__ __launch_bounds__(512) void attention3_kernel(const T* __restrict__ q
                 const auto s1 = __builtin_amdgcn_permlane16_swap(pk(o[nb][2 * p], 1), pk(o[nb][2 * p + 1], 1), false, false);
                 w[p][0] = (int)s0[0]; w[p][1] = (int)s1[0]; w[p][2] = (int)s0[1]; w[p][3] = (int)s1[1];
             }
-#if ATT3_FULL_LINES
-            // Full 128-byte lines per store instruction (8 rows x 128 B instead of 16 rows x 64 B; the store path is issue-bound at the end of an
-            // item and half lines cost it twice the requests): lanes c and c + 8 of a 16-lane row trade one chunk -- lane c < 8 gives its second-half
-            // chunk and takes lane c + 8's first-half chunk -- so the first store writes rows 0 .. 7 whole and the second rows 8 .. 15.  Three DPP
-            // moves per register (row rotate by 8 with a bank mask).
-            a3_i32x4 wa, wb;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int t = __builtin_amdgcn_update_dpp(0, w[0][e], 0x128, 0xF, 0xF, false);            // t[i] = w0[(i + 8) % 16]
-                wa[e] = __builtin_amdgcn_update_dpp(w[0][e], w[1][e], 0x128, 0xF, 0xC, false);            // lanes 8-15: w1 of lane i - 8; lanes 0-7 keep w0
-                wb[e] = __builtin_amdgcn_update_dpp(w[1][e], t, 0xE4, 0xF, 0x3, false);                   // lanes 0-7: w0 of lane i + 8; lanes 8-15 keep w1
-            }
-            const int qrow = Q0 + 16 * nb + (c & 7);
-            T* orow = out + ((int64_t)b * Tn + qrow) * E + h * 64 + 16 * (g & 1) + 8 * (g >> 1) + 32 * (c >> 3);
-            if (qrow < Tq) *(a3_i32x4*)orow = wa;
-            if (qrow + 8 < Tq) *(a3_i32x4*)(orow + 8 * (int64_t)E) = wb;
-#else
+            // 16 rows x 64 bytes per store instruction.  (Whole 128-byte lines, by trading a chunk between lanes c and c + 8 with three DPP
+            // moves per register, measured level: 285.2 vs 285.1 us, profiles/r05a_attention16.txt.)
             const int qrow = Q0 + 16 * nb + c;
             T* orow = out + ((int64_t)b * Tn + qrow) * E + h * 64 + 16 * (g & 1) + 8 * (g >> 1);
 #pragma unroll
@@ -314,7 +281,6 @@ __global__ __launch_bounds__(512) void attention3_kernel(const T* __restrict__ q
                 const a3_i32x4 wv = {w[p][0], w[p][1], w[p][2], w[p][3]};
                 if (qrow < Tq) *(a3_i32x4*)(orow + 32 * p) = wv;
             }
-#endif
         }
     };
 
@@ -410,7 +376,6 @@ __global__ __launch_bounds__(512) void attention3_kernel(const T* __restrict__ q
             const float* tp = tab + (e0 & 3) * A3_TLD + A3_TPAD + (e0 & ~3);
             const unsigned vaddr = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) const char*)(Kb + KBUF + v_lane);
 
-            if (ATT3_STAGGER > 0 && wave >= NW / 2) __builtin_amdgcn_s_sleep(ATT3_STAGGER);
             v8 kf[2][2];                                 // [k-step][key block]
 #pragma unroll
             for (int s = 0; s < 2; ++s)

@@ -166,17 +166,9 @@ static __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
 // per pair less, of ~15 vector slots.  |gelu - exact| <= 6.3e-6 over [-12, 12] in fp32 (fit: weighted minimax of log2 q with weight a q ln 2,
 // like the degree-6 one): a tenth of an f16 ulp at |gelu| = 0.1, i.e. + 0.5 % on the rounding noise (sqrt(1 + 12 delta^2)) of a stored
 // activation, against 3.5e-7 which is finer than any half type can hold.  fp32 outputs keep the degree-6 form.
-#define AVX_GELUH_C0 -1.0004795789718628f
-#define AVX_GELUH_C1 -1.1473724842071533f
-#define AVX_GELUH_C2 -0.46801453828811646f
-#define AVX_GELUH_C3 -0.044079434126615524f
-#define AVX_GELUH_C4 0.0038662925362586975f
 // ... and in the form  gelu(x) = max(x, 0) - a q(a),  a = min(|x|, 5.7):  the same function (x >= 0: x (1 - q) = x Phi(x); x < 0: -|x| Phi(-|x|)),
 // one |x|-clamp (the |.| is an operand modifier), one max and one packed FMA around the exponent instead of |x|, the clamp, a packed multiply,
 // a packed subtract and a packed FMA: 2.5 instead of 3.5 vector slots per element.  Beyond the clamp a q is 3.4e-8 instead of |x| q.
-#ifndef AVX_GELUH_RELU
-#define AVX_GELUH_RELU 1
-#endif
 // NaN in, NaN out, at no extra instruction (round 5).  min(|x|, 5.7) and max(x, 0) return their non-NaN operand, so the form above turned a NaN
 // pre-activation into -3e-8: the fc2 hook taps of a clip with one NaN sample -- what extract_embeddings returns -- were finite (the reference's fp32
 // F.gelu gives NaN, backbone.py:368).  The clamp of |x| is now the CLAMP OUTPUT MODIFIER of a multiply, t = clamp01(|x| / 5.7), which passes a NaN
@@ -196,7 +188,6 @@ static __device__ __forceinline__ float gelu_clamp_t(float x, float inva) {
     return t;
 }
 static __device__ __forceinline__ f32x2 gelu_erf2_h(f32x2 x, float inva) {
-#if AVX_GELUH_RELU
     const f32x2 t = {gelu_clamp_t(x[0], inva), gelu_clamp_t(x[1], inva)};
     f32x2 p = __builtin_elementwise_fma((f32x2)(AVX_GELUH_T4), t, (f32x2)(AVX_GELUH_T3));
     p = __builtin_elementwise_fma(p, t, (f32x2)(AVX_GELUH_T2));
@@ -206,20 +197,6 @@ static __device__ __forceinline__ f32x2 gelu_erf2_h(f32x2 x, float inva) {
     q[0] = __builtin_amdgcn_exp2f(p[0]); q[1] = __builtin_amdgcn_exp2f(p[1]);
     r[0] = __builtin_fmaxf(x[0], 0.f); r[1] = __builtin_fmaxf(x[1], 0.f);
     return __builtin_elementwise_fma(-t, q, r);
-#else
-    f32x2 a;
-    a[0] = __builtin_fminf(__builtin_fabsf(x[0]), AVX_GELU_A); a[1] = __builtin_fminf(__builtin_fabsf(x[1]), AVX_GELU_A);
-    f32x2 p = __builtin_elementwise_fma((f32x2)(AVX_GELUH_C4), a, (f32x2)(AVX_GELUH_C3));
-    p = __builtin_elementwise_fma(p, a, (f32x2)(AVX_GELUH_C2));
-    p = __builtin_elementwise_fma(p, a, (f32x2)(AVX_GELUH_C1));
-    p = __builtin_elementwise_fma(p, a, (f32x2)(AVX_GELUH_C0));
-    f32x2 q;
-    q[0] = __builtin_amdgcn_exp2f(p[0]); q[1] = __builtin_amdgcn_exp2f(p[1]);
-    f32x2 ax;
-    ax[0] = __builtin_fabsf(x[0]); ax[1] = __builtin_fabsf(x[1]);
-    const f32x2 u = (f32x2)(0.5f) - q;
-    return __builtin_elementwise_fma(ax, u, x * (f32x2)(0.5f));
-#endif
 }
 static __device__ __forceinline__ f32x4 gelu_erf4_h(f32x4 v, float inva) {
     const f32x2 a = gelu_erf2_h((f32x2){v[0], v[1]}, inva), b = gelu_erf2_h((f32x2){v[2], v[3]}, inva);
@@ -401,9 +378,8 @@ struct GemmArgs {
                               // avx::gemm folds per launch when the flag is clear; callers that launch the same fold repeatedly keep the vectors
     float* stats_out;         // [M][N/64][2] or NULL
     // The finished row statistics instead of (or beside) the partial ones: rows_out[m] = (rstd, -mu rstd) of output row m with rows_eps inside
-    // the root -- what avx::ln_rowstats makes of stats_out, same bits.  The full-row kernel (gemm_row.hip, N = 768) writes them from its
-    // epilogue; when another kernel runs the product, avx::gemm writes the partials to stats_out (required then, as scratch) and launches
-    // ln_rowstats itself.  Readable / writable up to M rounded up to even.
+    // the root -- what avx::ln_rowstats makes of stats_out, same bits: avx::gemm writes the partials to stats_out (required, as scratch) and
+    // launches ln_rowstats itself.  Readable / writable up to M rounded up to even.
     float* rows_out; float rows_eps;
     // Mean-pooled hook tap without the tap: the rows are clips of pool_T (>= 64) consecutive rows; each 64-row block writes the column
     // sums of acc + bias (what out_raw would hold) over its rows, split at the one clip boundary it can contain:
@@ -434,9 +410,6 @@ struct GemmArgs {
     int nt;                   // set by the launcher: bit 0 non-temporal output stores (256-tile kernels)
 };
 int gemm(const GemmArgs& a, int dtype, hipStream_t s);
-// the full-row residual kernel (gemm_row.hip): N = 768, one workgroup per 128 rows x all columns; avx::gemm dispatches to it (variant 8, or auto)
-bool gemm_row_ok(const GemmArgs& a);
-int gemm_row(const GemmArgs& a, int dtype, hipStream_t s);
 // fp32 NHWC rows [B * HW, ld] -> NCHW [B, C, HW], optionally undoing a folded BatchNorm: (x - shift[c]) / scale[c] (effnet.hip)
 int nhwc_to_nchw(const float* in, int64_t ld, int B, int HW, int C, const float* scale, const float* shift, float* out, hipStream_t s);
 // MBConv front in one kernel: 1x1 expansion (kin = 32 | 64 input channels) + BN + SiLU + depthwise k x k + BN + SiLU + squeeze sums (effnet.hip)

@@ -11,9 +11,6 @@
 //   scale_channels x[b, p, c] *= s[b, c] (the excitation), in place
 #include "common.h"
 
-#ifndef MBCONV_MODE_TOGGLE
-#define MBCONV_MODE_TOGGLE 1
-#endif
 namespace {
 
 __device__ __forceinline__ float silu1(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
@@ -86,12 +83,6 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
 #ifndef DW_PY
 #define DW_PY 1       // output rows per thread
 #endif
-#ifndef DW_ROLL
-#define DW_ROLL 0     // 1: the loop over input rows stays rolled (one row of loads live at a time: fewer registers, more waves per SIMD)
-#endif
-#ifndef DW_WAVES
-#define DW_WAVES 0    // > 0: amdgpu_waves_per_eu for dwconv_kernel
-#endif
 // one thread: 8 channels, PIX consecutive output pixels along x of PY consecutive output rows; squeeze sums leave as per-workgroup partials.  The kernel is
 // bound by its 16-byte loads from L2 (every input element is wanted by KS x KS outputs): a 1 x 4 tile makes 4.5 loads per output at 3 x 3
 // (13.5 ms per 256 clips of EfficientNet-B0 at the time), 1 x 8 3.75 (12.8 ms); wider tiles lose to their registers (1 x 12: 13.2, 1 x 16:
@@ -99,9 +90,6 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
 // Every output adds its taps in (ky, kx) order whatever the tile: the tile shape does not change a bit of the result.
 template <typename T, int KS, int ST>
 __global__ __launch_bounds__(256)
-#if DW_WAVES
-__attribute__((amdgpu_waves_per_eu(DW_WAVES, DW_WAVES)))
-#endif
 void dwconv_kernel(const T* __restrict__ in, int H, int W, int Ho, int Wo, int Cp,
                                                      const float* __restrict__ w /*[KS*KS][Cp]*/, const float* __restrict__ bias,
                                                      T* __restrict__ out, float* __restrict__ part /*[B][gridDim.x][Cp]*/) {
@@ -129,11 +117,7 @@ void dwconv_kernel(const T* __restrict__ in, int H, int W, int Ho, int Wo, int C
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[py][p][e] = 0.f;
         const T* src = in + (int64_t)b * H * W * Cp + c8;
-#if DW_ROLL
-#pragma unroll 1
-#else
 #pragma unroll
-#endif
         for (int r = 0; r < NROW; ++r) {
             const int iy = oy0 * ST - PAD + r;
             if (iy < 0 || iy >= H) continue;
@@ -395,8 +379,7 @@ template <typename T, int KS, int ST, int KIN, int TH, int TW, int PIX, int CC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MbGeo<KS, ST, KIN, TH, TW, CC>::WPE, MbGeo<KS, ST, KIN, TH, TW, CC>::WPE))) void mbconv_kernel(const MbArgs p) {
     // f16 outputs saturate through MODE.FP16_OVFL (common.h): no clamp instructions.  With the bit set the MFMAs treat a NaN operand as 0
     // (scripts/micro/mfma_nan.hip), so it is set per pair of pixel groups, behind their MFMAs and in front of their conversions, and around the
-    // depthwise stage (MBCONV_MODE_TOGGLE; 0 = round 4's form, the bit set once at the top: the A side of profiles/r05b_mbconv_mode.txt).
-    if (!MBCONV_MODE_TOGGLE) AVX_F16_SATURATE_ON();
+    // depthwise stage (measured against the bit set once at the top: profiles/r05b_mbconv_mode.txt).
     typedef typename Half<T>::v8 v8;
     typedef typename Half<T>::v4 v4;
     typedef MbGeo<KS, ST, KIN, TH, TW, CC> G;
@@ -497,7 +480,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MbGeo<KS, S
                     accs[u][mt] = acc;
                 }
             }
-            if (MBCONV_MODE_TOGGLE) AVX_F16_SAT_BEGIN();
+            AVX_F16_SAT_BEGIN();
 #pragma unroll
             for (int u = 0; u < NG; ++u) {
                 const int pix = (wave + 4 * (j0 + u)) * 16 + lr;
@@ -514,7 +497,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MbGeo<KS, S
                     *(a_i32x2m*)(s_exp + pix * ESTR + (16 * mt + 4 * lq) * 2) = hb;
                 }
             }
-            if (MBCONV_MODE_TOGGLE) AVX_F16_SAT_END();
+            AVX_F16_SAT_END();
         };
         // every wave has NPG / 4 groups, the first NPG % 4 waves one more
 #pragma unroll
@@ -527,7 +510,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MbGeo<KS, S
             cur = nxt;
         }
         __syncthreads();
-        if (MBCONV_MODE_TOGGLE) AVX_F16_SAT_BEGIN();      // the depthwise stage's output conversions; cleared at the end of the chunk
+        AVX_F16_SAT_BEGIN();      // the depthwise stage's output conversions; cleared at the end of the chunk
         float psum[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) psum[e] = 0.f;
@@ -598,7 +581,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MbGeo<KS, S
             for (int r = 0; r < 16; ++r) s += s_red[r * CC + tid];
             p.part[((int64_t)b * gridDim.x + blockIdx.x) * cp + c + tid] = s;
         }
-        if (MBCONV_MODE_TOGGLE) AVX_F16_SAT_END();      // the next chunk's MFMAs run with MODE.FP16_OVFL clear
+        AVX_F16_SAT_END();      // the next chunk's MFMAs run with MODE.FP16_OVFL clear
     }
     ovf_commit<T>(p.ovf, ovf_mx);
 }

@@ -20,29 +20,9 @@
 #include "common.h"
 #include "gemm_epi.h"
 
-#ifndef GEMM_PEEL
-#define GEMM_PEEL 1       // 1: K-tile 0 of every output tile is a copy of the loop body whose first MFMA per accumulator has C = 0 (no zeroing pass); 0: A/B
-#endif
-#ifndef GEMM_SADDR
-#define GEMM_SADDR 0      // 1 (A/B builds): the streaming kernel's LDS-DMA addresses as scalar base + 32-bit lane offset instead of 64-bit pointers per lane.
-                          // MEASURED (profiles/r04w_epilogue_instructions.txt): the six DMAs of a K-tile's main path lose their v_lshl_add_u64, eight registers
-                          // come free -- and the step is 0.2 % SLOWER (every shape within +-0.4 %): the scalar unit now forms each base (s_mul / s_addc chains
-                          // between the s_mov m0 writes).  Not the default.
-#endif
-#ifndef GEMM_LNA_PK
-#define GEMM_LNA_PK 1     // 1: EPI 1's folded LayerNorm as packed FMAs on column pairs (0: four scalar fmaf, A/B)
-#endif
-#ifndef GEMM_GELU_H
-#define GEMM_GELU_H 1     // 1: the streaming kernel's bias + GELU epilogue (half output) evaluates the degree-4 fit; 0: the degree-6 one (A/B)
-#endif
-#ifndef GEMM_HW_SAT
-#define GEMM_HW_SAT 1      // 1: the kernels of this file set MODE.FP16_OVFL around their epilogues (NOT while their MFMAs run: common.h) and their f16 outputs saturate through it instead of a v_med3_f32 per element
-#endif
-#if GEMM_HW_SAT
+// The kernels of this file set MODE.FP16_OVFL around their epilogues (NOT while their MFMAs run: common.h), so their f16 outputs
+// saturate in hardware instead of through a v_med3_f32 per element (profiles/r04u_fp16_ovfl.txt)
 #define HFROM(x) Half<T>::from_hw(x)
-#else
-#define HFROM(x) Half<T>::from(x)      // the software clamp (v_med3_f32 per element): the A side of profiles/r04u_fp16_ovfl.txt
-#endif
 
 namespace { template <int N> struct a_ic { static constexpr int value = N; }; }
 namespace {
@@ -194,7 +174,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(avx::GemmArgs p) {
         }
         return;
     }
-    if (GEMM_HW_SAT) AVX_F16_SAT_BEGIN();      // every MFMA of this workgroup has been issued: the f16 conversions below saturate in hardware (common.h)
+    AVX_F16_SAT_BEGIN();      // every MFMA of this workgroup has been issued: the f16 conversions below saturate in hardware (common.h)
     AVX_CLAMP_TOKEN(inva);
     const float alpha = p.alpha;
     float ovf_mx = 0.f;
@@ -238,7 +218,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(avx::GemmArgs p) {
 // split-K partials [S][M][N] -> the epilogue of gemm_nt_kernel on their sum (added in split order: reproducible).  One thread = 4 columns.
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_epilogue_kernel(avx::GemmArgs p, int S) {
-    if (GEMM_HW_SAT) AVX_F16_SATURATE_ON();
+    AVX_F16_SATURATE_ON();
     AVX_CLAMP_TOKEN(inva);
     typedef typename Half<T>::v4 v4;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(avx::GemmArgs p, i
 // Same per-row arithmetic as layernorm_half_kernel (two-pass statistics in registers, (v - mean) * rstd * w + b).
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_ln_epilogue_kernel(avx::GemmArgs p, int S) {
-    if (GEMM_HW_SAT) AVX_F16_SATURATE_ON();
+    AVX_F16_SATURATE_ON();
     typedef typename Half<T>::v4 v4;
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -415,20 +395,15 @@ constexpr int STAGE2 = 2 * T2 * BK * 2;   // 65536: W tile (32 KiB) + X tile (32
         xf[j][0] = *(const v8*)(r + foff0);                                                    \
         xf[j][1] = *(const v8*)(r + foff1);                                                    \
     }
-// AVX_SNAKE: walk the 4 x 4 MFMA grid boustrophedon so that consecutive MFMAs share one operand register (the B fragment stays when
-// the A fragment changes): operand toggling is worth a few percent of MFMA power (profiles/r01h_mfma_power.txt)
-// GEMM_NT: the 256-tile kernels' output stores carry the non-temporal hint.  Outputs are hundreds of MB per launch and are read next by
+// The 256-tile kernels' output stores carry the non-temporal hint.  Outputs are hundreds of MB per launch and are read next by
 // another kernel: letting them allocate in the 4 MiB L2 evicts the A / weight panels the next K-tiles need (profiles/r01h_gemm_nt.txt)
-#ifndef GEMM_NT
-#define GEMM_NT 1
-#endif
 template <typename V>
 static __device__ __forceinline__ void st_out(V* ptr, const V& v, int nt) {
     static_assert(sizeof(V) == 16, "16-byte stores only");
     typedef int i32x4_st __attribute__((ext_vector_type(4)));
     // the hinted store is inline asm: written as a builtin next to the plain store, the two branches are merged into ONE plain store
     // (the !nontemporal metadata is dropped) and the hint silently disappears
-    if (GEMM_NT && (nt & 1)) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(ptr), "v"(__builtin_bit_cast(i32x4_st, v)) : "memory");   // s_nop 1: the hazard recogniser does not see a store in an asm block; on gfx940+/gfx950 a VMEM store of more than 64 bits followed by a VALU write of its data registers needs TWO wait states
+    if (nt & 1) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(ptr), "v"(__builtin_bit_cast(i32x4_st, v)) : "memory");   // s_nop 1: the hazard recogniser does not see a store in an asm block; on gfx940+/gfx950 a VMEM store of more than 64 bits followed by a VALU write of its data registers needs TWO wait states
     else *ptr = v;
 }
 // (buf_rsrc, buf_st16, buf_ld16 -- raw-buffer access of the fast epilogues -- live in gemm_epi.h)
@@ -438,17 +413,15 @@ static int gemm_nt_mode(const avx::GemmArgs& a) {
     if ((mode & 4) && a.N <= 768) return 0;
     return mode & 1;
 }
-#ifndef AVX_SNAKE
-#define AVX_SNAKE 1
-#endif
 // (KT0: the first K-tile of an output tile -- its first MFMA per accumulator takes a literal zero as C, so the 128 accumulator registers are
-// never zeroed by v_mov_b32)
+// never zeroed by v_mov_b32.)  The 4 x 4 MFMA grid is walked boustrophedon so that consecutive MFMAs share one operand register (the B
+// fragment stays when the A fragment changes): operand toggling is worth a few percent of MFMA power (profiles/r01h_mfma_power.txt)
 #define AVX_HALF(hw)                                                                           \
     __builtin_amdgcn_s_setprio(1);                                                             \
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                           \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                              \
     _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                                         \
-        const int j = AVX_SNAKE && (i & 1) ? 3 - jj : jj;                                      \
+        const int j = (i & 1) ? 3 - jj : jj;                                                   \
         acc[4 * (hw) + i][j] = mfma16(wf[i][ks], xf[j][ks], (KT0 && ks == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[4 * (hw) + i][j]);             \
     }                                                                                          \
     __builtin_amdgcn_s_setprio(0);
@@ -458,7 +431,7 @@ static int gemm_nt_mode(const avx::GemmArgs& a) {
     __builtin_amdgcn_sched_barrier(0);
 
 
-// (seg8_sum, seg8_sum2, stats8 -- the row-statistics helpers both residual epilogues use -- live in gemm_epi.h: gemm_row.hip shares them)
+// (seg8_sum2, stats8 -- the row-statistics helpers of the residual epilogues -- live in gemm_epi.h)
 
 // ---------------------------------------------------------------------------------------------
 // The 256-tile kernel: the half-tile pipeline above as ONE CONTINUOUS K STREAM over a persistent workgroup's tiles (one
@@ -483,31 +456,8 @@ static_assert(L5_ROWS + 4096 <= 32768, "EPI 1 scratch above the stages");
 #ifndef GEMM_NOSTORE
 #define GEMM_NOSTORE 0   // diagnostic builds: 1 drops the half-only epilogue's global stores (is the tile start waiting for them?)
 #endif
-#ifndef GEMM_XCD_WALK
-#define GEMM_XCD_WALK 0
-#endif
 #ifndef GEMM_NOEPI
 #define GEMM_NOEPI 0
-#endif
-#ifndef GEMM_COL_WALK
-#define GEMM_COL_WALK 0     // 1: AVEX_AMD_GEMM_TILE_ORDER=-n selects the column-group walk (A/B builds; the scalar code of a third walk in
-                            // set_tile is kept out of the default kernel: it sits inside the K loop's second-to-last iteration)
-#endif
-#ifndef GEMM_GELU_CHAINS
-#define GEMM_GELU_CHAINS 0  // EPI 1: 1 = the activation of a 16-row chunk as 8 chains side by side (gelu_erf2xN); fewer stall cycles, same
-                            // instructions: fc1 -0.3 %, QKV +1.1 % (profiles/r04h_epilogue_ab2.txt) -- under the power cap stall cycles are not the currency
-#endif
-#ifndef GEMM_EPI2_EARLY
-#define GEMM_EPI2_EARLY 0
-#endif
-#ifndef GEMM_W_POLICY
-#define GEMM_W_POLICY 0
-#endif
-#ifndef GEMM_A_POLICY
-#define GEMM_A_POLICY 0
-#endif
-#ifndef GEMM_EPI1_SWAP
-#define GEMM_EPI1_SWAP 0   // EPI 1: 0 = transpose through a private LDS slab (default), 1 = in registers with v_permlane16_swap (A/B builds; measured SLOWER, see below)
 #endif
 
 template <typename T, int EPI, int LN, int ACT>
@@ -534,15 +484,12 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = (gridDim.x + 7) >> 3;
     int m0 = 0, n0 = 0;
 
-    // operand addresses of the LDS-DMA: a UNIFORM base per tile (the tile's first W row / A row: scalar registers) + a 32-bit byte offset per
-    // lane, so that the instruction takes the base from SGPRs and the K-tile's advance is scalar arithmetic.  As per-lane 64-bit pointers
-    // (GEMM_SADDR 0) every DMA cost a v_lshl_add_u64: eight 64-bit vector adds per K-tile and wave, and sixteen registers instead of eight.
-#if GEMM_SADDR
-    unsigned wsrc[2][2], xsrc[2][2];
-#else
+    // operand addresses of the LDS-DMA: a 64-bit pointer per lane.  A uniform base per tile (scalar registers) + a 32-bit byte offset per
+    // lane saves every DMA its v_lshl_add_u64 (eight 64-bit vector adds per K-tile and wave) and eight registers -- and measured 0.2 %
+    // SLOWER on the step (every shape within +-0.4 %): the scalar unit then forms each base, s_mul / s_addc chains between the s_mov m0
+    // writes (profiles/r04w_epilogue_instructions.txt).
     const T* wsrc[2][2];
     const T* xsrc[2][2];
-#endif
     int wdst[2][2], xdst[2][2];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -553,81 +500,40 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
         }
     // grouped walk where a group of 8 A panels fits the L2 (K < 2048: QKV, out_proj, fc1); measured against the row-major walk: fc1 +3 %,
     // out_proj +3 %, QKV +-0, whole step +1.4 %; HBM fetch per fc1 launch 1.57 -> 0.97 GB (profiles/r01g_gemm_tile_order.txt).
-    // At K = 3072 a group would be 12.6 MB: row-major there.
+    // At K = 3072 a group would be 12.6 MB: row-major there.  (A COLUMN-group walk, which keeps a group of weight panels in an XCD's L2,
+    // fetched less with a non-temporal A stream -- fc1 882 -> 528 MB -- and took longer in every form: profiles/r06c_walks.txt.)
     const bool grouped = p.tile_order >= 2 || (p.tile_order == 0 && p.K < 2048);
     const int group_m = p.tile_order >= 2 ? p.tile_order : 8;
-    // tile_order < 0: COLUMN-group walk, -tile_order column tiles per group.  Tile ids run (column group, row panel, column inside the
-    // group) and every XCD owns a contiguous eighth of them (xw below): an XCD keeps one group of weight panels (e.g. 6 x 393 KB) for
-    // hundreds of tiles while the A row panels stream past ONCE per group -- the row-group walk above re-fetches a group's A panels for
-    // every round of column tiles once 32 concurrent tiles have pushed 4.7 MB through a 4 MiB L2 (roofline.traffic_by_shape).
-    const bool colwalk = GEMM_COL_WALK && p.tile_order < 0;
-    const int group_n = colwalk ? (-p.tile_order < tiles_n ? -p.tile_order : tiles_n) : 1;
     auto set_tile = [&](int tile) __attribute__((always_inline)) {
         int tm, tn;
-        if (colwalk) {
-            const int per_group = tiles_m * group_n;
-            const int gid = tile / per_group;
-            const int first_n = gid * group_n;
-            const int gsz = (tiles_n - first_n) < group_n ? (tiles_n - first_n) : group_n;
-            const int r = tile - gid * per_group;
-            tm = r / gsz;
-            tn = first_n + (r - tm * gsz);
-        } else if (grouped) tile_coords(tile, tiles_m, tiles_n, group_m, tm, tn);
+        if (grouped) tile_coords(tile, tiles_m, tiles_n, group_m, tm, tn);
         else { tm = tile / tiles_n; tn = tile - tm * tiles_n; }
         m0 = tm * T2; n0 = tn * T2;
-#if GEMM_SADDR
-        m0 = __builtin_amdgcn_readfirstlane(m0); n0 = __builtin_amdgcn_readfirstlane(n0);      // scalar registers, said explicitly: the DMA bases are formed from them
-        const int last = p.M - 1 - m0;                       // rows past M read row M - 1 (their outputs are never stored)
-#endif
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int wr = 128 * q + 64 * h + 8 * wid + (lane >> 3);
                 const int xr = 128 * q + 64 * (wid >> 2) + 32 * h + 8 * (wid & 3) + (lane >> 3);
-#if GEMM_SADDR
-                wsrc[h][q] = (unsigned)(((int64_t)wr * p.ldw + (((lane & 7) ^ ((wr >> 1) & 7)) << 3)) * 2);
-                const int ar = xr < last ? xr : last;
-                xsrc[h][q] = (unsigned)(((int64_t)ar * p.lda + (((lane & 7) ^ ((xr >> 1) & 7)) << 3)) * 2);
-#else
                 wsrc[h][q] = W + (int64_t)(n0 + wr) * p.ldw + (((lane & 7) ^ ((wr >> 1) & 7)) << 3);
                 int arow = m0 + xr;
                 arow = arow < p.M ? arow : p.M - 1;
                 xsrc[h][q] = A + (int64_t)arow * p.lda + (((lane & 7) ^ ((xr >> 1) & 7)) << 3);
-#endif
             }
     };
-    // GEMM_W_POLICY / GEMM_A_POLICY (A/B builds): cache-policy bits of the two operand streams' LDS-DMA (0 default, 2 = nt: stream, evict first).
-    // Measured (profiles/r04g_epilogue_ab.txt, r04h_epilogue_ab2.txt): W nt 6 - 24 % slower on every shape; A nt 13 - 15 % slower on QKV / fc1
-    // and 8 % FASTER on out_proj stand-alone -- but chosen per product inside the step (N <= 768 only) it still LOSES 0.8 %: what it
-    // pushes out of the caches are the next kernels' inputs.  (As a run-time branch around each DMA pair it also cost the loop 1.5 %.)
+    // The two operand streams' LDS-DMA keep the default cache policy.  With the nt bit (stream, evict first) W measured 6 - 24 % slower on
+    // every shape; A 13 - 15 % slower on QKV / fc1 and 8 % FASTER on out_proj stand-alone -- but chosen per product inside the step (N <= 768
+    // only) it still LOST 0.8 %: what it pushes out of the caches are the next kernels' inputs (profiles/r04g_epilogue_ab.txt,
+    // r04h_epilogue_ab2.txt).
     auto dma_w = [&](int h, int kt, int stg) __attribute__((always_inline)) {
         char* base = smem + stg * STAGE2;
-#if GEMM_SADDR
-        const char* wk = (const char*)(W + (int64_t)n0 * p.ldw) + (int64_t)kt * (BK * 2);      // from the (scalar) tile coordinates every time: as a loop-carried pointer the base ends up in vector registers
-        // (the W offsets never change: left visible, their zero-extension is hoisted out of the loop as a 64-bit register pair and the DMA is
-        // back to a 64-bit vector address + v_lshl_add_u64; the empty asm keeps the extension at the instruction, where it is free)
-        unsigned w0 = wsrc[h][0], w1 = wsrc[h][1];
-        asm volatile("" : "+v"(w0), "+v"(w1));
-        __builtin_amdgcn_global_load_lds((gptr_t*)(wk + w0), (lptr_t*)(base + wdst[h][0]), 16, 0, GEMM_W_POLICY);
-        __builtin_amdgcn_global_load_lds((gptr_t*)(wk + w1), (lptr_t*)(base + wdst[h][1]), 16, 0, GEMM_W_POLICY);
-#else
-        __builtin_amdgcn_global_load_lds((gptr_t*)(wsrc[h][0] + kt * BK), (lptr_t*)(base + wdst[h][0]), 16, 0, GEMM_W_POLICY);
-        __builtin_amdgcn_global_load_lds((gptr_t*)(wsrc[h][1] + kt * BK), (lptr_t*)(base + wdst[h][1]), 16, 0, GEMM_W_POLICY);
-#endif
+        __builtin_amdgcn_global_load_lds((gptr_t*)(wsrc[h][0] + kt * BK), (lptr_t*)(base + wdst[h][0]), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t*)(wsrc[h][1] + kt * BK), (lptr_t*)(base + wdst[h][1]), 16, 0, 0);
     };
     auto dma_x = [&](int h, int kt, int stg) __attribute__((always_inline)) {
         char* base = smem + stg * STAGE2;
-#if GEMM_SADDR
-        const char* ak = (const char*)(A + (int64_t)m0 * p.lda) + (int64_t)kt * (BK * 2);
-        unsigned x0 = xsrc[h][0], x1 = xsrc[h][1];
-        asm volatile("" : "+v"(x0), "+v"(x1));
-        __builtin_amdgcn_global_load_lds((gptr_t*)(ak + x0), (lptr_t*)(base + xdst[h][0]), 16, 0, GEMM_A_POLICY);
-        __builtin_amdgcn_global_load_lds((gptr_t*)(ak + x1), (lptr_t*)(base + xdst[h][1]), 16, 0, GEMM_A_POLICY);
-#else
-        __builtin_amdgcn_global_load_lds((gptr_t*)(xsrc[h][0] + kt * BK), (lptr_t*)(base + xdst[h][0]), 16, 0, GEMM_A_POLICY);
-        __builtin_amdgcn_global_load_lds((gptr_t*)(xsrc[h][1] + kt * BK), (lptr_t*)(base + xdst[h][1]), 16, 0, GEMM_A_POLICY);
-#endif
+        __builtin_amdgcn_global_load_lds((gptr_t*)(xsrc[h][0] + kt * BK), (lptr_t*)(base + xdst[h][0]), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t*)(xsrc[h][1] + kt * BK), (lptr_t*)(base + xdst[h][1]), 16, 0, 0);
     };
     constexpr bool fast_half = EPI == 1, fast_resid = EPI == 2;
     constexpr bool LNA = EPI == 1 && (LN & 1), LNR = EPI == 2 && (LN & 1), STATS = EPI == 2 && (LN & 2);
@@ -663,17 +569,14 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
     v8 wf[4][2], xf[4][2];
     unsigned long long ovf_lanes = 0ull;      // range alarm: lanes that clipped a value in any tile so far (scalar registers)
 
-    // GEMM_XCD_WALK 1 (A/B builds): each XCD owns a CONTIGUOUS eighth of the logical tile ids and walks it 32 ids per round, so that a
-    // group's A panels could stay in that XCD's L2 from one round to the next.  MEASURED: no change in time (+-0.1 % on the step) and
-    // none in L2-miss bytes (QKV 806 -> 860 MB, fc1 879 -> 997 MB per launch, scripts/pmc_gemm_shapes.sh): 32 concurrent 256 x 256 tiles
-    // touch at least 11.3 operand panels of 393 KB (K = 768) per round, 4.4 MB against 4 MB of L2, so under LRU nothing survives from
-    // one round to the next whichever XCD runs it; the fetch counter sits at rounds x that footprint (the floor of this tiling), and
-    // what it counts is L2 <-> fabric traffic, of which the 256 MB Infinity Cache absorbs the A re-reads (A is 195 MB).
-    const bool xw = GEMM_XCD_WALK || colwalk;
-    const int t_lo = xw ? (int)(((int64_t)ntiles * xcd) >> 3) : 0;
-    const int t_hi = xw ? (int)(((int64_t)ntiles * (xcd + 1)) >> 3) : ntiles;
-    int tile = xw ? t_lo + slot : (0 * 8 + xcd) * per_xcd + slot;
-    if (tile >= t_hi) return;
+    // (Giving each XCD a CONTIGUOUS eighth of the logical tile ids instead, so that a group's A panels could stay in that XCD's L2 from one
+    // round to the next, MEASURED no change in time (+-0.1 % on the step) and none in L2-miss bytes (QKV 806 -> 860 MB, fc1 879 -> 997 MB
+    // per launch, scripts/pmc_gemm_shapes.sh): 32 concurrent 256 x 256 tiles touch at least 11.3 operand panels of 393 KB (K = 768) per
+    // round, 4.4 MB against 4 MB of L2, so under LRU nothing survives from one round to the next whichever XCD runs it; the fetch counter
+    // sits at rounds x that footprint (the floor of this tiling), and what it counts is L2 <-> fabric traffic, of which the 256 MB
+    // Infinity Cache absorbs the A re-reads (A is 195 MB).)
+    int tile = xcd * per_xcd + slot;
+    if (tile >= ntiles) return;
     set_tile(tile);
     dma_aux(n0, m0, 0);
     tile_prologue();
@@ -682,12 +585,12 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
     AVX_BAR();
     if (wm == 1) { AVX_BAR(); }      // stagger: waves 4-7 run one barrier behind, for the whole tile walk
     int g0 = 0;                      // global K-tile index of the tile's first K-tile: its stage parity
-    // EPI 1 (and EPI 2 in GEMM_EPI2_EARLY builds): the epilogue's trailing stores are COUNTED PAST by the next tile's first wait instead of
-    // waited for (see the B phase of K-tile 0 below).  Their number is exact since the stores became raw-buffer stores that always issue
-    // (rows past M are dropped by the bounds check, not skipped by an exec mask): 16 output stores per wave, EPI 2 with statistics 16 more,
-    // interleaved -- whichever form, at least the last 16 vector-memory operations before the new tile's DMAs are epilogue operations
-    // that need not have retired.  For EPI 2 it measured level (out_proj) to 1 % slower (fc2): profiles/r04h_epilogue_ab2.txt; not the default.
-    constexpr bool early_w1 = (EPI == 1 || (GEMM_EPI2_EARLY && EPI == 2)) && !GEMM_NOSTORE && !GEMM_NOEPI;
+    // EPI 1: the epilogue's trailing stores are COUNTED PAST by the next tile's first wait instead of waited for (see the B phase of
+    // K-tile 0 below).  Their number is exact since the stores became raw-buffer stores that always issue (rows past M are dropped by the
+    // bounds check, not skipped by an exec mask): the last 16 vector-memory operations before the new tile's DMAs are the wave's 16
+    // output stores, which need not have retired.  For EPI 2 the same measured level (out_proj) to 1 % slower (fc2):
+    // profiles/r04h_epilogue_ab2.txt.
+    constexpr bool early_w1 = EPI == 1 && !GEMM_NOSTORE && !GEMM_NOEPI;
 
     // One continuous K stream over this workgroup's tiles: the DMA for the next tile's first K-tiles is issued by the
     // LAST iterations of the current tile exactly as if they were K-tiles nk, nk + 1 of the same product (the source
@@ -695,16 +598,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
     // pipeline never drains: no per-tile prologue, no workgroup turnaround, and the epilogue (private LDS slabs above the
     // stages, no barrier) runs with two K-tiles of the next tile already in flight.
     for (int it = 0;; ++it) {
-#if !GEMM_PEEL
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#endif
         const bool stamp = stamp_on && tile < 8192;
         const int em0 = m0, en0 = n0;
-        const int next_tile = xw ? t_lo + (it + 1) * per_xcd + slot : ((it + 1) * 8 + xcd) * per_xcd + slot;
-        const bool has_next = next_tile < t_hi;
+        const int next_tile = ((it + 1) * 8 + xcd) * per_xcd + slot;
+        const bool has_next = next_tile < ntiles;
         AVX_STAMP(if (stamp) { g_gemm_stamps[4 * tile + 0] = g_gemm_stamps[4 * tile + 1] = __builtin_amdgcn_s_memrealtime(); g_gemm_clk[2 * tile] = __builtin_amdgcn_s_memtime(); });
         auto k_tile = [&](int kt, auto kt0_tag) __attribute__((always_inline)) {
             constexpr bool KT0 = decltype(kt0_tag)::value;
@@ -744,12 +641,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
             AVX_BAR();
         
         };
-#if GEMM_PEEL
         k_tile(0, a_ic<1>{});                              // K-tile 0: C = 0
         for (int kt = 1; kt < nk; ++kt) k_tile(kt, a_ic<0>{});
-#else
-        for (int kt = 0; kt < nk; ++kt) k_tile(kt, a_ic<0>{});
-#endif
         AVX_STAMP(if (stamp && it == 2 && nk < 64 && blockIdx.x < 256) g_gemm_kclk[blockIdx.x * 64 + nk] = __builtin_amdgcn_s_memtime(););
         // Re-align the two wave groups for the epilogue: left staggered, the lagging group cannot pass its last loop barrier before the
         // leading group reaches the next tile's first one, i.e. the two epilogues would run one after the other.
@@ -763,14 +656,16 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
         // ---- epilogue ---------------------------------------------------------------------------
         // Each wave transposes its 128(n) x 64(m) accumulators through a private LDS slab in 16-row chunks, so that global traffic is
         // row-contiguous: a lane owns 8 consecutive n of one row (16-byte f16 / 2 x 16-byte fp32 vectors), 8 lanes cover a 128-byte
-        // line, a wave instruction writes 8 full lines.  (The direct-from-accumulator form, 8-byte stores, ran the store path at ~2 TB/s.)
+        // line, a wave instruction writes 8 full lines.  (The direct-from-accumulator form, 8-byte stores, ran the store path at ~2 TB/s; a
+        // register transpose with v_permlane16_swap stores half lines, 16 rows x 64 bytes per instruction: QKV 6.5 % slower, out_proj 14 %,
+        // profiles/r04g_epilogue_ab.txt.)
         // the epilogue's lane constants (slab addresses, row / column offsets) are derived from an opaque copy of the lane id: computed from
         // `lane` itself they are loop-invariant, get hoisted above the tile loop, and then live -- spilled -- through the K loop
         int le = lane;
         asm volatile("" : "+v"(le));
         const int er = le >> 3, ec = le & 7, lc = le & 15, lg = le >> 4;
         float ovf_mx = 0.f;
-        if (GEMM_HW_SAT) AVX_F16_SAT_BEGIN();      // MODE.FP16_OVFL for the epilogue's conversions only: set, the MFMAs drop NaN operands (common.h)
+        AVX_F16_SAT_BEGIN();      // MODE.FP16_OVFL for the epilogue's conversions only: set, the MFMAs drop NaN operands (common.h)
         AVX_CLAMP_TOKEN(inva);
 
         if constexpr (GEMM_NOEPI && (EPI == 1 || EPI == 2)) {
@@ -783,7 +678,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
         } else if constexpr (fast_half) {
             // bias / GELU (/ the folded LayerNorm of the A rows) in the accumulator layout; the slab holds the converted halves
             // (ds_write_b64 of 4 halves, ds_read_b128 of 8); no uniform branches inside, so the scheduler interleaves the
-            // independent GELU chains of a 64-column slice
+            // independent GELU chains of a 64-column slice.  (Running a chunk's 16 values as 8 chains side by side saved stall cycles, not
+            // time: fc1 -0.3 %, QKV +1.1 %, profiles/r04h_epilogue_ab2.txt -- under the power cap stall cycles are not the currency.)
             const float* lb = ldsbias + (it & 1) * 256 + wm * 128;
             const float* lsv = ldslns + (it & 1) * 256 + wm * 128;
             float2 rst[4];
@@ -791,64 +687,6 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) rst[j] = ((const float2*)(ldsrows + (it & 1) * 512))[wn * 64 + 16 * j + lc];      // (rstd, -mu rstd) of tile row 64 wn + 16 j + lc
             }
-#if GEMM_EPI1_SWAP
-            // (A/B form, NOT the default: profiles/r04g_epilogue_ab.txt -- QKV 6.5 % slower than the slab form below, fc1 1.2 % faster; the
-            //  residual epilogue built the same way was 14 % / 4 % slower on out_proj / fc2.  What it loses is the store shape: 16 rows x 64
-            //  contiguous bytes per instruction instead of 8 rows x 128, i.e. half lines.)
-            // Register transpose instead of an LDS round trip.  After the arithmetic a lane holds, for each of the four 16-column MFMA tiles
-            // i of a 16-row chunk, 4 consecutive columns (16 i + 4 lg ..) of row lc as two registers of halves.  One v_permlane16_swap per
-            // register of a tile PAIR (2 p, 2 p + 1) exchanges the odd rows of 16 lanes of the first tile with the even rows of the second:
-            // a lane then owns 8 CONSECUTIVE columns of row lc -- lanes lg = 0, 2 the two halves of tile 2 p, lanes lg = 1, 3 those of tile
-            // 2 p + 1 -- i.e. one 16-byte store, 64 contiguous bytes per row and instruction (the fabric's request size).  Per chunk:
-            // 4 swaps in place of 4 ds_write_b64 + 2 ds_read_b128 + two lgkmcnt(0) waits (scripts/micro/permlane16.hip checks the rows).
-            const int ldh = (int)p.ldh;
-            const int vrows = p.M - (em0 + wn * 64);
-            const __amdgpu_buffer_rsrc_t obuf = buf_rsrc((const T*)p.out_half + (int64_t)(em0 + wn * 64) * p.ldh + en0 + wm * 128,
-                                                         vrows > 0 ? (unsigned)(vrows < 64 ? vrows : 64) * (unsigned)ldh * 2u : 0u);
-            const int ovoff = (lc * ldh + 16 * (lg & 1) + 8 * (lg >> 1)) * 2;
-#pragma unroll
-            for (int ih = 0; ih < 2; ++ih) {
-                f32x4 bv[4], sv[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) bv[i] = *(const f32x4*)(lb + 64 * ih + 16 * i + 4 * lg);
-                if (LNA) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) sv[i] = *(const f32x4*)(lsv + 64 * ih + 16 * i + 4 * lg);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f32x2 v[8];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            // LayerNorm of the A rows folded in: rstd * acc + ((-mu rstd) * s[n] + bias'[n])
-                            if (LNA) v[2 * i + (e >> 1)][e & 1] = __builtin_fmaf(rst[j].x, acc[4 * ih + i][j][e], __builtin_fmaf(rst[j].y, sv[i][e], bv[i][e]));
-                            else v[2 * i + (e >> 1)][e & 1] = acc[4 * ih + i][j][e] + bv[i][e];
-                        }
-                    }
-                    if constexpr (ACT == 1) gelu_erf2xN<8>(v);
-                    else if constexpr (ACT == 2) {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = silu2(v[q]);
-                    }
-                    unsigned hw[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        ovf_see<T>(ovf_mx, v[q][0], v[q][1]);
-                        typename Half<T>::v4 h2 = {HFROM(v[q][0]), HFROM(v[q][1]), HFROM(0.f), HFROM(0.f)};
-                        hw[q] = __builtin_bit_cast(uint2, h2).x;
-                    }
-#pragma unroll
-                    for (int pr = 0; pr < 2; ++pr) {
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(hw[4 * pr], hw[4 * pr + 2], false, false);          // columns 0, 1 of the lane's four
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(hw[4 * pr + 1], hw[4 * pr + 3], false, false);      // columns 2, 3
-                        const i32x4_buf o = {(int)s0[0], (int)s1[0], (int)s0[1], (int)s1[1]};
-                        if (!GEMM_NOSTORE) buf_st16<GEMM_NT ? 2 : 0>(o, obuf, ovoff + (16 * j * ldh + 64 * ih + 32 * pr) * 2);
-                    }
-                }
-            }
-#else
             constexpr int HP_LD = 72;     // halves per slab row (64 n + 8 pad = 144 B)
             T* slab = (T*)(smem + 2 * STAGE2 + wid * (16 * HP_LD * 2));
             // this wave's 64 rows x 128 columns of the output as a raw buffer that ends with the last valid row (see buf_rsrc)
@@ -868,32 +706,6 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-#if GEMM_GELU_CHAINS
-                    // the chunk's 16 values per lane as 8 pairs, so that the activation runs as 8 chains side by side (gelu_erf2xN)
-                    f32x2 v[8];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            // LayerNorm of the A rows folded in: rstd * acc + ((-mu rstd) * s[n] + bias'[n])
-                            if (LNA) v[2 * i + (e >> 1)][e & 1] = __builtin_fmaf(rst[j].x, acc[4 * ih + i][j][e], __builtin_fmaf(rst[j].y, sv[i][e], bv[i][e]));
-                            else v[2 * i + (e >> 1)][e & 1] = acc[4 * ih + i][j][e] + bv[i][e];
-                        }
-                    }
-                    if constexpr (ACT == 1) gelu_erf2xN<8>(v);
-                    else if constexpr (ACT == 2) {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = silu2(v[q]);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        ovf_see<T>(ovf_mx, v[2 * i][0], v[2 * i][1]);
-                        ovf_see<T>(ovf_mx, v[2 * i + 1][0], v[2 * i + 1][1]);
-                        v4 h;
-                        h[0] = HFROM(v[2 * i][0]); h[1] = HFROM(v[2 * i][1]); h[2] = HFROM(v[2 * i + 1][0]); h[3] = HFROM(v[2 * i + 1][1]);
-                        *(v4*)(slab + lc * HP_LD + 16 * i + 4 * lg) = h;
-                    }
-#else
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         f32x4 v;
@@ -901,39 +713,31 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
                             // LayerNorm of the A rows folded in: rstd * acc + ((-mu rstd) * s[n] + bias'[n]).  Written on column PAIRS: as four
                             // scalar fmaf the compiler kept them scalar (256 v_fma_f32 per 128 outputs of a lane: half of QKV's epilogue arithmetic);
                             // v_pk_fma_f32 with the row's two scalars broadcast does a pair per slot.  Same operations: same bits.
-#if GEMM_LNA_PK
                             const f32x2 rx = {rst[j].x, rst[j].x}, ry = {rst[j].y, rst[j].y};
                             const f32x4 a4 = acc[4 * ih + i][j];
                             const f32x2 lo = __builtin_elementwise_fma(rx, (f32x2){a4[0], a4[1]}, __builtin_elementwise_fma(ry, (f32x2){sv[i][0], sv[i][1]}, (f32x2){bv[i][0], bv[i][1]}));
                             const f32x2 hi = __builtin_elementwise_fma(rx, (f32x2){a4[2], a4[3]}, __builtin_elementwise_fma(ry, (f32x2){sv[i][2], sv[i][3]}, (f32x2){bv[i][2], bv[i][3]}));
                             v = (f32x4){lo[0], lo[1], hi[0], hi[1]};
-#else
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                v[e] = __builtin_fmaf(rst[j].x, acc[4 * ih + i][j][e], __builtin_fmaf(rst[j].y, sv[i][e], bv[i][e]));
-#endif
                         } else {
                             v = acc[4 * ih + i][j] + bv[i];
                         }
-                        if constexpr (ACT == 1) v = GEMM_GELU_H ? gelu_erf4_h(v, inva) : gelu_erf4(v);      // half output: the degree-4 fit (common.h)
+                        if constexpr (ACT == 1) v = gelu_erf4_h(v, inva);      // half output: the degree-4 fit (common.h)
                         else if constexpr (ACT == 2) v = silu4(v);
                         ovf_see4<T>(ovf_mx, v);
                         v4 h;
                         h[0] = HFROM(v[0]); h[1] = HFROM(v[1]); h[2] = HFROM(v[2]); h[3] = HFROM(v[3]);
                         *(v4*)(slab + lc * HP_LD + 16 * i + 4 * lg) = h;
                     }
-#endif
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
                     for (int ps = 0; ps < 2; ++ps) {
                         const int ml = 8 * ps + er;
                         const v8 h = *(const v8*)(slab + ml * HP_LD + 8 * ec);
-                        if (!GEMM_NOSTORE) buf_st16<GEMM_NT ? 2 : 0>(h, obuf, ovoff + (16 * j + 8 * ps) * ldh * 2 + 128 * ih);
+                        if (!GEMM_NOSTORE) buf_st16<2>(h, obuf, ovoff + (16 * j + 8 * ps) * ldh * 2 + 128 * ih);
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // slab reads done before the next chunk overwrites it
                 }
             }
-#endif
         } else if constexpr (fast_resid) {
             // out = half( resid * alpha + acc + bias ), the sum formed in fp32 AFTER the transpose (fp32 slab), so the residual is read and the
             // result written as row-contiguous 16-byte vectors and nothing is rounded twice.  LNR: resid = LayerNorm(lnr_y) applied on the
@@ -1025,7 +829,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
                     v8 h;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { h[e] = HFROM(o0[e]); h[4 + e] = HFROM(o1[e]); }
-                    buf_st16<GEMM_NT ? 2 : 0>(h, obuf, ovoff + (16 * j + 8 * ps) * ldh * 2 + 128 * ih);
+                    buf_st16<2>(h, obuf, ovoff + (16 * j + 8 * ps) * ldh * 2 + 128 * ih);
                     if (STATS) {
                         // partial LayerNorm statistics of the row segment (64 columns = the 8 lanes that share er), from the fp32 values
                         // (the rounding of the stored row moves the sums by ~2^-11 / sqrt(64) relative: far below LayerNorm's own error)
@@ -1173,7 +977,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
             }
         }
         ovf_lanes |= ovf_mask<T>(ovf_mx);
-        if (GEMM_HW_SAT) AVX_F16_SAT_END();
+        AVX_F16_SAT_END();
         AVX_STAMP(if (stamp) g_gemm_stamps[4 * tile + 3] = __builtin_amdgcn_s_memrealtime(););
         if (!has_next) break;
         {   // the next tile's 8 source pointers (16 registers) are computed a second time here instead of being carried through the
@@ -1264,7 +1068,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const avx::GemmArgs p)
             load_rows(blk, af);
         }
         if constexpr (SCALE) {
-            if (GEMM_HW_SAT) AVX_F16_SAT_BEGIN();      // (the conversions of the scaled rows; cleared again in front of the MFMAs below)
+            AVX_F16_SAT_BEGIN();      // (the conversions of the scaled rows; cleared again in front of the MFMAs below)
             // A rows scaled per (clip, input channel) on their way into the product: EfficientNet's squeeze-excitation rescale without its
             // own pass over the expanded tensor.  Same arithmetic as scale_channels_kernel (fp32 product, rounded to the operand type).
 #pragma unroll
@@ -1287,7 +1091,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const avx::GemmArgs p)
         constexpr int NTP = (NT > 8 && NT % 8 == 0) ? 8 : NT;
 #pragma unroll
         for (int np = 0; np < NT; np += NTP) {
-            if (GEMM_HW_SAT && (SCALE || np > 0 || blk != blk0)) AVX_F16_SAT_END();      // MFMAs run with MODE.FP16_OVFL clear (common.h)
+            if (SCALE || np > 0 || blk != blk0) AVX_F16_SAT_END();      // MFMAs run with MODE.FP16_OVFL clear (common.h)
             f32x4 acc[NTP][2];
 #pragma unroll
             for (int nt = 0; nt < NTP; ++nt) { acc[nt][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[nt][1] = acc[nt][0]; }
@@ -1301,7 +1105,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const avx::GemmArgs p)
                     acc[nt][1] = mfma16(wf, af[ks][1], acc[nt][1]);
                 }
             }
-            if (GEMM_HW_SAT) AVX_F16_SAT_BEGIN();
+            AVX_F16_SAT_BEGIN();
             AVX_CLAMP_TOKEN(inva);
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
@@ -1385,6 +1189,11 @@ static int launch_skinny_any(const avx::GemmArgs& a, hipStream_t s) {
 
 template <typename T>
 int launch(const avx::GemmArgs& a, hipStream_t s) {
+    if (a.variant == 8) {      // the number of a removed full-row kernel that gave variant 5's bits: another name of variant 5
+        avx::GemmArgs b = a;
+        b.variant = 5;
+        return launch<T>(b, s);
+    }
     // variant 7 / auto for long thin products: the skinny streaming kernel (W resident in LDS, A rows straight into MFMA operands)
     AVX_REQUIRE(!a.a_scale || ((a.variant == 7 || a.variant == 1) && a.a_scale_rows > 0 && a.a_scale_ld >= a.K && a.a_scale_ld % 4 == 0),
                 "gemm: a_scale is built for the skinny kernel (variant 7) and the register-staged 128-tile kernel (variant 1)");
@@ -1395,22 +1204,9 @@ int launch(const avx::GemmArgs& a, hipStream_t s) {
     if (a.variant == 0 && a.M >= 32768 && a.K % 64 == 0 && (a.N == 64 || a.N % 128 == 0) && !a.out_raw && skinny_ok(a) &&
         (a.N % BN != 0 || (!(getenv("AVEX_AMD_GEMM_SKINNY") && atoi(getenv("AVEX_AMD_GEMM_SKINNY")) == 0) && !getenv("AVEX_AMD_GEMM_VARIANT"))))
         return launch_skinny_any<T>(a, s);
-    // variant 8: the full-row residual kernel (gemm_row.hip), bit-identical to the streaming kernel.  NOT chosen automatically: measured on the
-    // attention output projection (126 976 rows, K = 768) it takes 228 us against 206 for the streaming kernel + ln_rowstats, on fc2's shape 25 %
-    // longer (profiles/r06b_gemm_row.txt: its 48 KiB of weights per 32-deep k-step arrive at the CU's L2 -> LDS rate, not at the MFMA rate).
-    // AVEX_AMD_GEMM_ROW=1 selects it for N = 768 products from 32 768 rows (A/B inside one process), AVEX_AMD_GEMM_ROW_KMAX bounds K.
-    if (a.variant == 8) {
-        AVX_REQUIRE(avx::gemm_row_ok(a), "gemm: variant 8 (full-row kernel) takes N = 768, K %% 32 == 0, K >= 128, a half output with bias and a half or LayerNorm-folded residual only (N=%d K=%d)", a.N, a.K);
-        return avx::gemm_row(a, __is_same(T, _Float16) ? AVEXHIP_F16 : AVEXHIP_BF16, s);
-    }
-    if (a.variant == 0 && a.N == 768 && a.M >= 32768 && avx::gemm_row_ok(a) && !getenv("AVEX_AMD_GEMM_VARIANT") && !getenv("AVEX_AMD_GEMM_GENERIC")) {
-        const char* er = getenv("AVEX_AMD_GEMM_ROW");      // read per launch: A/B runs switch it inside one process
-        const char* ek = getenv("AVEX_AMD_GEMM_ROW_KMAX");
-        if (er && atoi(er) != 0 && a.K <= (ek ? atoi(ek) : 1024)) return avx::gemm_row(a, __is_same(T, _Float16) ? AVEXHIP_F16 : AVEXHIP_BF16, s);
-    }
     if (a.rows_out) {
         // no kernel below finishes the row statistics: partials to stats_out, then ln_rowstats
-        AVX_REQUIRE(a.stats_out, "gemm: rows_out without the full-row kernel needs stats_out as scratch");
+        AVX_REQUIRE(a.stats_out, "gemm: rows_out needs stats_out as scratch");
         avx::GemmArgs b = a;
         b.rows_out = nullptr;
         const int rc = launch<T>(b, s);
@@ -1549,7 +1345,7 @@ int gemm(const GemmArgs& a, int dtype, hipStream_t s) {
         avexhip_set_error("gemm: unknown dtype %d", dtype);
         return AVEXHIP_ERR_INVALID;
     }
-    if (a.gelu == 1 && GEMM_GELU_H && a.out_half && !a.out_f32) {
+    if (a.gelu == 1 && a.out_half && !a.out_f32) {
         // GELU whose only consumer reads the operand type: the degree-4 fit, in whichever kernel and epilogue form runs (activation code 6)
         GemmArgs b = a;
         b.gelu = 6;

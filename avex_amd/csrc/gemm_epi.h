@@ -1,5 +1,6 @@
-// Row-statistics helpers of the residual epilogues (gemm.hip: gemm256p_kernel EPI 2; gemm_row.hip: the full-row kernel).  Both kernels
-// call exactly these functions on exactly the same values, so the folded-LayerNorm statistics they leave agree bit for bit.
+// Raw-buffer access and row-statistics helpers of the streaming GEMM's epilogues (gemm.hip: gemm256p_kernel).  The residual epilogue
+// (EPI 2) and the generic one (EPI 0) call the same statistics functions on the same values, so the folded-LayerNorm statistics they
+// leave agree bit for bit.
 #pragma once
 #include "common.h"
 
@@ -7,7 +8,7 @@
 // so rows past M are dropped (stores) or read as zero (loads) by the hardware's bounds check -- no exec masking, no row clamp -- and an
 // address is a 32-bit lane offset (made once per tile) + a scalar offset per store instead of a 64-bit multiply-add per row.  (As
 // global_store with a per-row "m < M" the epilogue was ~30 basic blocks of 64-bit address arithmetic: v_mul_lo_u32 / v_mad_u64_u32 are
-// quarter-rate instructions.)  AUX 2 = the non-temporal hint (GEMM_NT above).
+// quarter-rate instructions.)  AUX 2 = the non-temporal hint.
 typedef int i32x4_buf __attribute__((ext_vector_type(4)));
 typedef int i32x2_buf __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, unsigned bytes) {
@@ -34,24 +35,14 @@ static __device__ __forceinline__ V buf_ld16(__amdgpu_buffer_rsrc_t r, int voff)
     return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
 
-// Sum over the 8 consecutive lanes that share (lane >> 3), valid in the lane with (lane & 7) == 0: three DPP steps
-// (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_shl:4), no LDS traffic (a __shfl_xor becomes a ds_bpermute round trip).
-static __device__ __forceinline__ float seg8_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x104, 0xF, 0xF, true));
-    return v;
-}
-// The same reduction for TWO values at once with the DPP operand INSIDE the add (v_add_f32_dpp): six adds and three one-cycle nops.  From
-// the builtin hipcc makes, per step, two v_mov_b32 0 (the `old` operand), two v_mov_b32_dpp and one packed add -- fifteen instructions per
-// row segment, 13 % of the residual epilogue's vector instructions.  Written as one asm block because the hazard recogniser does not look
-// inside inline assembly: a DPP read needs two wait states after the VALU write of its source (the partner chain's add is one, s_nop 0 the
-// other; s_nop 1 covers whatever wrote the inputs).  a + dpp(a) either way: the same bits.
-#ifndef GEMM_DPP_ADD
-#define GEMM_DPP_ADD 1
-#endif
+// Sums of two values over the 8 consecutive lanes that share (lane >> 3), valid in the lane with (lane & 7) == 0: three DPP steps
+// (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_shl:4), no LDS traffic (a __shfl_xor becomes a ds_bpermute round trip), with the DPP
+// operand INSIDE the add (v_add_f32_dpp): six adds and three one-cycle nops.  From __builtin_amdgcn_update_dpp hipcc makes, per step, two
+// v_mov_b32 0 (the `old` operand), two v_mov_b32_dpp and one packed add -- fifteen instructions per row segment, 13 % of the residual
+// epilogue's vector instructions.  Written as one asm block because the hazard recogniser does not look inside inline assembly: a DPP read
+// needs two wait states after the VALU write of its source (the partner chain's add is one, s_nop 0 the other; s_nop 1 covers whatever
+// wrote the inputs).
 static __device__ __forceinline__ void seg8_sum2(float& s1, float& s2) {
-#if GEMM_DPP_ADD
     float a, b;
     asm("s_nop 1\n\t"
         "v_add_f32_dpp %0, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
@@ -65,9 +56,6 @@ static __device__ __forceinline__ void seg8_sum2(float& s1, float& s2) {
         "s_nop 0"
         : "=&v"(a), "=&v"(b) : "v"(s1), "v"(s2));
     s1 = a; s2 = b;
-#else
-    s1 = seg8_sum(s1); s2 = seg8_sum(s2);
-#endif
 }
 
 // Sum and sum of squares of a lane's 8 values x[0..3], y[0..3] (a row segment's share of the LayerNorm statistics), as PACKED operations down

@@ -658,7 +658,7 @@ inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>&
         else { g.resid = x32; g.ldr = E; g.out_f32 = pre32; g.ldo = E; }
         if (fold) {
             g.stats_out = w.st1;
-            g.rows_out = w.r1; g.rows_eps = c.eps;      // the product finishes LN1's row statistics itself (gemm_row.hip at N = 768; otherwise avx::gemm runs ln_rowstats behind it)
+            g.rows_out = w.r1; g.rows_eps = c.eps;      // LN1's row statistics with the product (avx::gemm runs ln_rowstats behind it)
             if (raw_in) {
                 g.resid_half = nullptr; g.ldrh = 0;
                 g.lnr_y = w.xh; g.ldy = E; g.lnr_rows = w.r2; g.lnr_gamma = ly.ga_o; g.lnr_beta = ly.bb_o; g.lnr_prefolded = 1;

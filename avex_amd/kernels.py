@@ -421,8 +421,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = Non
     treats the rows as clips of T rows and returns under ``"pooled"`` the per-clip mean of the raw output (bias added, before residual /
     activation) without materialising it (``pool_part`` + ``avexhip_pool_reduce``); ``pool_mode`` "max" / "cls_token" return the per-clip
     maximum / first row instead; ``rows_eps`` returns under ``"rows"`` the finished row statistics ``[M (+1 if odd), 2]`` = (rstd, -mean rstd)
-    of the output (what :func:`ln_rowstats` makes of ``"stats"``, same bits; the full-row kernel -- ``variant=8``, N = 768 -- writes them
-    from its epilogue)."""
+    of the output (what :func:`ln_rowstats` makes of ``"stats"``, same bits).  ``variant=8`` runs variant 5."""
     _need_cuda(a, w)
     if a.dtype != w.dtype or a.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError("a and w must both be float16 or bfloat16")

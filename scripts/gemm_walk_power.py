@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One layer GEMM in the step's form (scripts/gemm_forms.py: folded LayerNorm), looped for 3 s with board power and shader clock sampled
 from rocm-smi: time per launch, watts, MHz, joules per launch.  The tile walk comes from AVEX_AMD_GEMM_TILE_ORDER, the kernel build from
-AVEX_AMD_LIB (round 6: the column-group walk with / without the non-temporal A stream, scripts/walks_r06.sh).
+AVEX_AMD_LIB (round 6: the column-group walk with / without the non-temporal A stream, built by scripts/walks_r06.sh, in git history).
     python scripts/gemm_walk_power.py qkv|fc1|out|fc2 [label]"""
 import os, sys, subprocess, threading, time, re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

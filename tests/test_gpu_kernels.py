@@ -506,15 +506,15 @@ _ROW_CASES = [(1000, 768, 0), (128, 768, 0), (129, 128, 0), (5000, 768, 3), (205
 
 
 @pytest.mark.parametrize("dtype,M,Kd,grid", [(d,) + c for d in DTYPES for c in _ROW_CASES] + [("f16", 126976, 768, 0)])      # (the full size once)
-def test_gemm_full_row_kernel_is_bit_identical(built_lib, dtype, M, Kd, grid, monkeypatch):
-    """gemm_row.hip (variant 8: one workgroup = 128 rows x all 768 columns; the attention output projection, backbone.py:572 + :360-362)
-    against the streaming kernel's residual epilogue (variant 5) on the same inputs: outputs, partial statistics and the finished row
-    statistics BIT FOR BIT (same MFMA chain over k, same epilogue operations, ln_rowstats_kernel's additions), in both residual forms
-    (plain half residual, LayerNorm(lnr_y) on the fly), ragged last tiles, several tiles per workgroup, K = 128 / 768 / 3072; and the
-    streaming kernel's result against fp64 (its own tests do that in depth)."""
+def test_gemm_residual_epilogue_rows_out(built_lib, dtype, M, Kd, grid, monkeypatch):
+    """The streaming kernel's residual epilogue (variant 5) with ABI 9's rows_out (the attention output projection, backbone.py:572 +
+    :360-362), in both residual forms (plain half residual, LayerNorm(lnr_y) on the fly), ragged last tiles, several tiles per workgroup,
+    K = 128 / 768 / 3072: the output against fp64, the finished row statistics BIT FOR BIT what ln_rowstats makes of the partial
+    statistics (with stats_out, and without it, where the product's own scratch takes the partials), and variant 8 (the number of a
+    removed full-row kernel) returning variant 5's bits."""
     from avex_amd import kernels as K
     if grid:
-        monkeypatch.setenv("AVEX_AMD_GEMM_GRID", str(8 * grid))      # (the streaming kernel's grid is a multiple of 8; the row kernel takes min(grid, tiles))
+        monkeypatch.setenv("AVEX_AMD_GEMM_GRID", str(8 * grid))      # (the streaming kernel's grid is a multiple of 8)
     E = 768
     td = _tdt(dtype)
     g = torch.Generator().manual_seed(M + Kd)
@@ -530,29 +530,26 @@ def test_gemm_full_row_kernel_is_bit_identical(built_lib, dtype, M, Kd, grid, mo
     lrows = torch.zeros(M + (M & 1), 2, device="cuda"); lrows[:M, 0] = rstd; lrows[:M, 1] = -xf.mean(1) * rstd
     forms = {"plain": dict(resid_half=x), "lnr": dict(lnr_y=x, lnr_rows=lrows, lnr_gamma=gamma, lnr_beta=beta)}
     for name, kw in forms.items():
-        out = {}
-        for v in (5, 8):
-            out[v] = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, stats_out=True, rows_eps=1e-5, variant=v, **kw)
-        assert torch.equal(out[8]["half"], out[5]["half"]), (name, "output")
-        assert torch.equal(out[8]["stats"], out[5]["stats"]), (name, "partial statistics")
-        assert torch.equal(out[8]["rows"][:M], out[5]["rows"][:M]), (name, "row statistics")
-        assert torch.equal(out[5]["rows"][:M], K.ln_rowstats(out[5]["stats"], 1e-5)[:M])
+        out = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, stats_out=True, rows_eps=1e-5, variant=5, **kw)
+        assert torch.equal(out["rows"][:M], K.ln_rowstats(out["stats"], 1e-5)[:M]), (name, "row statistics")
         # without the partial statistics (what the encoder asks for) and without any
+        r5 = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, rows_eps=1e-5, variant=5, **kw)
+        assert torch.equal(r5["half"], out["half"]) and torch.equal(r5["rows"][:M], out["rows"][:M]), (name, "rows_out without stats_out")
+        r5 = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, variant=5, **kw)
+        assert torch.equal(r5["half"], out["half"]), (name, "output without rows_out")
+        # variant 8: variant 5's bits, with and without the statistics
+        r8 = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, stats_out=True, rows_eps=1e-5, variant=8, **kw)
+        assert torch.equal(r8["half"], out["half"]), (name, "variant 8 output")
+        assert torch.equal(r8["stats"], out["stats"]), (name, "variant 8 partial statistics")
+        assert torch.equal(r8["rows"][:M], out["rows"][:M]), (name, "variant 8 row statistics")
         r8 = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, rows_eps=1e-5, variant=8, **kw)
-        assert torch.equal(r8["half"], out[5]["half"]) and torch.equal(r8["rows"][:M], out[5]["rows"][:M])
+        assert torch.equal(r8["half"], out["half"]) and torch.equal(r8["rows"][:M], out["rows"][:M]), (name, "variant 8 without stats_out")
         r8 = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, variant=8, **kw)
-        assert torch.equal(r8["half"], out[5]["half"])
+        assert torch.equal(r8["half"], out["half"]), (name, "variant 8 without rows_out")
         if M <= 5000:
             res = xf.double() * alpha if name == "plain" else alpha * (torch.nn.functional.layer_norm(xf, (E,), gamma, beta, 1e-5)).double()
             ref = (res + a.double() @ w.double().T + bias.double()).cpu().numpy()
-            assert rel_l2(out[8]["half"].float().cpu().numpy(), ref) < (6e-4 if dtype == "f16" else 5e-3), name
-    # the automatic choice (variant 0) with AVEX_AMD_GEMM_ROW=1 takes the row kernel from 32 768 rows at K <= 1024: same bits either way, so only the plumbing shows
-    if M >= 32768:
-        monkeypatch.setenv("AVEX_AMD_GEMM_ROW", "1")
-        r0 = K.gemm(a, w, bias=bias, alpha=alpha, out_f32=False, out_half=True, rows_eps=1e-5, **forms["lnr"])
-        assert torch.equal(r0["half"], out[5]["half"]) and torch.equal(r0["rows"][:M], out[5]["rows"][:M])
-    with pytest.raises(K.AvexHipError, match="variant 8"):
-        K.gemm(a, w, bias=bias, out_f32=True, out_half=True, resid_half=x, variant=8)          # an fp32 output is not its business
+            assert rel_l2(out["half"].float().cpu().numpy(), ref) < (6e-4 if dtype == "f16" else 5e-3), name
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
