@@ -84,6 +84,14 @@ class EffnetConfig(C.Structure):
                 ("bn_eps", C.c_float), ("operand_dtype", C.c_int32), ("max_chunk_clips", C.c_int32)]
 
 
+class RetrievalArgs(C.Structure):
+    _fields_ = [("query", C.c_void_p), ("ld_query", C.c_int64), ("nb", C.c_int32), ("q0", C.c_int32), ("n_db", C.c_int32), ("d", C.c_int32),
+                ("batch", C.c_int32), ("n_words", C.c_int32), ("self_set", C.c_int32), ("k", C.c_int32), ("stages", C.c_int32),
+                ("reserved", C.c_int32), ("query_ids", C.c_void_p), ("db_ids", C.c_void_p), ("query_words", C.c_void_p),
+                ("db_words", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("u2", C.c_void_p),
+                ("stats", C.c_void_p), ("topk", C.c_void_p), ("sim_out", C.c_void_p), ("ld_sim", C.c_int64)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -195,6 +203,12 @@ SYMBOLS = {
     "avexhip_effnet_set_profiling": (C.c_int, [_P, C.c_int]),
     "avexhip_effnet_last_profile": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_double)),
                                               C.POINTER(C.c_int)]),
+    "avexhip_retrieval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "avexhip_retrieval_max_k": (C.c_int, []),
+    "avexhip_retrieval_pack_labels": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "avexhip_retrieval_prepare": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "avexhip_retrieval_batch": (C.c_int, [C.POINTER(RetrievalArgs), _P]),
+    "avexhip_retrieval_finalize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
 }
 
 # exported by the diagnostic build only (-DAVEX_DIAG; AVEX_AMD_DIAG=1 python -m avex_amd.build, then AVEX_AMD_LIB=.../libavexhip_diag.so)

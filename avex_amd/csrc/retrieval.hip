@@ -1,0 +1,511 @@
+// Retrieval metrics on the device: the arithmetic behind avex/evaluation/retrieval.py (mean per-query ROC-AUC and precision@k over a
+// cosine-similarity ranking), for embeddings that already live in HBM.
+//
+//   retr_normalize_kernel   rows / max(||row||_2, 1e-12) in fp32 (retrieval.py:242), written once with the width padded to the K tile
+//   retr_pack_kernel        multi-hot label rows -> 64-bit words: relevance "shares an active class" (retrieval.py:152) is (a & b) != 0
+//   retr_sim_kernel         S[b][n] = q^_b . d^_n on v_mfma_f32_32x32x2_f32: fp32 operands, one rounding per product (an f16-operand
+//                           product moves the mean AUC by 1e-6 and flips precision@k hits).  128 x 128 x 32 tiles, LDS-DMA double buffer
+//                           with the chunk swizzle of gemm_nt_kernel (gemm.hip).
+//   retr_rank_kernel        one workgroup per query row: relevance bits, top-k, and the Mann-Whitney count
+//                               U2 = sum over (positive p, negative n) of 2 [s_p > s_n] + [s_p == s_n]          AUC = U2 / (2 P Q)
+//                           as a 64-bit integer: exact for the similarities as computed, independent of any summation order.  The smaller
+//                           of {positives, negatives} is sorted in LDS (bitonic, chunks of <= 16 Ki keys); every element of the other side
+//                           does a lower- and an upper-bound search in it.
+//   retr_finalize_kernel    validity rules of the reference + the fp64 means, in a fixed order (bit-reproducible).
+#include "common.h"
+
+namespace {
+
+typedef __attribute__((address_space(1))) const void gptr_t;
+typedef __attribute__((address_space(3))) void lptr_t;
+
+constexpr int RBM = 128, RBN = 128, RBK = 32;      // similarity tile; RBK fp32 = one 128-B LDS row = 8 chunks of 16 B
+constexpr int RTILE_BYTES = 128 * RBK * 4;         // 16 KiB per operand tile
+constexpr int RANK_THREADS = 256;
+constexpr int RANK_MAX_K = 32;
+constexpr int RANK_MAX_CAP = 16384;                // keys per sorted chunk (64 KiB of LDS)
+constexpr int RETR_MAX_DB = 1 << 19;               // relevance bits of one row: 64 KiB of LDS
+
+static inline int64_t dpad_of(int d) { return ((int64_t)d + RBK - 1) / RBK * RBK; }
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline int64_t ldsim_of(int64_t n_db) { return (n_db + 63) / 64 * 64; }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void retr_normalize_kernel(const float* __restrict__ x, int64_t ldx, int n, int d, int dpad, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float* r = x + (int64_t)row * ldx;
+    float ss = 0.f;
+    for (int c = lane; c < d; c += 64) ss = __builtin_fmaf(r[c], r[c], ss);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    float nrm = __builtin_sqrtf(ss);
+    nrm = nrm < 1e-12f ? 1e-12f : nrm;
+    float* o = out + (int64_t)row * dpad;
+    for (int c = lane; c < dpad; c += 64) o[c] = c < d ? r[c] / nrm : 0.f;
+}
+
+__global__ __launch_bounds__(256) void retr_pack_kernel(const uint8_t* __restrict__ hot, int n, int c, int n_words, unsigned long long* __restrict__ words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)n * n_words) return;
+    const int row = (int)(i / n_words), w = (int)(i - (int64_t)row * n_words);
+    const uint8_t* r = hot + (int64_t)row * c;
+    unsigned long long v = 0ull;
+    const int hi = c - w * 64 < 64 ? c - w * 64 : 64;
+    for (int b = 0; b < hi; ++b) v |= (unsigned long long)(r[w * 64 + b] != 0) << b;
+    words[i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// S[q][n] for q in [0, nq), n in [0, nd): Q and D are normalised rows of dpad floats (dpad % 32 == 0, zero beyond d).  Wave (wr, wc) owns
+// queries [64 wr, +64) x database rows [64 wc, +64) of the tile as 2 x 2 MFMA tiles.  v_mfma_f32_32x32x2_f32 takes ONE float per lane and
+// operand: lane (i = lane & 31, h = lane >> 5) supplies row i at k-index h.  A lane reads 4 consecutive floats (one swizzled 16-B chunk,
+// chunk 2 kk + h) and feeds them to 4 MFMAs; both operands use the same k assignment, so the order of the sum inside a K tile is
+// permuted, not its terms.
+__global__ __launch_bounds__(256) void retr_sim_kernel(const float* __restrict__ Q, int nq, const float* __restrict__ D, int nd, int dpad,
+                                                        float* __restrict__ S, int64_t lds_) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int n0 = blockIdx.x * RBN, q0 = blockIdx.y * RBM;
+    const int wr = wid >> 1, wc = wid & 1;
+    const int nk = dpad / RBK;
+
+    auto stage_dma = [&](int st, int k0) __attribute__((always_inline)) {
+        char* qbase = smem + st * (2 * RTILE_BYTES);
+        char* dbase = qbase + RTILE_BYTES;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rloc = wid * 32 + i * 8 + (lane >> 3);
+            const int chunk = (lane & 7) ^ ((rloc >> 1) & 7);
+            int qrow = q0 + rloc, drow = n0 + rloc;
+            qrow = qrow < nq ? qrow : nq - 1;      // rows past the end repeat the last one; their results are not stored
+            drow = drow < nd ? drow : nd - 1;
+            const float* qsrc = Q + (int64_t)qrow * dpad + k0 + chunk * 4;
+            const float* dsrc = D + (int64_t)drow * dpad + k0 + chunk * 4;
+            const int dst = (wid * 32 + i * 8) * 128;      // wave-uniform; hardware adds lane * 16
+            __builtin_amdgcn_global_load_lds((gptr_t*)qsrc, (lptr_t*)(qbase + dst), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t*)dsrc, (lptr_t*)(dbase + dst), 16, 0, 0);
+        }
+    };
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    auto compute = [&](int st) __attribute__((always_inline)) {
+        const char* qbase = smem + st * (2 * RTILE_BYTES);
+        const char* dbase = qbase + RTILE_BYTES;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            f32x4 qf[2], df[2];
+            const int chunk = 2 * kk + (lane >> 5);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int row = wr * 64 + i * 32 + (lane & 31);
+                qf[i] = *(const f32x4*)(qbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int row = wc * 64 + j * 32 + (lane & 31);
+                df[j] = *(const f32x4*)(dbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[i][e], df[j][e], acc[i][j], 0, 0, 0);
+        }
+    };
+
+    stage_dma(0, 0);
+    for (int kt = 0; kt < nk; ++kt) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my DMA pieces of tile kt have landed
+        __syncthreads();                                      // everyone's landed; everyone finished reading buffer (kt + 1) & 1
+        if (kt + 1 < nk) stage_dma((kt + 1) & 1, (kt + 1) * RBK);
+        compute(kt & 1);
+    }
+    // C/D of the 32x32 forms: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wc * 64 + j * 32 + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int q = q0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (q < nq && n < nd) S[(int64_t)q * lds_ + n] = acc[i][j][r];
+            }
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct RankArgs {
+    const float* S;
+    int64_t lds_;
+    int nd, self_base, n_words, k, cap;
+    const int32_t* q_ids;
+    const int32_t* d_ids;
+    const unsigned long long* q_words;
+    const unsigned long long* d_words;
+    long long* u2;
+    int32_t* stats;
+    int32_t* topk;
+};
+
+// order-preserving map of a float onto unsigned integers (-0 is folded onto +0 first by the caller)
+static __device__ __forceinline__ unsigned mono32(float v) {
+    const unsigned u = __float_as_uint(v);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+static __device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(v, o);
+        v = t > v ? t : v;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    unsigned long long m = red[0];
+#pragma unroll
+    for (int w = 1; w < RANK_THREADS / 64; ++w) m = red[w] > m ? red[w] : m;
+    return m;
+}
+
+static __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    unsigned long long m = red[0];
+#pragma unroll
+    for (int w = 1; w < RANK_THREADS / 64; ++w) m += red[w];
+    return m;
+}
+
+// number of keys < x (LE = false) or <= x (LE = true) among the np2 ascending keys of a (np2 a power of two; the tail beyond the real
+// keys is +inf).  Branch-free: the probe addresses of the first steps are the same in every lane (LDS broadcast).
+template <bool LE> static __device__ __forceinline__ int count_below(const float* a, int np2, float x) {
+    int lo = 0;
+    for (int s = np2 >> 1; s >= 1; s >>= 1) {
+        const float v = a[lo + s - 1];
+        lo += (LE ? v <= x : v < x) ? s : 0;
+    }
+    const float v = a[lo];
+    return lo + ((LE ? v <= x : v < x) ? 1 : 0);
+}
+
+__global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ unsigned long long red[8][RANK_THREADS / 64];
+    __shared__ int fill;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x;
+    const int nd = p.nd, k = p.k;
+    const int self = p.self_base >= 0 ? p.self_base + b : -1;      // column of the query itself (self-set), never ranked
+    const float* __restrict__ srow = p.S + (int64_t)b * p.lds_;
+    const int nmw = (nd + 63) >> 6;
+    unsigned long long* mask = (unsigned long long*)smem;                       // relevance bit of every column
+    char* work = smem + (((size_t)nmw * 8 + 15) & ~(size_t)15);
+    unsigned long long* list = (unsigned long long*)work;                       // [k][256] per-thread candidates, best first
+    float* keys = (float*)work;                                                 // the sorted chunk (after the top-k is out)
+
+    // ---- pass 1: relevance bits, positives, per-thread top-k candidates ---------------------------------------------------------
+    for (int j = 0; j < k; ++j) list[j * RANK_THREADS + tid] = 0ull;
+    unsigned long long thr = 0ull;
+    int npos = 0, relself = 0;
+    const int32_t qid = p.n_words == 0 ? p.q_ids[b] : 0;
+    const unsigned long long* qw = p.q_words + (int64_t)b * p.n_words;
+    for (int base = wid * 64; base < nd; base += RANK_THREADS) {      // wave-uniform trip count: the ballot sees all 64 lanes
+        const int n = base + lane;
+        const bool in = n < nd;
+        bool rel = false;
+        if (in) {
+            if (p.n_words == 0) {
+                rel = p.d_ids[n] == qid;
+            } else {
+                const unsigned long long* dw = p.d_words + (int64_t)n * p.n_words;
+                unsigned long long any = 0ull;
+                for (int w = 0; w < p.n_words; ++w) any |= dw[w] & qw[w];
+                rel = any != 0ull;
+            }
+        }
+        const unsigned long long bal = __ballot(rel);
+        if (lane == 0) mask[base >> 6] = bal;
+        if (in && n == self) relself = rel ? 1 : 0;
+        if (in && n != self) {
+            npos += rel ? 1 : 0;
+            const unsigned long long key = ((unsigned long long)mono32(srow[n] + 0.0f) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
+            if (key > thr) {      // higher similarity first, then lower index
+                int j = k - 1;
+                while (j > 0 && list[(j - 1) * RANK_THREADS + tid] < key) {
+                    list[j * RANK_THREADS + tid] = list[(j - 1) * RANK_THREADS + tid];
+                    --j;
+                }
+                list[j * RANK_THREADS + tid] = key;
+                thr = list[(k - 1) * RANK_THREADS + tid];
+            }
+        }
+    }
+    const int P = (int)block_sum_u64((unsigned long long)npos, red[0], tid);                  // the barrier inside publishes mask[]
+    const int rel_total = P + (int)block_sum_u64((unsigned long long)relself, red[1], tid);
+    const int n_eff = nd - ((self >= 0 && self < nd) ? 1 : 0);
+    const int Q = n_eff - P;
+
+    // ---- top-k: k rounds of "best head among the 256 sorted lists" --------------------------------------------------------------
+    int head = 0, nhit = 0;
+    for (int r = 0; r < RANK_MAX_K; ++r) {
+        if (r >= k) {
+            if (tid == 0) p.topk[(int64_t)b * RANK_MAX_K + r] = -1;
+            continue;
+        }
+        const unsigned long long cur = head < k ? list[head * RANK_THREADS + tid] : 0ull;
+        const unsigned long long best = block_max_u64(cur, red[2 + (r & 1)], tid);
+        if (best != 0ull && cur == best) ++head;      // keys carry their column: unique
+        if (tid == 0) {
+            const int idx = best != 0ull ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
+            p.topk[(int64_t)b * RANK_MAX_K + r] = idx;
+            if (idx >= 0) nhit += (int)((mask[idx >> 6] >> (idx & 63)) & 1ull);
+        }
+    }
+    if (tid == 0) {
+        int32_t* st = p.stats + (int64_t)b * 4;
+        st[0] = P;
+        st[1] = Q;
+        st[2] = rel_total;
+        st[3] = nhit;
+    }
+
+    // ---- U2: sort the smaller side chunk by chunk, search with the larger -------------------------------------------------------
+    unsigned long long u2 = 0ull;
+    if (P > 0 && Q > 0) {
+        const bool pos_small = P <= Q;
+        const int m = pos_small ? P : Q;
+        // a chunk is a column range that holds at most cap keys of the smaller side: every column when they all fit, cap columns otherwise
+        const int cw = m <= p.cap ? ((nd + 63) & ~63) : p.cap;
+        for (int c0 = 0; c0 < nd; c0 += cw) {
+            __syncthreads();      // the previous chunk's searches (or the top-k lists) are done with `work`
+            if (tid == 0) fill = 0;
+            __syncthreads();
+            const int c1 = c0 + cw < nd ? c0 + cw : nd;
+            for (int base = c0 + wid * 64; base < c1; base += RANK_THREADS) {
+                const int n = base + lane;
+                const bool rel = (mask[base >> 6] >> lane) & 1ull;
+                const bool sel = n < c1 && n != self && rel == pos_small;
+                const unsigned long long bal = __ballot(sel);
+                if (bal != 0ull) {
+                    int at = 0;
+                    if (lane == 0) at = atomicAdd(&fill, (int)__popcll(bal));
+                    at = __shfl(at, 0);
+                    if (sel) keys[at + (int)__popcll(bal & ((1ull << lane) - 1ull))] = srow[n] + 0.0f;
+                }
+            }
+            __syncthreads();
+            const int cnt = fill;
+            if (cnt == 0) continue;      // block-uniform
+            int np2 = 2;
+            while (np2 < cnt) np2 <<= 1;
+            for (int i = cnt + tid; i < np2; i += RANK_THREADS) keys[i] = __builtin_inff();
+            __syncthreads();
+            for (int size = 2; size <= np2; size <<= 1)
+                for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                    for (int t = tid; t < (np2 >> 1); t += RANK_THREADS) {
+                        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                        const float x = keys[i], y = keys[j];
+                        if ((x > y) == ((i & size) == 0)) {
+                            keys[i] = y;
+                            keys[j] = x;
+                        }
+                    }
+                    __syncthreads();
+                }
+            for (int base = wid * 64; base < nd; base += RANK_THREADS) {
+                const int n = base + lane;
+                const bool rel = (mask[base >> 6] >> lane) & 1ull;
+                if (n < nd && n != self && rel != pos_small) {
+                    const float x = srow[n] + 0.0f;
+                    const int lb = count_below<false>(keys, np2, x);
+                    int ub = lb;
+                    if (lb < cnt && keys[lb] == x) ub = count_below<true>(keys, np2, x);      // ties are rare: one search for most elements
+                    // sorted positives, x a negative: 2 (cnt - ub) wins + (ub - lb) ties; sorted negatives, x a positive: 2 lb + (ub - lb)
+                    u2 += (unsigned long long)(pos_small ? 2 * cnt - ub - lb : lb + ub);
+                }
+            }
+        }
+    }
+    const unsigned long long tot = block_sum_u64(u2, red[4], tid);
+    if (tid == 0) p.u2[b] = (long long)tot;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// out[0] = sum of per-query AUC over the valid queries, out[1] = their number, out[2] = sum of precision@k, out[3] = its number.
+// Self-set (retrieval.py:262-284, 470-486): a query whose relevance vector, itself included, sums to <= 1 is skipped in both; so is, for
+// the AUC, one with no negative left.  Cross-set (:386-399, 640-660): no positive = skipped in both; no negative = skipped in the AUC.
+__global__ __launch_bounds__(256) void retr_finalize_kernel(const long long* __restrict__ u2, const int32_t* __restrict__ stats, int nq, int self_set,
+                                                             int k, double* __restrict__ out) {
+    __shared__ double red[4][256];
+    const int tid = threadIdx.x;
+    double a = 0.0, an = 0.0, pr = 0.0, pn = 0.0;
+    for (int i = tid; i < nq; i += 256) {
+        const int P = stats[4 * i], Q = stats[4 * i + 1], rt = stats[4 * i + 2], hit = stats[4 * i + 3];
+        const bool vp = self_set ? rt > 1 : P > 0;
+        const bool va = vp && P > 0 && Q > 0;
+        if (va) {
+            a += (double)u2[i] / (2.0 * (double)P * (double)Q);
+            an += 1.0;
+        }
+        if (vp) {
+            pr += (double)hit / (double)k;
+            pn += 1.0;
+        }
+    }
+    red[0][tid] = a;
+    red[1][tid] = an;
+    red[2][tid] = pr;
+    red[3][tid] = pn;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int c = 0; c < 4; ++c) red[c][tid] += red[c][tid + s];
+        __syncthreads();
+    }
+    if (tid < 4) out[tid] = red[tid][0];
+}
+
+struct Workspace {
+    float* dbn;
+    float* qn;
+    float* sim;
+    size_t bytes;
+};
+
+static Workspace carve(void* ws, int64_t n_db, int d, int batch) {
+    Workspace w;
+    const size_t dp = (size_t)dpad_of(d);
+    char* p = (char*)ws;
+    w.dbn = (float*)p;
+    p += align256((size_t)n_db * dp * 4);
+    w.qn = (float*)p;
+    p += align256((size_t)batch * dp * 4);
+    w.sim = (float*)p;
+    p += align256((size_t)batch * (size_t)ldsim_of(n_db) * 4);
+    w.bytes = (size_t)(p - (char*)ws);
+    return w;
+}
+
+static size_t rank_lds_bytes(int nd, int k, int cap) {
+    const size_t mask = ((size_t)((nd + 63) >> 6) * 8 + 15) & ~(size_t)15;
+    const size_t lists = (size_t)k * RANK_THREADS * 8, keys = (size_t)cap * 4;
+    return mask + (lists > keys ? lists : keys);
+}
+
+}  // namespace
+
+extern "C" size_t avexhip_retrieval_workspace_bytes(int64_t n_db, int d, int batch, int n_words) {
+    (void)n_words;      // packed labels are caller-owned buffers
+    if (n_db <= 0 || d <= 0 || batch <= 0) return 0;
+    return carve(nullptr, n_db, d, batch).bytes;
+}
+
+extern "C" int avexhip_retrieval_max_k(void) { return RANK_MAX_K; }
+
+extern "C" int avexhip_retrieval_pack_labels(const uint8_t* multihot_dev, int n, int n_classes, uint64_t* words_dev, void* stream) {
+    AVX_REQUIRE(multihot_dev && words_dev && n >= 0 && n_classes >= 1, "retrieval_pack_labels: bad arguments (n %d, classes %d)", n, n_classes);
+    if (n == 0) return AVEXHIP_OK;
+    const int nw = (n_classes + 63) / 64;
+    const int64_t blocks = ((int64_t)n * nw + 255) / 256;
+    AVX_REQUIRE(blocks <= 0x7fffffff, "retrieval_pack_labels: too many label words");
+    retr_pack_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(multihot_dev, n, n_classes, nw, (unsigned long long*)words_dev);
+    AVX_LAUNCH_CHECK();
+    return AVEXHIP_OK;
+}
+
+extern "C" int avexhip_retrieval_prepare(const float* db_dev, int64_t ld_db, int n_db, int d, int batch, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    AVX_REQUIRE(db_dev && workspace, "retrieval_prepare: null argument");
+    AVX_REQUIRE(n_db >= 1 && n_db <= RETR_MAX_DB && d >= 1 && batch >= 1 && ld_db >= d, "retrieval_prepare: bad shape (n_db %d [1, %d], d %d, batch %d)",
+                n_db, RETR_MAX_DB, d, batch);
+    const Workspace w = carve(workspace, n_db, d, batch);
+    if (workspace_bytes < w.bytes) {
+        avexhip_set_error("retrieval_prepare: workspace %zu B < %zu B", workspace_bytes, w.bytes);
+        return AVEXHIP_ERR_WORKSPACE;
+    }
+    retr_normalize_kernel<<<dim3((n_db + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(db_dev, ld_db, n_db, d, (int)dpad_of(d), w.dbn);
+    AVX_LAUNCH_CHECK();
+    return AVEXHIP_OK;
+}
+
+extern "C" int avexhip_retrieval_batch(const avexhip_retrieval_args* a, void* stream) {
+    AVX_REQUIRE(a && a->workspace && a->u2 && a->stats && a->topk, "retrieval_batch: null argument");
+    AVX_REQUIRE(a->n_db >= 1 && a->n_db <= RETR_MAX_DB && a->d >= 1 && a->batch >= 1 && a->nb >= 1 && a->nb <= a->batch,
+                "retrieval_batch: bad shape (n_db %d, d %d, batch %d, nb %d)", a->n_db, a->d, a->batch, a->nb);
+    AVX_REQUIRE(a->k >= 1 && a->k <= RANK_MAX_K, "retrieval_batch: k %d outside [1, %d]", a->k, RANK_MAX_K);
+    AVX_REQUIRE(a->n_words >= 0, "retrieval_batch: n_words %d", a->n_words);
+    if (a->n_words == 0) AVX_REQUIRE(a->query_ids && a->db_ids, "retrieval_batch: class ids missing");
+    else AVX_REQUIRE(a->query_words && a->db_words, "retrieval_batch: label words missing");
+    if (a->self_set) AVX_REQUIRE(!a->query && a->q0 >= 0 && (int64_t)a->q0 + a->nb <= a->n_db, "retrieval_batch: self-set rows [%d, +%d) outside the database", a->q0, a->nb);
+    else AVX_REQUIRE(a->query && a->ld_query >= a->d, "retrieval_batch: query rows missing");
+    const Workspace w = carve(a->workspace, a->n_db, a->d, a->batch);
+    if (a->workspace_bytes < w.bytes) {
+        avexhip_set_error("retrieval_batch: workspace %zu B < %zu B", a->workspace_bytes, w.bytes);
+        return AVEXHIP_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int dp = (int)dpad_of(a->d);
+    const int64_t lds_ = ldsim_of(a->n_db);
+    const int stages = a->stages == 0 ? 3 : a->stages;
+    if (stages & 1) {
+        const float* qn = w.dbn + (int64_t)a->q0 * dp;
+        if (!a->self_set) {
+            retr_normalize_kernel<<<dim3((a->nb + 3) / 4), dim3(256), 0, s>>>(a->query, a->ld_query, a->nb, a->d, dp, w.qn);
+            AVX_LAUNCH_CHECK();
+            qn = w.qn;
+        }
+        AVX_ENSURE_LDS(retr_sim_kernel, 4 * RTILE_BYTES);
+        const dim3 grid((a->n_db + RBN - 1) / RBN, (a->nb + RBM - 1) / RBM);
+        retr_sim_kernel<<<grid, dim3(256), 4 * RTILE_BYTES, s>>>(qn, a->nb, w.dbn, a->n_db, dp, w.sim, lds_);
+        AVX_LAUNCH_CHECK();
+        if (a->sim_out) {
+            AVX_REQUIRE(a->ld_sim >= a->n_db, "retrieval_batch: ld_sim %lld < n_db", (long long)a->ld_sim);
+            AVX_HIP_CHECK(hipMemcpy2DAsync(a->sim_out, (size_t)a->ld_sim * 4, w.sim, (size_t)lds_ * 4, (size_t)a->n_db * 4, (size_t)a->nb,
+                                           hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (stages & 2) {
+        RankArgs r;
+        r.S = w.sim;
+        r.lds_ = lds_;
+        r.nd = a->n_db;
+        r.self_base = a->self_set ? a->q0 : -1;
+        r.n_words = a->n_words;
+        r.k = a->k;
+        int cap = 64;      // the smaller side has at most n_db / 2 keys
+        while (cap < (a->n_db + 1) / 2 && cap < RANK_MAX_CAP) cap <<= 1;
+        r.cap = cap;
+        r.q_ids = a->query_ids;
+        r.d_ids = a->db_ids;
+        r.q_words = (const unsigned long long*)a->query_words;
+        r.d_words = (const unsigned long long*)a->db_words;
+        r.u2 = (long long*)a->u2;
+        r.stats = a->stats;
+        r.topk = a->topk;
+        const size_t lds = rank_lds_bytes(a->n_db, a->k, cap);
+        AVX_ENSURE_LDS(retr_rank_kernel, rank_lds_bytes(RETR_MAX_DB, RANK_MAX_K, RANK_MAX_CAP));
+        retr_rank_kernel<<<dim3(a->nb), dim3(RANK_THREADS), lds, s>>>(r);
+        AVX_LAUNCH_CHECK();
+    }
+    return AVEXHIP_OK;
+}
+
+extern "C" int avexhip_retrieval_finalize(const int64_t* u2_dev, const int32_t* stats_dev, int n_query, int self_set, int k, double* out_dev,
+                                          void* stream) {
+    AVX_REQUIRE(u2_dev && stats_dev && out_dev && n_query >= 0 && k >= 1, "retrieval_finalize: bad arguments");
+    retr_finalize_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>((const long long*)u2_dev, stats_dev, n_query, self_set, k, out_dev);
+    AVX_LAUNCH_CHECK();
+    return AVEXHIP_OK;
+}

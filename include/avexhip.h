@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 9
+#define AVEXHIP_ABI_VERSION 10
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -345,6 +345,55 @@ int avexhip_debug_gemm_clocks(unsigned long long* host_out, int n_tiles);
  * (variant 5, stamps enabled): host_out[64 * block + kt], blocks < 256, kt < 64. */
 int avexhip_debug_gemm_kclocks(unsigned long long* host_out, int n_blocks);
 #endif /* AVEX_DIAG */
+
+/* ------------------------------------------------------------------------------------------
+ * Retrieval metrics (ABI 10): what avex/evaluation/retrieval.py computes from cached embeddings -- mean per-query ROC-AUC and
+ * precision@k over a cosine-similarity ranking (run_evaluate.py:956-961) -- for embeddings that are already on the device.
+ * Rows are divided by max(||row||, 1e-12) (retrieval.py:242); similarities are fp32 products on the fp32 MFMA; a query's ROC-AUC
+ * is U2 / (2 P Q) with U2 = sum over (positive, negative) pairs of 2 [s_p > s_n] + [s_p == s_n], held as a 64-bit integer.
+ * Working memory is O(batch x n_db); nothing here allocates or synchronises.
+ *   1. avexhip_retrieval_prepare  normalises the database rows into the workspace (once);
+ *   2. avexhip_retrieval_batch    one batch of <= `batch` queries: similarities against the whole database, then per query U2,
+ *                                 the counts and the top-k columns (higher similarity first, then lower index);
+ *   3. avexhip_retrieval_finalize the reference's skip rules and the fp64 sums over all queries.
+ * Relevance is `same class id` (n_words == 0: int32 ids) or `shares an active class` (n_words > 0: multi-hot rows packed to
+ * n_words 64-bit words by avexhip_retrieval_pack_labels, n_words = ceil(n_classes / 64)).  n_db <= 524288, k <= 32.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float* query;          /* cross-set: [nb, d] fp32 rows of this batch (row stride ld_query); self-set: NULL */
+    int64_t ld_query;
+    int32_t nb;                  /* queries in this batch, 1 .. batch */
+    int32_t q0;                  /* self-set: the batch is database rows [q0, q0 + nb); column q0 + b is never ranked for query b */
+    int32_t n_db, d, batch;      /* as given to avexhip_retrieval_workspace_bytes / _prepare */
+    int32_t n_words;             /* 0: class ids; > 0: packed multi-hot words per row */
+    int32_t self_set;            /* 1: queries are the database itself (eval_retrieval); 0: eval_retrieval_cross_set */
+    int32_t k;                   /* 1 .. 32, already clipped to the number of rankable columns */
+    int32_t stages;              /* 0 or 3: similarity + rank; 1: similarity only; 2: rank only (of the similarities in the workspace) */
+    int32_t reserved;
+    const int32_t* query_ids;    /* [nb] for this batch */
+    const int32_t* db_ids;       /* [n_db] */
+    const uint64_t* query_words; /* [nb, n_words] for this batch */
+    const uint64_t* db_words;    /* [n_db, n_words] */
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t* u2;                 /* out [nb] */
+    int32_t* stats;              /* out [nb, 4]: positives, negatives (both without the query's own column), relevant columns with it, hits in the top k */
+    int32_t* topk;               /* out [nb, 32]: columns, best first; -1 beyond k */
+    float* sim_out;              /* optional [nb, n_db] copy of the similarities (row stride ld_sim), for tests */
+    int64_t ld_sim;
+} avexhip_retrieval_args;
+
+size_t avexhip_retrieval_workspace_bytes(int64_t n_db, int d, int batch, int n_words);
+int avexhip_retrieval_max_k(void);      /* 32 */
+/* multihot_dev [n, n_classes] bytes (non-zero = active) -> words_dev [n, ceil(n_classes / 64)], class c at bit c % 64 of word c / 64 */
+int avexhip_retrieval_pack_labels(const uint8_t* multihot_dev, int n, int n_classes, uint64_t* words_dev, void* stream);
+int avexhip_retrieval_prepare(const float* db_dev, int64_t ld_db, int n_db, int d, int batch, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int avexhip_retrieval_batch(const avexhip_retrieval_args* args, void* stream);
+/* u2_dev [n_query], stats_dev [n_query, 4] as the batches left them -> out_dev[4] fp64: sum of AUC over the valid queries, their
+ * number, sum of precision@k, its number (retrieval.py:262-284, 386-399, 470-486, 640-660 for who is valid). */
+int avexhip_retrieval_finalize(const int64_t* u2_dev, const int32_t* stats_dev, int n_query, int self_set, int k, double* out_dev,
+                               void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
