@@ -92,6 +92,13 @@ class RetrievalArgs(C.Structure):
                 ("stats", C.c_void_p), ("topk", C.c_void_p), ("sim_out", C.c_void_p), ("ld_sim", C.c_int64)]
 
 
+class ClusteringArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("ld_x", C.c_int64), ("n", C.c_int32), ("d", C.c_int32), ("k", C.c_int32), ("n_init", C.c_int32),
+                ("max_iter", C.c_int32), ("tol", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("labels_out", C.c_void_p), ("centers_out", C.c_void_p), ("inertias_out", C.c_void_p), ("n_iters_out", C.c_void_p),
+                ("seeds_out", C.c_void_p), ("summary_out", C.c_void_p)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -209,6 +216,16 @@ SYMBOLS = {
     "avexhip_retrieval_prepare": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "avexhip_retrieval_batch": (C.c_int, [C.POINTER(RetrievalArgs), _P]),
     "avexhip_retrieval_finalize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "avexhip_clustering_max_k": (C.c_int, []),
+    "avexhip_clustering_trials": (C.c_int, [C.c_int]),
+    "avexhip_clustering_prepare": (C.c_int, [C.POINTER(ClusteringArgs), _P]),
+    "avexhip_clustering_seed": (C.c_int, [C.POINTER(ClusteringArgs), _P, _P, _P]),
+    "avexhip_clustering_set_init": (C.c_int, [C.POINTER(ClusteringArgs), _P, C.c_int64, _P]),
+    "avexhip_clustering_iterate": (C.c_int, [C.POINTER(ClusteringArgs), C.c_int, C.c_int, _P, _P]),
+    "avexhip_clustering_finish": (C.c_int, [C.POINTER(ClusteringArgs), _P]),
+    "avexhip_clustering_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "avexhip_clustering_scores": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
 }
 
 # exported by the diagnostic build only (-DAVEX_DIAG; AVEX_AMD_DIAG=1 python -m avex_amd.build, then AVEX_AMD_LIB=.../libavexhip_diag.so)

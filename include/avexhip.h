@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 10
+#define AVEXHIP_ABI_VERSION 11
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -394,6 +394,60 @@ int avexhip_retrieval_batch(const avexhip_retrieval_args* args, void* stream);
  * number, sum of precision@k, its number (retrieval.py:262-284, 386-399, 470-486, 640-660 for who is valid). */
 int avexhip_retrieval_finalize(const int64_t* u2_dev, const int32_t* stats_dev, int n_query, int self_set, int k, double* out_dev,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Clustering metrics (ABI 11): what avex/evaluation/clustering.py computes from cached embeddings -- scikit-learn's
+ * KMeans(n_clusters, random_state, n_init = 10, max_iter = 300) (greedy k-means++ seeding, Lloyd's algorithm with the strict /
+ * tolerance stopping rules and the empty-cluster relocation) followed by adjusted_rand_score, normalized_mutual_info_score and
+ * v_measure_score -- for embeddings that are already on the device.  All n_init restarts advance in lock-step; the host supplies
+ * only the random numbers (numpy RandomState draws, which do not depend on the data) and polls one word between chunks of
+ * iterations.  Arithmetic is fp32 (distances on the fp32 MFMA, centre sums in ascending row order: a run is bit-reproducible);
+ * potentials, prefix sums, inertia and the scores are fp64.  Nothing here allocates or synchronises.
+ *   1. avexhip_clustering_prepare   column means, X - mean (width padded to 32), tol_abs = mean(var(X, axis 0)) * tol, finite flag;
+ *                                   touches only the (n, d)-sized head of the workspace: one prepared workspace, sized for the
+ *                                   largest k, serves every smaller k (eval_clustering_multiple_k);
+ *   2. avexhip_clustering_seed      k-means++ for every restart, or avexhip_clustering_set_init for one run from given centres;
+ *   3. avexhip_clustering_iterate   n_iters Lloyd iterations (assign, update, relocate, stopping rules); finished restarts are frozen;
+ *   4. avexhip_clustering_finish    inertia per restart, the first strictly smallest, its labels and centres (mean added back);
+ *   5. avexhip_clustering_scores    contingency table of two dense int32 labelings -> ARI, NMI (arithmetic), V-measure (beta 1).
+ * Limits: k <= 4096 (avexhip_clustering_max_k), n_init <= 64, n <= 2^24.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float* x;              /* [n, d] fp32 rows on the device (row stride ld_x); read by _prepare only */
+    int64_t ld_x;
+    int32_t n, d;
+    int32_t k;                   /* clusters, 1 .. min(n, 4096) */
+    int32_t n_init;              /* restarts, 1 .. 64 (1 with avexhip_clustering_set_init) */
+    int32_t max_iter;
+    float tol;                   /* relative tolerance (sklearn's tol); _prepare scales it by the mean column variance */
+    void* workspace;
+    size_t workspace_bytes;
+    /* outputs of avexhip_clustering_finish */
+    int32_t* labels_out;         /* [n] labels of the winning restart */
+    float* centers_out;          /* [k, d] its centres, mean added back */
+    double* inertias_out;        /* [n_init] */
+    int32_t* n_iters_out;        /* [n_init] iterations as sklearn counts them */
+    int32_t* seeds_out;          /* [n_init, k] data rows k-means++ chose (-1 after set_init) */
+    int32_t* summary_out;        /* [4]: winning restart, its n_iter, 1 = every input value finite, restarts not finished */
+} avexhip_clustering_args;
+
+size_t avexhip_clustering_workspace_bytes(int64_t n, int d, int k, int n_init);
+int avexhip_clustering_max_k(void);        /* 4096 */
+int avexhip_clustering_trials(int k);      /* 2 + int(ln k): candidates per k-means++ step */
+int avexhip_clustering_prepare(const avexhip_clustering_args* args, void* stream);
+/* first_dev [n_init] int32: each restart's first centre (RandomState.choice); u_dev [n_init, k - 1, trials] fp64: the uniform draws of
+ * the following steps, in stream order.  Resets the iteration state. */
+int avexhip_clustering_seed(const avexhip_clustering_args* args, const int32_t* first_dev, const double* u_dev, void* stream);
+/* init_dev [k, d] fp32 centres in the coordinates of x (the mean is subtracted here); n_init must be 1.  Resets the iteration state. */
+int avexhip_clustering_set_init(const avexhip_clustering_args* args, const float* init_dev, int64_t ld_init, void* stream);
+/* stages: 0 or 3 whole iterations; 1 the assign product only, 2 everything after it (for timing).  unfinished_out_dev (optional)
+ * receives the number of restarts that have not stopped after these iterations. */
+int avexhip_clustering_iterate(const avexhip_clustering_args* args, int n_iters, int stages, int32_t* unfinished_out_dev, void* stream);
+int avexhip_clustering_finish(const avexhip_clustering_args* args, void* stream);
+size_t avexhip_clustering_scores_workspace_bytes(int n_true, int n_pred);
+/* ids dense in [0, n_true) and [0, n_pred); out_dev[3] fp64 = ARI, NMI, V-measure */
+int avexhip_clustering_scores(const int32_t* true_ids_dev, int n_true, const int32_t* pred_ids_dev, int n_pred, int n, void* workspace,
+                              size_t workspace_bytes, double* out_dev, void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
