@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .retrieval import _as_tensor, _device_of, _joint_ids, _stream
+from ._metric_inputs import _as_tensor, _device_of, _joint_ids, _len0, _stream
 
 logger = logging.getLogger(__name__)
 
@@ -61,10 +61,6 @@ def _get_empty_clustering_best_metrics() -> Dict[str, float]:
 
 def _numel(x) -> int:
     return int(x.numel()) if isinstance(x, torch.Tensor) else int(np.asarray(x).size)
-
-
-def _len0(x) -> int:
-    return int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.asarray(x).shape[0])
 
 
 def _trials(k: int) -> int:

@@ -13,9 +13,9 @@
 //   clus_seed_pick_kernel   one workgroup per restart: candidate potentials (fp64), arg-min (first on ties), the new centre; then the fp64 prefix
 //                           sum of the closest distances and a left binary search per draw = the next step's candidate rows
 //   clus_assign_kernel      argmin_j (||c_j||^2 - 2 x.c_j) on v_mfma_f32_32x32x2_f32 (exact fp32 operands): the 128 x 128 x 32 LDS-DMA tile of
-//                           retr_sim_kernel (retrieval.hip) with a reducing epilogue: a 5-step butterfly over the 32 lanes that hold one row's
-//                           columns, then a 64-bit atomicMin of (monotone(dist) << 32 | j) -- order-free, first minimum on ties.  The
-//                           N x R k distance matrix is never written.
+//                           f32_tile.h, which retr_sim_kernel (retrieval.hip) uses too, with a reducing epilogue: a 5-step butterfly over the
+//                           32 lanes that hold one row's columns, then a 64-bit atomicMin of (monotone(dist) << 32 | j) -- order-free, first
+//                           minimum on ties.  The N x R k distance matrix is never written.
 //   clus_post_kernel        labels out of the packed minima, number of changed labels (integer atomics)
 //   clus_update_kernel      per (restart, cluster): the sum of its rows IN ASCENDING ROW ORDER (labels compacted tile by tile, then a sequential
 //                           fp32 sum: bit-reproducible, no float atomics) and the count
@@ -28,34 +28,22 @@
 //   clus_contingency / scores   integer contingency table, then ARI / NMI / V-measure in fp64 by scikit-learn's formulas
 //
 // Limits: k <= 4096, n_init <= 64, n <= 2^24.
-#include "common.h"
+#include "f32_tile.h"
 
 namespace {
 
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-
-constexpr int CBM = 128, CBN = 128, CBK = 32;      // assign tile; CBK fp32 = one 128-B LDS row = 8 chunks of 16 B
-constexpr int CTILE_BYTES = 128 * CBK * 4;
 constexpr int CLUS_MAX_K = 4096, CLUS_MAX_INIT = 64, CLUS_MAX_N = 1 << 24;
 constexpr int CLUS_MAX_TRIALS = 12;                // 2 + int(ln 4096) = 10
 constexpr int NCHUNK = 128;                        // row chunks of the column reductions
 constexpr int SG = 16;                             // candidates per seed_dist workgroup
 constexpr unsigned long long KEY_NONE = ~0ull;
 
-static inline int64_t dpad_of(int d) { return ((int64_t)d + CBK - 1) / CBK * CBK; }
 static inline int kpad_of(int k) { return (k + 31) / 32 * 32; }
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int trials_of(int k) {
     int t = 2;      // 2 + int(ln k) without floating point on the boundary: ln k >= m  <=>  k >= ceil(e^m)
     static const int ceil_exp[] = {3, 8, 21, 55, 149, 404, 1097, 2981, 8104};
     for (int m = 0; m < 9 && k >= ceil_exp[m]; ++m) ++t;
     return t;
-}
-
-static __device__ __forceinline__ unsigned mono32(float v) {
-    const unsigned u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
 template <int THREADS> static __device__ __forceinline__ double block_sum_f64(double v, double* red, int tid) {
@@ -159,7 +147,7 @@ __global__ __launch_bounds__(256) void clus_rownorm_kernel(const float* __restri
 // One thread per point; the candidates' K tile sits in LDS (every lane reads the same address: broadcast).
 __global__ __launch_bounds__(256) void clus_seed_dist_kernel(const float* __restrict__ xc, int n, int dpad, const int32_t* __restrict__ cand, int n_cand,
                                                               int T, int first, const float* __restrict__ closest, float* __restrict__ mind) {
-    __shared__ __attribute__((aligned(16))) float tile[SG][CBK];
+    __shared__ __attribute__((aligned(16))) float tile[SG][FT_BK];
     const int tid = threadIdx.x;
     const int row = blockIdx.x * 256 + tid;
     const int g0 = blockIdx.y * SG;
@@ -168,20 +156,20 @@ __global__ __launch_bounds__(256) void clus_seed_dist_kernel(const float* __rest
     float acc[SG];
 #pragma unroll
     for (int g = 0; g < SG; ++g) acc[g] = 0.f;
-    for (int k0 = 0; k0 < dpad; k0 += CBK) {
+    for (int k0 = 0; k0 < dpad; k0 += FT_BK) {
         __syncthreads();
-        for (int e = tid; e < SG * CBK; e += 256) {
+        for (int e = tid; e < SG * FT_BK; e += 256) {
             const int g = e >> 5, c = e & 31;
             int id = g0 + g < n_cand ? cand[g0 + g] : 0;
             id = id < 0 ? 0 : (id >= n ? n - 1 : id);
             tile[g][c] = xc[(int64_t)id * dpad + k0 + c];
         }
         __syncthreads();
-        f32x4 xv[CBK / 4];
+        f32x4 xv[FT_BK / 4];
 #pragma unroll
-        for (int c4 = 0; c4 < CBK / 4; ++c4) xv[c4] = *(const f32x4*)(xr + k0 + c4 * 4);
+        for (int c4 = 0; c4 < FT_BK / 4; ++c4) xv[c4] = *(const f32x4*)(xr + k0 + c4 * 4);
 #pragma unroll
-        for (int c4 = 0; c4 < CBK / 4; ++c4)
+        for (int c4 = 0; c4 < FT_BK / 4; ++c4)
 #pragma unroll
             for (int g = 0; g < SG; ++g) {
                 const f32x4 t = *(const f32x4*)&tile[g][c4 * 4];
@@ -297,89 +285,29 @@ __global__ __launch_bounds__(256) void clus_cnorm_kernel(const float* __restrict
 }
 
 // best[rst][q] = min over the centres j of restart rst of (mono(||c_j||^2 - 2 x_q . c_j) << 32 | j).  X = points (rows of the MFMA result),
-// C = the R * kpad centre rows (its columns).  Tile, DMA staging, swizzle and k order are retr_sim_kernel's (retrieval.hip).
+// C = the R * kpad centre rows (its columns).  The product is f32_tile_product (f32_tile.h).
 __global__ __launch_bounds__(256) void clus_assign_kernel(const float* __restrict__ X, int nq, const float* __restrict__ Cn, int nd, int dpad, int k, int kpad,
                                                            const float* __restrict__ cnorm, const int32_t* __restrict__ status,
                                                            unsigned long long* __restrict__ best) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int n0 = blockIdx.x * CBN, q0 = blockIdx.y * CBM;
-    const int wr = wid >> 1, wc = wid & 1;
-    const int nk = dpad / CBK;
+    const int lane = threadIdx.x & 63;
+    const int n0 = blockIdx.x * FT_BN, q0 = blockIdx.y * FT_BM;
     {      // a tile whose restarts are all finished has nothing to do (block-uniform, before any barrier)
-        const int last = n0 + CBN - 1 < nd - 1 ? n0 + CBN - 1 : nd - 1;
+        const int last = n0 + FT_BN - 1 < nd - 1 ? n0 + FT_BN - 1 : nd - 1;
         bool live = false;
         for (int rst = n0 / kpad; rst <= last / kpad; ++rst) live |= status[rst] != 2;
         if (!live) return;
     }
-
-    auto stage_dma = [&](int st, int k0) __attribute__((always_inline)) {
-        char* qbase = smem + st * (2 * CTILE_BYTES);
-        char* dbase = qbase + CTILE_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rloc = wid * 32 + i * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((rloc >> 1) & 7);
-            int qrow = q0 + rloc, drow = n0 + rloc;
-            qrow = qrow < nq ? qrow : nq - 1;      // rows past the end repeat the last one; their results are not used
-            drow = drow < nd ? drow : nd - 1;
-            const float* qsrc = X + (int64_t)qrow * dpad + k0 + chunk * 4;
-            const float* dsrc = Cn + (int64_t)drow * dpad + k0 + chunk * 4;
-            const int dst = (wid * 32 + i * 8) * 128;      // wave-uniform; hardware adds lane * 16
-            __builtin_amdgcn_global_load_lds((gptr_t*)qsrc, (lptr_t*)(qbase + dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t*)dsrc, (lptr_t*)(dbase + dst), 16, 0, 0);
-        }
-    };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    auto compute = [&](int st) __attribute__((always_inline)) {
-        const char* qbase = smem + st * (2 * CTILE_BYTES);
-        const char* dbase = qbase + CTILE_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            f32x4 qf[2], df[2];
-            const int chunk = 2 * kk + (lane >> 5);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = wr * 64 + i * 32 + (lane & 31);
-                qf[i] = *(const f32x4*)(qbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int row = wc * 64 + j * 32 + (lane & 31);
-                df[j] = *(const f32x4*)(dbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[i][e], df[j][e], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    stage_dma(0, 0);
-    for (int kt = 0; kt < nk; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my DMA pieces of tile kt have landed
-        __syncthreads();                                      // everyone's landed; everyone finished reading buffer (kt + 1) & 1
-        if (kt + 1 < nk) stage_dma((kt + 1) & 1, (kt + 1) * CBK);
-        compute(kt & 1);
-    }
-    // C/D of the 32x32 forms: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  The 32 lanes of a half hold the 32 columns
-    // of one row: a butterfly over them leaves the row's minimum in every lane; lane (reg) keeps the one of register reg, so that the
-    // atomics of a 32-row block go out as one instruction over 256 contiguous bytes.
+    f32_tile_product(X, nq, q0, Cn, nd, n0, dpad, acc);
+    // The 32 lanes of a half wave hold the 32 columns of one row (f32_tile_row / f32_tile_col): a butterfly over them leaves the row's minimum
+    // in every lane; lane (reg) keeps the one of register reg, so that the atomics of a 32-row block go out as one instruction over 256
+    // contiguous bytes.
     int rst[2], jj[2];
     float cn[2];
     bool ok[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wc * 64 + j * 32 + (lane & 31);
+        const int col = n0 + f32_tile_col(j);
         const int cc = col < nd ? col : nd - 1;
         rst[j] = cc / kpad;      // uniform over the 32 lanes: kpad % 32 == 0
         jj[j] = cc - rst[j] * kpad;
@@ -419,7 +347,7 @@ __global__ __launch_bounds__(256) void clus_assign_kernel(const float* __restric
                 }
         }
         const int reg = lane & 31;
-        const int q = q0 + wr * 64 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+        const int q = q0 + f32_tile_row(i, reg);
         if (reg < 16 && q < nq) {
             if (mine[0] != KEY_NONE) atomicMin(best + (int64_t)rst[0] * nq + q, mine[0]);
             if (!one_restart && mine[1] != KEY_NONE) atomicMin(best + (int64_t)rst[1] * nq + q, mine[1]);
@@ -807,12 +735,6 @@ struct Workspace {
     size_t bytes;
 };
 
-template <typename T> static T* take(char*& p, size_t count) {
-    T* r = (T*)p;
-    p += align256(count * sizeof(T));
-    return r;
-}
-
 static Workspace carve(void* ws, int64_t n, int d, int k, int R) {
     Workspace w;
     const size_t dp = (size_t)dpad_of(d), kp = (size_t)kpad_of(k), T = (size_t)trials_of(k);
@@ -959,13 +881,13 @@ extern "C" int avexhip_clustering_iterate(const avexhip_clustering_args* a, int 
     hipStream_t s = (hipStream_t)stream;
     const int dp = (int)dpad_of(a->d), kp = kpad_of(a->k), R = a->n_init, n = a->n, k = a->k;
     const int st = stages == 0 ? 3 : stages;
-    AVX_ENSURE_LDS(clus_assign_kernel, 4 * CTILE_BYTES);
+    AVX_ENSURE_LDS(clus_assign_kernel, FT_LDS_BYTES);
     for (int it = 0; it < n_iters; ++it) {
         if (st & 1) {
             clus_cnorm_kernel<<<dim3((R * kp + 255) / 256), dim3(256), 0, s>>>(w.centres, R * kp, dp, w.cnorm);
             AVX_LAUNCH_CHECK();
             AVX_HIP_CHECK(hipMemsetAsync(w.best, 0xFF, (size_t)R * n * 8, s));
-            clus_assign_kernel<<<dim3((R * kp + CBN - 1) / CBN, (n + CBM - 1) / CBM), dim3(256), 4 * CTILE_BYTES, s>>>(w.xc, n, w.centres, R * kp, dp, k, kp,
+            clus_assign_kernel<<<dim3((R * kp + FT_BN - 1) / FT_BN, (n + FT_BM - 1) / FT_BM), dim3(256), FT_LDS_BYTES, s>>>(w.xc, n, w.centres, R * kp, dp, k, kp,
                                                                                                                     w.cnorm, w.status, w.best);
             AVX_LAUNCH_CHECK();
         }

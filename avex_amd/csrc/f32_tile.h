@@ -1,0 +1,116 @@
+// The fp32 product of the evaluation metrics: a 128 x 128 x 32 tile of A B^T on v_mfma_f32_32x32x2_f32 (fp32 operands, one rounding per
+// product), shared by retr_sim_kernel (retrieval.hip) and clus_assign_kernel (clustering.hip), with the small helpers both files use
+// around it.  Not for the f16 GEMM or the attention kernels: their tiles and staging differ.
+#pragma once
+#include "common.h"
+
+namespace {
+
+typedef __attribute__((address_space(1))) const void gptr_t;
+typedef __attribute__((address_space(3))) void lptr_t;
+
+constexpr int FT_BM = 128, FT_BN = 128, FT_BK = 32;      // FT_BK fp32 = one 128-B LDS row = 8 chunks of 16 B
+constexpr int FT_TILE_BYTES = 128 * FT_BK * 4;           // 16 KiB per operand tile
+constexpr int FT_LDS_BYTES = 4 * FT_TILE_BYTES;          // dynamic LDS of a launch: two operands, double-buffered
+
+static inline int64_t dpad_of(int d) { return ((int64_t)d + FT_BK - 1) / FT_BK * FT_BK; }
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the next `count` elements of a workspace carved in 256-byte steps
+template <typename T> static T* take(char*& p, size_t count) {
+    T* r = (T*)p;
+    p += align256(count * sizeof(T));
+    return r;
+}
+
+// order-preserving map of a float onto unsigned integers (-0 is folded onto +0 first by the caller)
+static __device__ __forceinline__ unsigned mono32(float v) {
+    const unsigned u = __float_as_uint(v);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+// acc = A[a0 .. a0 + 128) . B[b0 .. b0 + 128)^T for a workgroup of 256 threads with FT_LDS_BYTES of dynamic LDS.  A (na rows) and B (nb rows)
+// are row-major with dpad floats per row (dpad % 32 == 0, zero beyond the real width).  Wave (wr, wc) = (wid >> 1, wid & 1) owns rows
+// [64 wr, +64) x columns [64 wc, +64) of the tile as 2 x 2 MFMA tiles, acc[i][j] at (32 i, 32 j) of that block; f32_tile_row / f32_tile_col
+// name its elements.  Operands are staged by LDS-DMA into a double buffer with the chunk swizzle of gemm_nt_kernel (gemm.hip), one barrier
+// per K tile; every thread of the workgroup must make the call.  v_mfma_f32_32x32x2_f32 takes ONE float per lane and operand: lane
+// (i = lane & 31, h = lane >> 5) supplies row i at k-index h.  A lane reads 4 consecutive floats (one swizzled 16-B chunk, chunk 2 kk + h)
+// and feeds them to 4 MFMAs; both operands use the same k assignment, so the order of the sum inside a K tile is permuted, not its terms.
+static __device__ __forceinline__ void f32_tile_product(const float* A, int na, int a0, const float* B, int nb, int b0, int dpad,
+                                                        f32x16 (&acc)[2][2]) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+    const int nk = dpad / FT_BK;
+
+    auto stage_dma = [&](int st, int k0) __attribute__((always_inline)) {
+        char* abase = smem + st * (2 * FT_TILE_BYTES);
+        char* bbase = abase + FT_TILE_BYTES;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rloc = wid * 32 + i * 8 + (lane >> 3);
+            const int chunk = (lane & 7) ^ ((rloc >> 1) & 7);
+            int arow = a0 + rloc, brow = b0 + rloc;
+            arow = arow < na ? arow : na - 1;      // rows past the end repeat the last one; the caller does not use their results
+            brow = brow < nb ? brow : nb - 1;
+            const float* asrc = A + (int64_t)arow * dpad + k0 + chunk * 4;
+            const float* bsrc = B + (int64_t)brow * dpad + k0 + chunk * 4;
+            const int dst = (wid * 32 + i * 8) * 128;      // wave-uniform; hardware adds lane * 16
+            __builtin_amdgcn_global_load_lds((gptr_t*)asrc, (lptr_t*)(abase + dst), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t*)bsrc, (lptr_t*)(bbase + dst), 16, 0, 0);
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    auto compute = [&](int st) __attribute__((always_inline)) {
+        const char* abase = smem + st * (2 * FT_TILE_BYTES);
+        const char* bbase = abase + FT_TILE_BYTES;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            f32x4 af[2], bf[2];
+            const int chunk = 2 * kk + (lane >> 5);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int row = wr * 64 + i * 32 + (lane & 31);
+                af[i] = *(const f32x4*)(abase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int row = wc * 64 + j * 32 + (lane & 31);
+                bf[j] = *(const f32x4*)(bbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bf[j][e], acc[i][j], 0, 0, 0);
+        }
+    };
+
+    stage_dma(0, 0);
+    for (int kt = 0; kt < nk; ++kt) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my DMA pieces of tile kt have landed
+        __syncthreads();                                      // everyone's landed; everyone finished reading buffer (kt + 1) & 1
+        if (kt + 1 < nk) stage_dma((kt + 1) & 1, (kt + 1) * FT_BK);
+        compute(kt & 1);
+    }
+}
+
+// Row and column, within the 128 x 128 tile, of acc[i][j][reg] of the calling thread (C/D layout of the 32x32 MFMA forms inside the wave's
+// 64 x 64 block).  The 32 lanes of a half wave hold the 32 columns of one row.
+static __device__ __forceinline__ int f32_tile_row(int i, int reg) {
+    const int lane = threadIdx.x & 63, wr = threadIdx.x >> 7;
+    return wr * 64 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+}
+static __device__ __forceinline__ int f32_tile_col(int j) {
+    const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
+    return wc * 64 + j * 32 + (lane & 31);
+}
+
+}  // namespace

@@ -4,30 +4,22 @@
 //   retr_normalize_kernel   rows / max(||row||_2, 1e-12) in fp32 (retrieval.py:242), written once with the width padded to the K tile
 //   retr_pack_kernel        multi-hot label rows -> 64-bit words: relevance "shares an active class" (retrieval.py:152) is (a & b) != 0
 //   retr_sim_kernel         S[b][n] = q^_b . d^_n on v_mfma_f32_32x32x2_f32: fp32 operands, one rounding per product (an f16-operand
-//                           product moves the mean AUC by 1e-6 and flips precision@k hits).  128 x 128 x 32 tiles, LDS-DMA double buffer
-//                           with the chunk swizzle of gemm_nt_kernel (gemm.hip).
+//                           product moves the mean AUC by 1e-6 and flips precision@k hits).  The 128 x 128 x 32 LDS-DMA tile of f32_tile.h.
 //   retr_rank_kernel        one workgroup per query row: relevance bits, top-k, and the Mann-Whitney count
 //                               U2 = sum over (positive p, negative n) of 2 [s_p > s_n] + [s_p == s_n]          AUC = U2 / (2 P Q)
 //                           as a 64-bit integer: exact for the similarities as computed, independent of any summation order.  The smaller
 //                           of {positives, negatives} is sorted in LDS (bitonic, chunks of <= 16 Ki keys); every element of the other side
 //                           does a lower- and an upper-bound search in it.
 //   retr_finalize_kernel    validity rules of the reference + the fp64 means, in a fixed order (bit-reproducible).
-#include "common.h"
+#include "f32_tile.h"
 
 namespace {
 
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-
-constexpr int RBM = 128, RBN = 128, RBK = 32;      // similarity tile; RBK fp32 = one 128-B LDS row = 8 chunks of 16 B
-constexpr int RTILE_BYTES = 128 * RBK * 4;         // 16 KiB per operand tile
 constexpr int RANK_THREADS = 256;
 constexpr int RANK_MAX_K = 32;
 constexpr int RANK_MAX_CAP = 16384;                // keys per sorted chunk (64 KiB of LDS)
 constexpr int RETR_MAX_DB = 1 << 19;               // relevance bits of one row: 64 KiB of LDS
 
-static inline int64_t dpad_of(int d) { return ((int64_t)d + RBK - 1) / RBK * RBK; }
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int64_t ldsim_of(int64_t n_db) { return (n_db + 63) / 64 * 64; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -58,86 +50,21 @@ __global__ __launch_bounds__(256) void retr_pack_kernel(const uint8_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// S[q][n] for q in [0, nq), n in [0, nd): Q and D are normalised rows of dpad floats (dpad % 32 == 0, zero beyond d).  Wave (wr, wc) owns
-// queries [64 wr, +64) x database rows [64 wc, +64) of the tile as 2 x 2 MFMA tiles.  v_mfma_f32_32x32x2_f32 takes ONE float per lane and
-// operand: lane (i = lane & 31, h = lane >> 5) supplies row i at k-index h.  A lane reads 4 consecutive floats (one swizzled 16-B chunk,
-// chunk 2 kk + h) and feeds them to 4 MFMAs; both operands use the same k assignment, so the order of the sum inside a K tile is
-// permuted, not its terms.
+// S[q][n] for q in [0, nq), n in [0, nd): Q and D are normalised rows of dpad floats (dpad % 32 == 0, zero beyond d).  The product is
+// f32_tile_product (f32_tile.h); this kernel adds the store.
 __global__ __launch_bounds__(256) void retr_sim_kernel(const float* __restrict__ Q, int nq, const float* __restrict__ D, int nd, int dpad,
                                                         float* __restrict__ S, int64_t lds_) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int n0 = blockIdx.x * RBN, q0 = blockIdx.y * RBM;
-    const int wr = wid >> 1, wc = wid & 1;
-    const int nk = dpad / RBK;
-
-    auto stage_dma = [&](int st, int k0) __attribute__((always_inline)) {
-        char* qbase = smem + st * (2 * RTILE_BYTES);
-        char* dbase = qbase + RTILE_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rloc = wid * 32 + i * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((rloc >> 1) & 7);
-            int qrow = q0 + rloc, drow = n0 + rloc;
-            qrow = qrow < nq ? qrow : nq - 1;      // rows past the end repeat the last one; their results are not stored
-            drow = drow < nd ? drow : nd - 1;
-            const float* qsrc = Q + (int64_t)qrow * dpad + k0 + chunk * 4;
-            const float* dsrc = D + (int64_t)drow * dpad + k0 + chunk * 4;
-            const int dst = (wid * 32 + i * 8) * 128;      // wave-uniform; hardware adds lane * 16
-            __builtin_amdgcn_global_load_lds((gptr_t*)qsrc, (lptr_t*)(qbase + dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t*)dsrc, (lptr_t*)(dbase + dst), 16, 0, 0);
-        }
-    };
+    const int n0 = blockIdx.x * FT_BN, q0 = blockIdx.y * FT_BM;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    auto compute = [&](int st) __attribute__((always_inline)) {
-        const char* qbase = smem + st * (2 * RTILE_BYTES);
-        const char* dbase = qbase + RTILE_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            f32x4 qf[2], df[2];
-            const int chunk = 2 * kk + (lane >> 5);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = wr * 64 + i * 32 + (lane & 31);
-                qf[i] = *(const f32x4*)(qbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int row = wc * 64 + j * 32 + (lane & 31);
-                df[j] = *(const f32x4*)(dbase + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[i][e], df[j][e], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    stage_dma(0, 0);
-    for (int kt = 0; kt < nk; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my DMA pieces of tile kt have landed
-        __syncthreads();                                      // everyone's landed; everyone finished reading buffer (kt + 1) & 1
-        if (kt + 1 < nk) stage_dma((kt + 1) & 1, (kt + 1) * RBK);
-        compute(kt & 1);
-    }
-    // C/D of the 32x32 forms: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    f32_tile_product(Q, nq, q0, D, nd, n0, dpad, acc);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wc * 64 + j * 32 + (lane & 31);
+            const int n = n0 + f32_tile_col(j);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int q = q0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int q = q0 + f32_tile_row(i, r);
                 if (q < nq && n < nd) S[(int64_t)q * lds_ + n] = acc[i][j][r];
             }
         }
@@ -156,12 +83,6 @@ struct RankArgs {
     int32_t* stats;
     int32_t* topk;
 };
-
-// order-preserving map of a float onto unsigned integers (-0 is folded onto +0 first by the caller)
-static __device__ __forceinline__ unsigned mono32(float v) {
-    const unsigned u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
 
 static __device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red, int tid) {
 #pragma unroll
@@ -388,12 +309,9 @@ static Workspace carve(void* ws, int64_t n_db, int d, int batch) {
     Workspace w;
     const size_t dp = (size_t)dpad_of(d);
     char* p = (char*)ws;
-    w.dbn = (float*)p;
-    p += align256((size_t)n_db * dp * 4);
-    w.qn = (float*)p;
-    p += align256((size_t)batch * dp * 4);
-    w.sim = (float*)p;
-    p += align256((size_t)batch * (size_t)ldsim_of(n_db) * 4);
+    w.dbn = take<float>(p, (size_t)n_db * dp);
+    w.qn = take<float>(p, (size_t)batch * dp);
+    w.sim = take<float>(p, (size_t)batch * (size_t)ldsim_of(n_db));
     w.bytes = (size_t)(p - (char*)ws);
     return w;
 }
@@ -466,9 +384,9 @@ extern "C" int avexhip_retrieval_batch(const avexhip_retrieval_args* a, void* st
             AVX_LAUNCH_CHECK();
             qn = w.qn;
         }
-        AVX_ENSURE_LDS(retr_sim_kernel, 4 * RTILE_BYTES);
-        const dim3 grid((a->n_db + RBN - 1) / RBN, (a->nb + RBM - 1) / RBM);
-        retr_sim_kernel<<<grid, dim3(256), 4 * RTILE_BYTES, s>>>(qn, a->nb, w.dbn, a->n_db, dp, w.sim, lds_);
+        AVX_ENSURE_LDS(retr_sim_kernel, FT_LDS_BYTES);
+        const dim3 grid((a->n_db + FT_BN - 1) / FT_BN, (a->nb + FT_BM - 1) / FT_BM);
+        retr_sim_kernel<<<grid, dim3(256), FT_LDS_BYTES, s>>>(qn, a->nb, w.dbn, a->n_db, dp, w.sim, lds_);
         AVX_LAUNCH_CHECK();
         if (a->sim_out) {
             AVX_REQUIRE(a->ld_sim >= a->n_db, "retrieval_batch: ld_sim %lld < n_db", (long long)a->ld_sim);

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._metric_inputs import _as_tensor, _device_of, _joint_ids, _len0, _stream
 
 MAX_K = 32                     # avexhip_retrieval_max_k(): the rank kernel's top-k limit
 MAX_DB = 1 << 19               # database items per call: a row's relevance bits live in LDS (64 KiB)
@@ -53,10 +54,6 @@ __all__ = ["evaluate_auc_roc", "evaluate_auc_roc_batched", "evaluate_auc_roc_cro
 # ------------------------------------------------------------------------------------------------------------------------------
 def _ndim(x) -> int:
     return x.dim() if isinstance(x, torch.Tensor) else np.asarray(x).ndim
-
-
-def _len0(x) -> int:
-    return int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.asarray(x).shape[0])
 
 
 def _non_numeric(x) -> bool:
@@ -78,27 +75,6 @@ def _label_tensors(query_labels, db_labels=None):
     return codes[: q.shape[0]], None if db_labels is None else codes[q.shape[0]:]
 
 
-def _as_tensor(x) -> torch.Tensor:
-    """A torch tensor over a numeric `x` where it lives."""
-    if isinstance(x, torch.Tensor):
-        return x
-    a = np.asarray(x)
-    if a.dtype.kind not in "biuf":
-        raise ValueError(f"dtype {a.dtype} is not numeric")
-    if a.dtype.kind == "u" and a.dtype.itemsize > 1:
-        a = a.astype(np.int64)
-    if a.dtype == np.float16:
-        a = a.astype(np.float32)
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def _device_of(*xs) -> torch.device:
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _embeddings(x, dev: torch.device) -> torch.Tensor:
     t = _as_tensor(x)
     if t.dim() != 2:
@@ -112,17 +88,6 @@ def _collapse_one_hot(lab: torch.Tensor) -> torch.Tensor:
         if bool((lab.sum(dim=1) == 1).all()):
             return lab.argmax(dim=1)
     return lab
-
-
-def _joint_ids(q: torch.Tensor, d: Optional[torch.Tensor], dev: torch.device):
-    """Dense int32 class ids with `==` preserved across both sets."""
-    if d is None:
-        inv = torch.unique(q.to(dev), return_inverse=True)[1]
-        ids = inv.to(torch.int32).contiguous()
-        return ids, ids
-    dt = torch.promote_types(q.dtype, d.dtype)
-    inv = torch.unique(torch.cat([q.to(dev).to(dt), d.to(dev).to(dt)]), return_inverse=True)[1].to(torch.int32)
-    return inv[: q.shape[0]].contiguous(), inv[q.shape[0]:].contiguous()
 
 
 def _pack(lab: torch.Tensor, dev: torch.device) -> torch.Tensor:
@@ -159,10 +124,6 @@ def _relevance(qlab: torch.Tensor, dlab: Optional[torch.Tensor], dev: torch.devi
         return "words", _pack(qlab, dev), _pack(dlab, dev)
     # 1-D database labels under 2-D multi-hot queries: all-zero relevance (retrieval.py:191-194)
     return ("ids", torch.full((qlab.shape[0],), -1, dtype=torch.int32, device=dev), torch.zeros((dlab.shape[0],), dtype=torch.int32, device=dev))
-
-
-def _stream() -> int:
-    return int(torch.cuda.current_stream().cuda_stream)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
