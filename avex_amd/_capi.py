@@ -99,6 +99,13 @@ class ClusteringArgs(C.Structure):
                 ("seeds_out", C.c_void_p), ("summary_out", C.c_void_p)]
 
 
+class SilhouetteArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("ld_x", C.c_int64), ("n", C.c_int32), ("d", C.c_int32), ("metric", C.c_int32), ("n_labels", C.c_int32),
+                ("n_slots", C.c_int32), ("batch", C.c_int32), ("slot_src", C.c_void_p), ("group_label", C.c_void_p), ("counts", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("row0", C.c_int32), ("nb", C.c_int32), ("stages", C.c_int32),
+                ("reserved", C.c_int32), ("samples_out", C.c_void_p)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -226,6 +233,13 @@ SYMBOLS = {
     "avexhip_clustering_finish": (C.c_int, [C.POINTER(ClusteringArgs), _P]),
     "avexhip_clustering_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "avexhip_clustering_scores": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
+    "avexhip_clustering_centred_rows": (_P, [C.POINTER(ClusteringArgs)]),
+    "avexhip_silhouette_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "avexhip_silhouette_max_labels": (C.c_int, []),
+    "avexhip_silhouette_max_n": (C.c_int, []),
+    "avexhip_silhouette_prepare": (C.c_int, [C.POINTER(SilhouetteArgs), _P]),
+    "avexhip_silhouette_batch": (C.c_int, [C.POINTER(SilhouetteArgs), _P]),
+    "avexhip_silhouette_finalize": (C.c_int, [C.POINTER(SilhouetteArgs), _P, _P]),
 }
 
 # exported by the diagnostic build only (-DAVEX_DIAG; AVEX_AMD_DIAG=1 python -m avex_amd.build, then AVEX_AMD_LIB=.../libavexhip_diag.so)

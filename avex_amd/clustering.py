@@ -26,6 +26,11 @@ invariant under renaming clusters.  What is computed, and where it differs from 
   NaN or infinite embeddings, found by a flag of the centring pass that is read back with the results.
 * Limits: ``n_clusters <= MAX_K`` (4096), ``n_init <= MAX_INIT`` (64), ``N <= MAX_N`` (2^24); beyond them ``ValueError``.
 
+``silhouette_samples`` / ``silhouette_score`` are scikit-learn's functions of those names (metric ``"euclidean"`` or ``"cosine"``) on the
+device: the metric the reference dropped "for speed" (clustering.py:123) while its configs still list ``clustering_silhouette``.
+``eval_clustering_silhouette`` / ``eval_clustering_multiple_k_silhouette`` are the two reference functions with that column added; the
+reference's own two keep their signatures and return values.
+
 ``kmeans`` and ``clustering_scores`` are the layers below.  Sharding the points over ranks is not built; the per-cluster sums and
 counts of the update step are where an all-reduce would go.
 """
@@ -48,7 +53,12 @@ MAX_INIT = 64
 MAX_N = 1 << 24
 _POLL_EVERY = 8                # Lloyd iterations enqueued between two looks at the "restarts not finished" word
 
-__all__ = ["eval_clustering", "eval_clustering_multiple_k", "kmeans", "clustering_scores", "MAX_K"]
+MAX_SIL_N = 1 << 19            # avexhip_silhouette_max_n()
+MAX_SIL_LABELS = 4096          # avexhip_silhouette_max_labels()
+_SIL_METRICS = {"euclidean": 0, "cosine": 1}      # AVEXHIP_SILHOUETTE_*
+
+__all__ = ["eval_clustering", "eval_clustering_multiple_k", "kmeans", "clustering_scores", "MAX_K", "silhouette_samples", "silhouette_score",
+           "eval_clustering_silhouette", "eval_clustering_multiple_k_silhouette"]
 
 
 def _get_empty_clustering_metrics() -> Dict[str, float]:
@@ -113,6 +123,13 @@ class _Prepared:
         a.x, a.ld_x, a.n, a.d, a.k, a.n_init, a.max_iter, a.tol = self.x.data_ptr(), self.x.stride(0), self.n, self.d, k, self.n_init, max_iter, self.tol
         a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.bytes
         return a
+
+    def centred_rows(self):
+        """(device address, row stride in floats) of X - mean as the centring pass left it."""
+        ptr = self.lib.avexhip_clustering_centred_rows(C.byref(self.args(self.k_max, 1)))
+        if not ptr:
+            raise _capi.AvexHipError("clustering workspace holds no centred rows")
+        return int(ptr), (self.d + 31) // 32 * 32
 
 
 def _check_kmeans_args(n: int, n_clusters: int, n_init: int, max_iter: int) -> None:
@@ -250,6 +267,159 @@ def clustering_scores(labels_true, labels_pred) -> Dict[str, float]:
         return {"ari": float(h[0]), "nmi": float(h[1]), "v_measure": float(h[2])}
 
 
+def _check_random_state(seed) -> np.random.RandomState:
+    """sklearn.utils.check_random_state."""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        return np.random.RandomState(int(seed))
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise ValueError(f"{seed!r} cannot be used to seed a numpy.random.RandomState instance")
+
+
+def _label_tensor(labels) -> torch.Tensor:
+    """1-D labels as a tensor where they live; a non-numeric NumPy dtype (strings, objects) is numbered on the host first."""
+    if not isinstance(labels, torch.Tensor):
+        a = np.asarray(labels)
+        if a.dtype.kind not in "biuf":
+            labels = np.unique(a.reshape(-1), return_inverse=True)[1].astype(np.int64).reshape(a.shape)
+    t = _as_tensor(labels)
+    if t.dim() != 1:
+        raise ValueError(f"y should be a 1d array, got an array of shape {tuple(t.shape)} instead.")
+    return t
+
+
+def _sil_layout(ids: torch.Tensor, n_labels: int, dev: torch.device):
+    """The cluster-ordered layout of avexhip_silhouette_args: rows in label order (stable: ascending row inside a cluster), every cluster
+    padded to a multiple of 32 slots, the whole to a multiple of 128.  -> slot_src, group_label, counts (int32, device), n_slots."""
+    n = int(ids.numel())
+    ids64 = ids.to(torch.int64)
+    counts = torch.bincount(ids64, minlength=n_labels)
+    counts_h = counts.cpu().numpy()
+    padded = (counts_h + 31) // 32 * 32
+    offset = np.concatenate([[0], np.cumsum(padded)])
+    n_slots = int((offset[-1] + 127) // 128 * 128)
+    start = np.cumsum(counts_h) - counts_h
+    shift = torch.from_numpy((offset[:-1] - start).astype(np.int64)).to(dev)
+    order = torch.argsort(ids64, stable=True)
+    slot = torch.arange(n, device=dev, dtype=torch.int64) + shift[ids64[order]]
+    slot_src = torch.full((n_slots,), -1, dtype=torch.int32, device=dev)
+    slot_src[slot] = order.to(torch.int32)
+    group = np.full(n_slots // 32, -1, dtype=np.int32)
+    group[: int(offset[-1]) // 32] = np.repeat(np.arange(n_labels, dtype=np.int32), padded // 32)
+    return slot_src, torch.from_numpy(group).to(dev), counts.to(torch.int32).contiguous(), n_slots
+
+
+def _sil_launch(rows_ptr: int, ld: int, n: int, d: int, ids: torch.Tensor, n_labels: int, metric: str, batch_size: int, dev: torch.device,
+                _timing: Optional[dict] = None):
+    """-> (samples [n] fp64, summary [2] fp64 = mean, finite flag), both on the device; nothing is read back here but the cluster sizes."""
+    lib = _capi.lib()
+    slot_src, group, counts, n_slots = _sil_layout(ids, n_labels, dev)
+    batch = min(max(int(batch_size), 1), n_slots)
+    nbytes = int(lib.avexhip_silhouette_workspace_bytes(n_slots, d, n_labels, batch))
+    if nbytes == 0:
+        raise ValueError(f"silhouette workspace: unsupported shape (n {n}, d {d}, labels {n_labels}, batch {batch})")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    samples = torch.zeros((n,), dtype=torch.float64, device=dev)
+    summary = torch.empty((2,), dtype=torch.float64, device=dev)
+    a = _capi.SilhouetteArgs()
+    a.x, a.ld_x, a.n, a.d, a.metric, a.n_labels, a.n_slots, a.batch = rows_ptr, ld, n, d, _SIL_METRICS[metric], n_labels, n_slots, batch
+    a.slot_src, a.group_label, a.counts = slot_src.data_ptr(), group.data_ptr(), counts.data_ptr()
+    a.workspace, a.workspace_bytes, a.samples_out = ws.data_ptr(), nbytes, samples.data_ptr()
+    s = _stream()
+    ev = []
+
+    def mark():
+        if _timing is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            ev.append(e)
+
+    mark()
+    _capi.check(lib.avexhip_silhouette_prepare(C.byref(a), s), "silhouette_prepare")
+    mark()
+    for row0 in range(0, n_slots, batch):
+        a.row0, a.nb = row0, min(batch, n_slots - row0)
+        for stage in ((0,) if _timing is None else (1, 2)):      # timed: the product and the per-point pass launched apart
+            a.stages = stage
+            _capi.check(lib.avexhip_silhouette_batch(C.byref(a), s), "silhouette_batch")
+            mark()
+    _capi.check(lib.avexhip_silhouette_finalize(C.byref(a), summary.data_ptr(), s), "silhouette_finalize")
+    mark()
+    if _timing is not None:
+        torch.cuda.synchronize(dev)
+        dt = [ev[i].elapsed_time(ev[i + 1]) * 1e-3 for i in range(len(ev) - 1)]
+        _timing["prepare_s"] = _timing.get("prepare_s", 0.0) + dt[0]
+        _timing["product_s"] = _timing.get("product_s", 0.0) + sum(dt[1:-1:2])
+        _timing["finalize_s"] = _timing.get("finalize_s", 0.0) + sum(dt[2:-1:2]) + dt[-1]
+        _timing["n_slots"] = n_slots
+    return samples, summary
+
+
+def _silhouette(X, labels, metric, sample_size, random_state, batch_size, _timing=None):
+    if metric not in _SIL_METRICS:
+        raise ValueError(f"metric must be 'euclidean' or 'cosine', got {metric!r}")
+    t = _as_tensor(X)
+    if t.dim() != 2:
+        raise ValueError(f"Expected 2D array, got {t.dim()}D array instead")
+    lab = _label_tensor(labels)
+    if int(t.shape[0]) != int(lab.shape[0]):
+        raise ValueError(f"Found input variables with inconsistent numbers of samples: [{int(t.shape[0])}, {int(lab.shape[0])}]")
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    idx = None
+    if sample_size is not None:
+        idx = _check_random_state(random_state).permutation(int(t.shape[0]))[: int(sample_size)]      # scikit-learn's draw, on the host
+    n = int(t.shape[0]) if idx is None else int(idx.shape[0])
+    if n > MAX_SIL_N:
+        raise ValueError(f"{n} points exceed the silhouette kernels' limit of {MAX_SIL_N}")
+    if n > 0 and int(t.shape[1]) == 0:
+        raise ValueError("X must have a non-zero width")
+    _capi.require_gpu()
+    dev = _device_of(X, labels)
+    with torch.cuda.device(dev):
+        xd, lab = _embeddings(X, dev), lab.to(dev)
+        if idx is not None:                        # rows and labels gathered on the device
+            idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+            xd, lab = xd[idx_d].contiguous(), lab[idx_d]
+        ids, n_labels = _dense_ids(lab, dev)
+        if not 1 < n_labels < n:
+            raise ValueError(f"Number of labels is {n_labels}. Valid values are 2 to n_samples - 1 (inclusive)")
+        if n_labels > MAX_SIL_LABELS:
+            raise ValueError(f"{n_labels} labels exceed the silhouette kernels' limit of {MAX_SIL_LABELS}")
+        if metric == "euclidean":                  # distances do not change under translation; the fp32 Gram form needs small norms
+            prep = _Prepared(xd, 1, 1, 1e-4)
+            ptr, ld = prep.centred_rows()
+        else:
+            ptr, ld = xd.data_ptr(), xd.stride(0)
+        samples, summary = _sil_launch(ptr, ld, n, int(xd.shape[1]), ids, n_labels, metric, batch_size, dev, _timing)
+        host = summary.cpu()                       # the mean and the finite flag in one read-back
+        if not bool(host[1]):
+            raise ValueError("Input X contains NaN or infinity.")
+        return samples, float(host[0])
+
+
+def silhouette_samples(X, labels, *, metric: str = "euclidean", batch_size: int = 2048) -> torch.Tensor:
+    """scikit-learn's ``silhouette_samples(X, labels, metric=...)`` on the device: an ``[N]`` fp64 device tensor.
+
+    ``X`` (NumPy or torch, host or device, any float dtype) is computed in fp32; ``labels`` are any integers or a non-numeric NumPy
+    dtype.  ``metric="euclidean"`` is ``sqrt(max(||x||^2 + ||y||^2 - 2 x.y, 0))`` on the centred rows, ``"cosine"`` is
+    ``clip(1 - x^.y^, 0, 2)`` on rows divided by ``max(||row||, 1e-12)``; anything else raises.  ``a`` is the mean distance to the other
+    members of the point's cluster, ``b`` the smallest mean distance to another cluster, ``s = (b - a) / max(a, b)``; a point alone in
+    its cluster gets 0.  ``batch_size`` rows of the cluster-ordered layout are handled per launch (working memory
+    ``O(N D + batch_size n_labels)``); the result is the same bit for bit for every ``batch_size`` and from run to run."""
+    return _silhouette(X, labels, metric, None, None, batch_size)[0]
+
+
+def silhouette_score(X, labels, *, metric: str = "euclidean", sample_size: Optional[int] = None, random_state=None, batch_size: int = 2048,
+                     _timing: Optional[dict] = None) -> float:
+    """scikit-learn's ``silhouette_score``: the mean of ``silhouette_samples`` (an fp64 sum in a fixed order), as a Python float.
+    ``sample_size``: the subsample ``check_random_state(random_state).permutation(N)[:sample_size]``, drawn on the host as scikit-learn
+    draws it; the number of labels is checked on the subsample."""
+    return _silhouette(X, labels, metric, sample_size, random_state, batch_size, _timing)[1]
+
+
 def _reduce_labels(labels) -> torch.Tensor:
     """clustering.py:66-72: [N, 1] squeezed, wider label matrices reduced by argmax."""
     lab = _as_tensor(labels)
@@ -258,16 +428,25 @@ def _reduce_labels(labels) -> torch.Tensor:
     return lab.reshape(-1)
 
 
-def _eval_prepared(prep: _Prepared, true_ids: torch.Tensor, n_true: int, k: int, random_state) -> Dict[str, float]:
+def _eval_prepared(prep: _Prepared, true_ids: torch.Tensor, n_true: int, k: int, random_state, silhouette: bool = False) -> Dict[str, float]:
     dev = prep.x.device
     run = _run(prep, k, 300, random_state, None)
     out = torch.empty((3,), dtype=torch.float64, device=dev)
     _scores_launch(true_ids, n_true, run["labels"], k, out)
-    host = torch.cat([out, run["_summary"].to(torch.float64)]).cpu()      # the scores and the finite flag in one read-back
+    sil = torch.zeros((2,), dtype=torch.float64, device=dev)
+    if silhouette:                                 # of the partition just computed, on the rows the centring pass left
+        ids, n_ids = _dense_ids(run["labels"], dev)
+        if 2 <= n_ids <= prep.n - 1 and n_ids <= MAX_SIL_LABELS and prep.n <= MAX_SIL_N:
+            ptr, ld = prep.centred_rows()
+            sil = _sil_launch(ptr, ld, prep.n, prep.d, ids, n_ids, "euclidean", 2048, dev)[1]
+    host = torch.cat([out, run["_summary"].to(torch.float64), sil]).cpu()      # the scores and the finite flag in one read-back
+    extra = {"clustering_silhouette": 0.0} if silhouette else {}
     if not bool(host[3 + 2]):
         logger.error("Clustering evaluation failed: Input X contains NaN or infinity.")
-        return _get_empty_clustering_metrics()
-    return {"clustering_ari": float(host[0]), "clustering_nmi": float(host[1]), "clustering_v_measure": float(host[2])}
+        return {**_get_empty_clustering_metrics(), **extra}
+    if silhouette:
+        extra["clustering_silhouette"] = float(host[7])
+    return {"clustering_ari": float(host[0]), "clustering_nmi": float(host[1]), "clustering_v_measure": float(host[2]), **extra}
 
 
 def eval_clustering(embeds, labels, n_clusters: Optional[int] = None, random_state: int = 42) -> Dict[str, float]:
@@ -282,11 +461,25 @@ def eval_clustering(embeds, labels, n_clusters: Optional[int] = None, random_sta
     return _eval(embeds, labels, [n_clusters], random_state)[0][1]
 
 
-def _eval(embeds, labels, ks, random_state):
+def eval_clustering_silhouette(embeds, labels, n_clusters: Optional[int] = None, random_state: int = 42) -> Dict[str, float]:
+    """``eval_clustering`` with one more key, ``"clustering_silhouette"``: the Euclidean silhouette score of the k-means partition it
+    computes, on the same centred data (the column the reference's configs ask for and its code no longer fills).  0.0 wherever
+    ``eval_clustering`` returns the all-zero dict."""
+    empty = {**_get_empty_clustering_metrics(), "clustering_silhouette": 0.0}
+    if _numel(embeds) == 0 or _numel(labels) == 0:
+        logger.warning("Empty embeddings or labels provided to clustering evaluation")
+        return empty
+    if _len0(embeds) != _len0(labels):
+        raise ValueError(f"Embeddings and labels must have same length: {_len0(embeds)} vs {_len0(labels)}")
+    return _eval(embeds, labels, [n_clusters], random_state, silhouette=True)[0][1]
+
+
+def _eval(embeds, labels, ks, random_state, silhouette: bool = False):
     """[(k, metrics)] for every k in ks (None = the number of distinct labels >= 0): the data is centred and uploaded once."""
     n = _len0(embeds)
+    zero = {**_get_empty_clustering_metrics(), **({"clustering_silhouette": 0.0} if silhouette else {})}
     if _as_tensor(embeds).dim() != 2:
-        return [(k, _get_empty_clustering_metrics()) for k in ks]      # scikit-learn raises on anything but a 2-D array: swallowed
+        return [(k, dict(zero)) for k in ks]      # scikit-learn raises on anything but a 2-D array: swallowed
     _capi.require_gpu()
     dev = _device_of(embeds, labels)
     with torch.cuda.device(dev):
@@ -309,9 +502,9 @@ def _eval(embeds, labels, ks, random_state):
         for k in resolved:
             if k < 2:
                 logger.warning(f"Need at least 2 clusters for meaningful clustering evaluation, got {k}")
-                res.append((k, _get_empty_clustering_metrics()))
+                res.append((k, dict(zero)))
             else:
-                res.append((k, _eval_prepared(prep, true_ids, n_true, k, random_state)))
+                res.append((k, _eval_prepared(prep, true_ids, n_true, k, random_state, silhouette)))
         return res
 
 
@@ -319,9 +512,21 @@ def eval_clustering_multiple_k(embeds, labels, k_range: Optional[tuple] = None, 
     """The best of ``eval_clustering`` over a range of k, by ARI, the first on ties (clustering.py:114-190): ``{"clustering_best_k",
     "clustering_ari_best", "clustering_nmi_best", "clustering_v_measure_best"}``.  Default range: ``max(2, true_k - 2) ..
     min(N // 2, true_k + 3)``; the range stops at ``k >= N``.  The data is centred and uploaded once."""
+    return _eval_multiple_k(embeds, labels, k_range, random_state, False)
+
+
+def eval_clustering_multiple_k_silhouette(embeds, labels, k_range: Optional[tuple] = None, random_state: int = 42) -> Dict[str, float]:
+    """``eval_clustering_multiple_k`` with one more key, ``"clustering_silhouette_best"``: the Euclidean silhouette score at the k its
+    (unchanged) ARI rule selects; 0.0 wherever it returns the all-zero dict."""
+    return _eval_multiple_k(embeds, labels, k_range, random_state, True)
+
+
+def _eval_multiple_k(embeds, labels, k_range, random_state, silhouette: bool) -> Dict[str, float]:
+    """``eval_clustering_multiple_k``; with ``silhouette`` each k also carries its silhouette score and the winner's is reported."""
+    empty = {**_get_empty_clustering_best_metrics(), **({"clustering_silhouette_best": 0.0} if silhouette else {})}
     if _numel(embeds) == 0 or _numel(labels) == 0:
         logger.warning("Empty embeddings or labels provided to clustering evaluation")
-        return _get_empty_clustering_best_metrics()
+        return empty
     n = _len0(embeds)
     if k_range is None:
         lab = _reduce_labels(labels)
@@ -329,13 +534,15 @@ def eval_clustering_multiple_k(embeds, labels, k_range: Optional[tuple] = None, 
         k_range = (max(2, true_k - 2), min(n // 2, true_k + 3))
     ks = [k for k in range(int(k_range[0]), int(k_range[1]) + 1) if k < n]
     if not ks:
-        return _get_empty_clustering_best_metrics()
+        return empty
     if n != _len0(labels):
         raise ValueError(f"Embeddings and labels must have same length: {n} vs {_len0(labels)}")
     best, best_score = {}, -1.0
-    for k, m in _eval(embeds, labels, ks, random_state):
+    for k, m in _eval(embeds, labels, ks, random_state, silhouette):
         if m["clustering_ari"] > best_score:
             best_score = m["clustering_ari"]
             best = {"clustering_best_k": float(k), "clustering_ari_best": m["clustering_ari"], "clustering_nmi_best": m["clustering_nmi"],
                     "clustering_v_measure_best": m["clustering_v_measure"]}
-    return best if best else _get_empty_clustering_best_metrics()
+            if silhouette:
+                best["clustering_silhouette_best"] = m["clustering_silhouette"]
+    return best if best else empty

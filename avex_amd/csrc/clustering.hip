@@ -805,6 +805,12 @@ extern "C" size_t avexhip_clustering_workspace_bytes(int64_t n, int d, int k, in
 
 extern "C" int avexhip_clustering_max_k(void) { return CLUS_MAX_K; }
 
+extern "C" const float* avexhip_clustering_centred_rows(const avexhip_clustering_args* a) {
+    if (!a || !a->workspace || a->n < 1 || a->n > CLUS_MAX_N || a->d < 1 || a->k < 1 || a->k > CLUS_MAX_K || a->n_init < 1 || a->n_init > CLUS_MAX_INIT) return nullptr;
+    const Workspace w = carve(a->workspace, a->n, a->d, a->k, a->n_init);
+    return a->workspace_bytes >= w.bytes ? w.xc : nullptr;
+}
+
 extern "C" int avexhip_clustering_trials(int k) { return k >= 1 ? trials_of(k) : 0; }
 
 extern "C" int avexhip_clustering_prepare(const avexhip_clustering_args* a, void* stream) {

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 11
+#define AVEXHIP_ABI_VERSION 12
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -448,6 +448,56 @@ size_t avexhip_clustering_scores_workspace_bytes(int n_true, int n_pred);
 /* ids dense in [0, n_true) and [0, n_pred); out_dev[3] fp64 = ARI, NMI, V-measure */
 int avexhip_clustering_scores(const int32_t* true_ids_dev, int n_true, const int32_t* pred_ids_dev, int n_pred, int n, void* workspace,
                               size_t workspace_bytes, double* out_dev, void* stream);
+
+/* The centred rows avexhip_clustering_prepare left in the workspace: [n] rows of fp32, row stride = d rounded up to 32 (zero beyond d).
+ * NULL on bad arguments.  This is what the Euclidean silhouette below reads (ABI 12). */
+const float* avexhip_clustering_centred_rows(const avexhip_clustering_args* args);
+
+/* ------------------------------------------------------------------------------------------
+ * Silhouette coefficient (ABI 12): scikit-learn's silhouette_samples / silhouette_score for embeddings that are already on the
+ * device -- the metric avex/evaluation/clustering.py dropped "for speed" while its configs still list clustering_silhouette.
+ * Pairwise distances are fp32 products on the fp32 MFMA; "euclidean" is sqrt(max(||x||^2 + ||y||^2 - 2 x.y, 0)) on the rows as given
+ * (pass centred rows: avexhip_clustering_centred_rows), with the norms taken from the diagonal of the same product, so that
+ * bit-identical rows are at distance exactly 0; "cosine" is clip(1 - x^.y^, 0, 2) on rows divided by max(||row||, 1e-12).  The
+ * distance of a point to itself is 0.  Per (point, cluster) the distances are summed in fp64 over 32 columns, then in 64-bit fixed
+ * point with integer atomics: the result is the same bit for bit from run to run and for every batch.  The N x N matrix is never
+ * written; working memory is O(n_slots x d + batch x n_labels).  Nothing here allocates or synchronises.
+ * The caller lays the rows out by cluster: slot_src[n_slots] = input row of each slot or -1, each cluster padded to a multiple of
+ * 32 slots, n_slots padded to a multiple of 128 (n_slots <= n + 32 n_labels + 128); group_label[n_slots / 32] = dense cluster id of each
+ * group of 32 slots or -1; counts[n_labels] = cluster sizes.
+ *   1. avexhip_silhouette_prepare   gathers (and for cosine normalises) the rows into the workspace, norms, finite flag;
+ *   2. avexhip_silhouette_batch     slots [row0, row0 + nb), nb <= batch: distance sums against every cluster, then a, b and
+ *                                   s = (b - a) / max(a, b) per point into samples_out[input row] (0 for a cluster of one and for 0 / 0);
+ *   3. avexhip_silhouette_finalize  out[0] = mean of samples_out in a fixed order, out[1] = 1.0 when every input value was finite.
+ * Limits: n <= 524288 (avexhip_silhouette_max_n), n_labels <= 4096 (avexhip_silhouette_max_labels).
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_SILHOUETTE_EUCLIDEAN 0
+#define AVEXHIP_SILHOUETTE_COSINE 1
+typedef struct {
+    const float* x;              /* [n, d] fp32 rows on the device (row stride ld_x); read by _prepare only */
+    int64_t ld_x;
+    int32_t n, d;
+    int32_t metric;              /* AVEXHIP_SILHOUETTE_* */
+    int32_t n_labels;            /* distinct clusters, 1 .. 4096 */
+    int32_t n_slots;             /* rows of the cluster-ordered, padded layout; a multiple of 128 */
+    int32_t batch;               /* capacity of one _batch call in slots, as given to avexhip_silhouette_workspace_bytes */
+    const int32_t* slot_src;     /* [n_slots] */
+    const int32_t* group_label;  /* [n_slots / 32] */
+    const int32_t* counts;       /* [n_labels] */
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t row0, nb;            /* _batch: the slots of this call */
+    int32_t stages;              /* _batch: 0 or 3 both; 1: the distance product and its sums only; 2: a, b, s from the sums in the workspace */
+    int32_t reserved;
+    double* samples_out;         /* [n] fp64, indexed by input row */
+} avexhip_silhouette_args;
+
+size_t avexhip_silhouette_workspace_bytes(int64_t n_slots, int d, int n_labels, int batch);
+int avexhip_silhouette_max_labels(void);   /* 4096 */
+int avexhip_silhouette_max_n(void);        /* 524288 */
+int avexhip_silhouette_prepare(const avexhip_silhouette_args* args, void* stream);
+int avexhip_silhouette_batch(const avexhip_silhouette_args* args, void* stream);
+int avexhip_silhouette_finalize(const avexhip_silhouette_args* args, double* out_dev, void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
