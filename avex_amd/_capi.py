@@ -135,6 +135,8 @@ SYMBOLS = {
     "avexhip_resample_out_length": (C.c_int64, [_P, C.c_int64]),
     "avexhip_resample_forward": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     "avexhip_pcm_to_mono_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, _P, _P]),
+    "avexhip_ingest_batch_workspace_bytes": (C.c_size_t, [_P, C.c_int, _P, C.c_int, C.c_int64]),
+    "avexhip_ingest_batch": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "avexhip_flac_open": (_P, [_P, C.c_size_t]),
     "avexhip_flac_close": (None, [_P]),
     "avexhip_flac_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), _P]),

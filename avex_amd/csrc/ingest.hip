@@ -249,3 +249,266 @@ extern "C" int avexhip_pcm_to_mono_f32(const void* raw_dev, int sample_format, i
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Batched ingest: B clips of any format / channel count / rate / length -> the padded model batch, in a fixed number of launches.
+// What the reference's Collater makes on the host (avex/data/dataset.py:256-399 on avex/data/audio_utils.py:16-73): channel mean,
+// clips with a NaN / Inf replaced by zeros, a window of the clip or zero padding up to the model length, the padding mask.
+//   ingest_mono_kernel      every item's raw samples -> mono fp32, only the input span its window (and the filter halo) reads;
+//                           float payloads are scanned whole for NaN / Inf (flag per item)
+//   ingest_resample_kernel  row b, sample j = sample start_b + j of the item's full-clip resampling (same fmaf chains as
+//                           resample_kernel / resample_interp_kernel, so the same bits), zeros behind `valid`, the mask, zero rows
+//                           for flagged items
+// ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kIngestMaxPlans = 16;
+constexpr int kIngestMonoBlocks = 64;          // blocks per item in the mono stage; each walks its item's chunks with this stride
+
+struct IngestPlanDev {
+    const float* table;
+    int orig, newr, width, taps;               // sinc plans
+    int interp, nwin, num_table, index_step;   // interpolating plans
+    double scale, time_increment, ratio;
+    float post;
+};
+struct IngestPlanTable { IngestPlanDev p[kIngestMaxPlans]; };
+
+__host__ __device__ inline int ingest_sample_bytes(int fmt) { return fmt == 8 ? 1 : fmt == 16 ? 2 : fmt == 24 ? 3 : fmt == 64 ? 8 : 4; }
+
+// [lo, hi): the mono samples of a clip of T frames that the outputs start .. start + valid - 1 of its resampling read (pl == nullptr:
+// the clip is at the target rate already).  The same integer / double arithmetic as the kernels, so host and device agree.
+__host__ __device__ inline void ingest_span(const IngestPlanDev* pl, int64_t T, int64_t start, int64_t valid, int64_t* lo, int64_t* hi) {
+    int64_t a = 0, b = 0;
+    if (valid > 0) {
+        const int64_t last = start + valid - 1;
+        if (!pl) { a = start; b = last + 1; }
+        else if (!pl->interp) {
+            a = (start / pl->newr) * pl->orig - pl->width;
+            b = (last / pl->newr) * pl->orig - pl->width + pl->taps;
+        } else {
+            const int64_t n_res = (int64_t)((double)T * pl->ratio);
+            const int64_t t1 = last < n_res - 1 ? last : n_res - 1;
+            if (t1 >= start) {
+                const int64_t wing = pl->nwin / pl->index_step + 1;      // a wing reads at most (nwin - offset) / index_step samples
+                a = (int64_t)((double)start * pl->time_increment) - wing;
+                b = (int64_t)((double)t1 * pl->time_increment) + wing + 1;
+            }
+        }
+        a = a < 0 ? 0 : a;
+        b = b > T ? T : b;
+        if (b < a) b = a;
+    }
+    *lo = a; *hi = b;
+}
+
+// one item's sample i, channels averaged: pcm_to_mono_kernel's arithmetic; `bad` collects non-finite float samples
+__device__ __forceinline__ float ingest_mono_sample(const unsigned char* __restrict__ raw, int fmt, int channels, int64_t i, bool& bad) {
+    float acc = 0.f;
+    for (int c = 0; c < channels; ++c) {
+        const int64_t e = i * channels + c;
+        float v;
+        if (fmt == 16) v = (float)((const short*)raw)[e] * (1.0f / 32768.0f);
+        else if (fmt == 32) v = (float)((const int*)raw)[e] * (1.0f / 2147483648.0f);
+        else if (fmt == 24) {
+            const unsigned char* p = raw + 3 * e;
+            int s = (int)p[0] | ((int)p[1] << 8) | ((int)(signed char)p[2] << 16);
+            v = (float)s * (1.0f / 8388608.0f);
+        } else if (fmt == 8) v = ((float)raw[e] - 128.0f) * (1.0f / 128.0f);
+        else {
+            v = fmt == 64 ? (float)((const double*)raw)[e] : ((const float*)raw)[e];
+            bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;      // exponent all ones: NaN or Inf
+        }
+        acc += v;
+    }
+    return channels > 1 ? acc / (float)channels : acc;
+}
+
+// grid (kIngestMonoBlocks, B).  Integer PCM: the span only.  Float payloads: the whole clip (the NaN / Inf test covers every sample the
+// reference's Collater would see), stores inside the span only.
+__global__ __launch_bounds__(256) void ingest_mono_kernel(const unsigned char* __restrict__ raw, const avexhip_ingest_item* __restrict__ items,
+                                                          IngestPlanTable plans, float* __restrict__ ws, int64_t ws_stride, int* __restrict__ flags) {
+    const int b = blockIdx.y;
+    const avexhip_ingest_item it = items[b];
+    int64_t lo, hi;
+    ingest_span(it.plan >= 0 ? &plans.p[it.plan] : nullptr, it.frames, it.start, it.valid, &lo, &hi);
+    const bool is_float = it.sample_format == 0 || it.sample_format == 64;
+    const int64_t first = is_float ? 0 : lo, end = is_float ? it.frames : hi;
+    const unsigned char* src = raw + it.offset;
+    float* dst = ws + (int64_t)b * ws_stride;
+    bool bad = false;
+    for (int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)kIngestMonoBlocks * 256) {
+        const float v = ingest_mono_sample(src, it.sample_format, it.channels, i, bad);
+        if (i >= lo && i < hi) dst[i - lo] = v;
+    }
+    if (bad) flags[b] = 1;                     // every writer stores the same value
+}
+
+// grid (ceil(T_out / 256), B): one workgroup = 256 consecutive samples of one output row.
+__global__ __launch_bounds__(256) void ingest_resample_kernel(const avexhip_ingest_item* __restrict__ items, IngestPlanTable plans, const float* __restrict__ ws,
+                                                              int64_t ws_stride, const int* __restrict__ flags, float* __restrict__ out, int64_t out_stride,
+                                                              unsigned char* __restrict__ mask, int64_t T_out) {
+    extern __shared__ float xs[];
+    const int b = blockIdx.y;
+    const avexhip_ingest_item it = items[b];
+    const int64_t j0 = (int64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
+    const int64_t valid = it.valid;
+    float acc = 0.f;
+    if (j0 < valid && flags[b] == 0) {                              // workgroup-uniform
+        const IngestPlanDev* pl = it.plan >= 0 ? &plans.p[it.plan] : nullptr;
+        int64_t lo, hi;
+        ingest_span(pl, it.frames, it.start, valid, &lo, &hi);
+        const float* src = ws + (int64_t)b * ws_stride - lo;        // src[k] = mono sample k of the clip, for lo <= k < hi
+        const int64_t T = it.frames;
+        if (!pl) {
+            if (j < valid) acc = src[it.start + j];
+        } else if (!pl->interp) {
+            const int orig = pl->orig, newr = pl->newr, taps = pl->taps;
+            const int64_t i0 = it.start + j0;
+            const int64_t ilast = it.start + (j0 + 255 < valid - 1 ? j0 + 255 : valid - 1);
+            const int64_t q0 = i0 / newr, q1 = ilast / newr;
+            const int64_t first = q0 * orig - pl->width;             // first input sample any of the workgroup's outputs reads
+            const int span = (int)((q1 - q0) * orig) + taps;
+            for (int s = threadIdx.x; s < span; s += 256) {
+                const int64_t k = first + s;
+                xs[s] = (k >= lo && k < hi) ? src[k] : 0.f;          // [lo, hi) is what [0, T) holds of the reads: zero outside, as resample_kernel
+            }
+            __syncthreads();
+            if (j < valid) {
+                const int64_t i = it.start + j;
+                const int64_t q = i / newr;
+                const int p = (int)(i - q * newr);
+                const float* row = pl->table + (int64_t)p * taps;
+                const float* xin = xs + (int)((q - q0) * orig);
+                for (int k = 0; k < taps; ++k) acc = __builtin_fmaf(row[k], xin[k], acc);
+            }
+        } else if (j < valid) {
+            const int64_t t = it.start + j;
+            const int64_t n_res = (int64_t)((double)T * pl->ratio);
+            if (t < n_res) {
+                const float* win = pl->table;
+                const float* delta = pl->table + pl->nwin;
+                const int nwin = pl->nwin, num_table = pl->num_table, index_step = pl->index_step;
+                const double scale = pl->scale;
+                const double time_register = (double)t * pl->time_increment;
+                const int64_t n = (int64_t)time_register;
+                double frac = scale * (time_register - (double)n);
+                double index_frac = frac * num_table;
+                int offset = (int)index_frac;
+                float eta = (float)(index_frac - offset);
+                int64_t i_max = (nwin - offset) / index_step;
+                i_max = i_max < n + 1 ? i_max : n + 1;
+                for (int64_t i = 0; i < i_max; ++i) {
+                    const int k = offset + (int)i * index_step;
+                    acc = __builtin_fmaf(__builtin_fmaf(eta, delta[k], win[k]), src[n - i], acc);
+                }
+                frac = scale - frac;
+                index_frac = frac * num_table;
+                offset = (int)index_frac;
+                eta = (float)(index_frac - offset);
+                int64_t k_max = (nwin - offset) / index_step;
+                k_max = k_max < T - n - 1 ? k_max : T - n - 1;
+                for (int64_t k = 0; k < k_max; ++k) {
+                    const int q = offset + (int)k * index_step;
+                    acc = __builtin_fmaf(__builtin_fmaf(eta, delta[q], win[q]), src[n + k + 1], acc);
+                }
+            }
+            acc = acc * pl->post;
+        }
+    }
+    if (j < T_out) {
+        out[(int64_t)b * out_stride + j] = acc;                      // acc is still 0 behind `valid` and in flagged rows
+        mask[(int64_t)b * T_out + j] = j >= valid ? 1 : 0;
+    }
+}
+
+// everything avexhip_ingest_batch_workspace_bytes / avexhip_ingest_batch check, and the layout they share
+struct IngestLayout { IngestPlanTable table; int64_t ws_stride; size_t flag_bytes, total_bytes, lds_bytes; };
+
+int ingest_layout(const avexhip_ingest_item* items, int B, const avexhip_resample_plan* const* plans, int n_plans, int64_t T_out, size_t raw_bytes,
+                  bool check_raw, IngestLayout* L) {
+    AVX_REQUIRE(items, "ingest_batch: null item list");
+    AVX_REQUIRE(B >= 1 && B <= 65535, "ingest_batch: B=%d outside 1..65535", B);
+    AVX_REQUIRE(T_out >= 1 && T_out <= ((int64_t)1 << 31) - 256, "ingest_batch: T_out=%lld", (long long)T_out);
+    AVX_REQUIRE(n_plans >= 0 && n_plans <= kIngestMaxPlans && (n_plans == 0 || plans), "ingest_batch: %d resample plans (at most %d per batch)", n_plans,
+                kIngestMaxPlans);
+    memset(&L->table, 0, sizeof(L->table));
+    size_t lds = 0;
+    for (int i = 0; i < n_plans; ++i) {
+        const avexhip_resample_plan* p = plans[i];
+        AVX_REQUIRE(p && p->table, "ingest_batch: plan %d is null", i);
+        IngestPlanDev& d = L->table.p[i];
+        d.table = p->table; d.orig = p->orig; d.newr = p->newr; d.width = p->width; d.taps = p->taps;
+        d.interp = p->interp ? 1 : 0; d.nwin = p->nwin; d.num_table = p->num_table; d.index_step = p->index_step;
+        d.scale = p->scale; d.time_increment = 1.0 / p->ratio; d.ratio = p->ratio; d.post = p->post;
+        if (!p->interp) {
+            const size_t need = sizeof(float) * (size_t)((256 / p->newr + 2) * p->orig + p->taps);
+            lds = need > lds ? need : lds;
+        }
+    }
+    int64_t stride = 1;
+    for (int b = 0; b < B; ++b) {
+        const avexhip_ingest_item& it = items[b];
+        const int f = it.sample_format;
+        AVX_REQUIRE(f == 0 || f == 8 || f == 16 || f == 24 || f == 32 || f == 64, "ingest_batch: item %d: sample_format %d", b, f);
+        AVX_REQUIRE(it.channels > 0 && it.channels <= 64 && it.frames > 0 && it.frames <= ((int64_t)1 << 40), "ingest_batch: item %d: channels=%d frames=%lld", b,
+                    it.channels, (long long)it.frames);
+        AVX_REQUIRE(it.plan >= -1 && it.plan < n_plans, "ingest_batch: item %d: plan index %d outside -1..%d", b, it.plan, n_plans - 1);
+        AVX_REQUIRE(it.valid >= 0 && it.valid <= T_out, "ingest_batch: item %d: valid=%lld outside 0..T_out=%lld", b, (long long)it.valid, (long long)T_out);
+        const int64_t n_out = it.plan < 0 ? it.frames : avexhip_resample_out_length(plans[it.plan], it.frames);
+        AVX_REQUIRE(it.start >= 0 && it.start <= n_out - it.valid, "ingest_batch: item %d: window %lld + %lld leaves the clip's %lld resampled samples", b,
+                    (long long)it.start, (long long)it.valid, (long long)n_out);
+        if (check_raw) {
+            const uint64_t bytes = (uint64_t)it.frames * (uint64_t)it.channels * (uint64_t)ingest_sample_bytes(f);
+            AVX_REQUIRE(it.offset >= 0 && it.offset % 8 == 0, "ingest_batch: item %d: byte offset %lld is not a non-negative multiple of 8", b, (long long)it.offset);
+            AVX_REQUIRE((uint64_t)it.offset <= raw_bytes && bytes <= raw_bytes - (uint64_t)it.offset, "ingest_batch: item %d: %llu bytes at offset %lld leave the %llu-byte buffer",
+                        b, (unsigned long long)bytes, (long long)it.offset, (unsigned long long)raw_bytes);
+        }
+        int64_t lo, hi;
+        ingest_span(it.plan >= 0 ? &L->table.p[it.plan] : nullptr, it.frames, it.start, it.valid, &lo, &hi);
+        stride = hi - lo > stride ? hi - lo : stride;
+    }
+    L->ws_stride = (stride + 3) & ~(int64_t)3;
+    L->flag_bytes = ((size_t)B * sizeof(int) + 255) & ~(size_t)255;
+    L->total_bytes = L->flag_bytes + (size_t)B * (size_t)L->ws_stride * sizeof(float);
+    L->lds_bytes = lds;
+    return AVEXHIP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t avexhip_ingest_batch_workspace_bytes(const avexhip_ingest_item* items_host, int B, const avexhip_resample_plan* const* plans, int n_plans,
+                                                       int64_t T_out) {
+    IngestLayout L;
+    if (ingest_layout(items_host, B, plans, n_plans, T_out, 0, false, &L) != AVEXHIP_OK) return 0;
+    return L.total_bytes;
+}
+
+extern "C" int avexhip_ingest_batch(const void* raw_dev, size_t raw_bytes, const avexhip_ingest_item* items_host, const avexhip_ingest_item* items_dev, int B,
+                                    const avexhip_resample_plan* const* plans, int n_plans, int64_t T_out, float* wav_dev, int64_t wav_stride,
+                                    uint8_t* mask_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    AVX_REQUIRE(raw_dev && items_dev && wav_dev && mask_dev && workspace_dev, "ingest_batch: null argument");
+    AVX_REQUIRE(((uintptr_t)raw_dev & 7) == 0 && ((uintptr_t)items_dev & 7) == 0 && ((uintptr_t)workspace_dev & 15) == 0,
+                "ingest_batch: raw_dev / items_dev must be 8-byte aligned, workspace_dev 16-byte aligned");
+    IngestLayout L;
+    const int rc = ingest_layout(items_host, B, plans, n_plans, T_out, raw_bytes, true, &L);
+    if (rc != AVEXHIP_OK) return rc;
+    if (wav_stride <= 0) wav_stride = T_out;
+    AVX_REQUIRE(wav_stride >= T_out, "ingest_batch: wav_stride %lld < T_out %lld", (long long)wav_stride, (long long)T_out);
+    if (workspace_bytes < L.total_bytes) {
+        avexhip_set_error("ingest_batch: workspace of %llu bytes, %llu needed (avexhip_ingest_batch_workspace_bytes)", (unsigned long long)workspace_bytes,
+                          (unsigned long long)L.total_bytes);
+        return AVEXHIP_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* flags = (int*)workspace_dev;
+    float* ws = (float*)((char*)workspace_dev + L.flag_bytes);
+    AVX_HIP_CHECK(hipMemsetAsync(flags, 0, L.flag_bytes, s));
+    hipLaunchKernelGGL(ingest_mono_kernel, dim3(kIngestMonoBlocks, B), dim3(256), 0, s, (const unsigned char*)raw_dev, items_dev, L.table, ws, L.ws_stride, flags);
+    AVX_LAUNCH_CHECK();
+    AVX_ENSURE_LDS(ingest_resample_kernel, 160 * 1024);
+    hipLaunchKernelGGL(ingest_resample_kernel, dim3((unsigned)((T_out + 255) / 256), B), dim3(256), L.lds_bytes, s, items_dev, L.table, ws, L.ws_stride, flags,
+                       wav_dev, wav_stride, mask_dev, T_out);
+    AVX_LAUNCH_CHECK();
+    return AVEXHIP_OK;
+}

@@ -14,11 +14,17 @@ stream carries); lossy codecs (MP3, OGG Vorbis) need a codec library that neithe
 those with the reference's reader and hand the array to :func:`to_device_mono`.  The resampler is torchaudio's algorithm (Hann-windowed sinc); librosa's ``kaiser_best``
 filter is a different low-pass design and is NOT reproduced sample for sample (PARITY UNPINNED for both: neither library is
 installed; checker = oracle/ingest_oracle.py).
+
+:func:`load_batch` / :class:`Collater` turn a whole batch of files into the padded ``[B, T]`` batch and padding mask of the reference's
+``Collater`` (avex/data/dataset.py:256-399) in one copy and a fixed number of launches (``avexhip_ingest_batch``), each row bit-identical
+to :func:`load_audio` followed by a slice / pad.
 """
 from __future__ import annotations
 
+import os
 import struct
-from typing import Dict, Optional, Tuple, Union
+import random
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -26,7 +32,7 @@ import torch
 from . import _capi
 from ._capi import AvexHipError, check, lib
 
-__all__ = ["parse_wav", "FlacStream", "Resampler", "to_device_mono", "load_audio"]
+__all__ = ["parse_wav", "FlacStream", "Resampler", "to_device_mono", "load_audio", "load_batch", "Collater"]
 
 
 def parse_wav(path_or_bytes: Union[str, bytes]) -> Tuple[np.ndarray, int, int, int]:
@@ -201,3 +207,259 @@ def load_audio(path_or_bytes: Union[str, bytes], target_sr: Optional[int] = 1600
             _RESAMPLERS[key] = Resampler(sr, int(target_sr))
         x, sr = _RESAMPLERS[key](x), int(target_sr)
     return x, sr
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Batched ingest: files -> the padded batch a model takes (avexhip_ingest_batch), what the reference's Collater builds on the host
+# (avex/data/dataset.py:256-399 on avex/data/audio_utils.py:16-73).  The host parses containers and chooses the windows; every sample is
+# decoded, averaged, resampled, cropped and padded on the device, from one packed buffer that crosses PCIe in one copy.
+# ------------------------------------------------------------------------------------------------------------------------
+WINDOW_SELECTIONS = ("random", "center", "start")
+# avexhip_ingest_item, field for field
+ITEM_DTYPE = np.dtype([("offset", "<i8"), ("frames", "<i8"), ("start", "<i8"), ("valid", "<i4"), ("sample_format", "<i4"), ("channels", "<i4"),
+                       ("plan", "<i4")])
+_SAMPLE_BYTES = {8: 1, 16: 2, 24: 3, 32: 4, 0: 4, 64: 8}
+
+
+class _Entry:
+    """One source after its container was parsed: the payload as the file holds it (or the FLAC stream that will be decoded into the
+    packed buffer), its rate, layout and length."""
+    __slots__ = ("payload", "flac", "sr", "channels", "fmt", "frames")
+
+    def __init__(self, payload, flac, sr, channels, fmt, frames):
+        self.payload, self.flac, self.sr, self.channels, self.fmt, self.frames = payload, flac, int(sr), int(channels), int(fmt), int(frames)
+        if self.frames <= 0:
+            raise ValueError("no audio frames")
+
+    @property
+    def nbytes(self) -> int:
+        return self.frames * self.channels * _SAMPLE_BYTES[self.fmt]
+
+
+def _open_source(src: Any, array_sr: int) -> _Entry:
+    """A path or bytes (WAV / FLAC), or a ``(T,)`` / ``(C, T)`` float array or tensor taken to be at ``array_sr``."""
+    if isinstance(src, (str, os.PathLike, bytes, bytearray)):
+        data = bytes(src) if isinstance(src, (bytes, bytearray)) else open(src, "rb").read()
+        if data[:4] == b"fLaC":
+            fl = FlacStream(data)
+            return _Entry(None, fl, fl.sample_rate, fl.channels, 32, fl.total_samples)      # decoded left-justified: 32-bit full scale
+        raw, sr, ch, code = parse_wav(data)
+        return _Entry(raw, None, sr, ch, code, raw.size // (ch * _SAMPLE_BYTES[code]))
+    a = src.detach().cpu().numpy() if isinstance(src, torch.Tensor) else np.asarray(src)
+    if a.ndim not in (1, 2):
+        raise ValueError(f"audio array of shape {a.shape}: (T,) or (C, T) expected")
+    a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    ch = 1 if a.ndim == 1 else a.shape[0]
+    inter = np.ascontiguousarray(a if a.ndim == 1 else a.T)                                  # [frames][channels], as a file holds them
+    return _Entry(inter.reshape(-1).view(np.uint8), None, array_sr, ch, 64 if a.dtype == np.float64 else 0, a.shape[-1])
+
+
+def _crop_start(length: int, target: int, selection: str) -> int:
+    """Where ``pad_or_window`` starts its window when it crops (audio_utils.py:52-62); ``random`` draws from torch's global CPU generator."""
+    if selection == "random":
+        return int(torch.randint(0, length - target + 1, ()).item())
+    if selection == "center":
+        return (length - target) // 2
+    return 0
+
+
+def plan_windows(lengths: Sequence[int], target_len: Optional[int] = None, window_selection: str = "start", dataset_max_len: Optional[int] = None,
+                 starts: Optional[Sequence[int]] = None) -> Tuple[List[int], List[int], int]:
+    """``(starts, valid lengths, T)`` of a batch whose clips hold ``lengths`` samples at the target rate.  Item by item, as the
+    reference's Collater walks its batch: a clip longer than ``dataset_max_len`` is cropped to it first, then cropped or padded to
+    ``target_len`` (``None``: the longest clip after the first step); a random start is drawn only by a step that crops, the dataset
+    step first.  ``starts`` replaces the choice (the window then begins there and ends where the clip or a limit ends)."""
+    if window_selection not in WINDOW_SELECTIONS:
+        raise ValueError(f"Unknown window selection: {window_selection!r} (one of {WINDOW_SELECTIONS})")
+    if len(lengths) == 0:
+        raise ValueError("empty batch")
+    if target_len is not None and target_len <= 0 or dataset_max_len is not None and dataset_max_len <= 0:
+        raise ValueError(f"target_len={target_len}, dataset_max_len={dataset_max_len}: positive lengths expected")
+    if starts is not None and len(starts) != len(lengths):
+        raise ValueError(f"{len(starts)} starts for {len(lengths)} items")
+    limit = [int(n) if dataset_max_len is None else min(int(n), int(dataset_max_len)) for n in lengths]
+    T = int(target_len) if target_len is not None else max(limit)
+    out_s, out_v = [], []
+    for i, n in enumerate(lengths):
+        n = int(n)
+        if starts is not None:
+            s0 = int(starts[i])
+            if not 0 <= s0 < n:
+                raise ValueError(f"item {i}: start {s0} outside its {n} samples")
+            out_s.append(s0)
+            out_v.append(min(T, limit[i], n - s0))
+            continue
+        s0 = _crop_start(n, limit[i], window_selection) if n > limit[i] else 0
+        if limit[i] > T:
+            s0 += _crop_start(limit[i], T, window_selection)
+        out_s.append(s0)
+        out_v.append(min(limit[i], T))
+    return out_s, out_v, T
+
+
+def pack_batch(entries: Sequence[_Entry], starts: Sequence[int], valids: Sequence[int], plan_index: Sequence[int]) -> Tuple[np.ndarray, int, int]:
+    """``(descriptors, bytes to copy, bytes in all)`` of the packed buffer: the descriptors at its head, then every host payload, each at
+    an 8-byte aligned offset -- that much is copied -- then the space the FLAC streams are decoded into on the device."""
+    items = np.zeros(len(entries), dtype=ITEM_DTYPE)
+    pos = (items.nbytes + 7) & ~7
+    for flac_pass in (False, True):
+        if flac_pass:
+            copy_bytes = pos
+        for i, e in enumerate(entries):
+            if (e.flac is not None) != flac_pass:
+                continue
+            items[i] = (pos, e.frames, starts[i], valids[i], e.fmt, e.channels, plan_index[i])
+            pos = (pos + e.nbytes + 7) & ~7
+    return items, copy_bytes, pos
+
+
+_BATCH_RESAMPLERS: Dict[Tuple[int, int, Optional[str]], Resampler] = {}
+_BATCH_BUFFERS: Dict[int, Dict[str, Any]] = {}
+
+
+def _grown(bufs: Dict[str, Any], name: str, nbytes: int, **kw) -> torch.Tensor:
+    t = bufs.get(name)
+    if t is None or t.numel() < nbytes:
+        t = bufs[name] = torch.empty((max(nbytes, 1) * 5 // 4 + 255) & ~255, dtype=torch.uint8, **kw)
+    return t
+
+
+def _ingest(entries: Sequence[_Entry], target_sr: int, target_len: Optional[int], window_selection: str, starts, dataset_max_len: Optional[int],
+            res_type: Optional[str], device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    import ctypes as C
+    if window_selection not in WINDOW_SELECTIONS:
+        raise ValueError(f"Unknown window selection: {window_selection!r} (one of {WINDOW_SELECTIONS})")
+    if len(entries) == 0:
+        raise ValueError("empty batch")
+    _capi.require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        plans: List[Resampler] = []
+        plan_index, lengths = [], []
+        for e in entries:
+            if e.sr == int(target_sr):
+                plan_index.append(-1); lengths.append(e.frames)
+                continue
+            key = (e.sr, int(target_sr), res_type)
+            if key not in _BATCH_RESAMPLERS:
+                _BATCH_RESAMPLERS[key] = Resampler(e.sr, int(target_sr), res_type=res_type)
+            rs = _BATCH_RESAMPLERS[key]
+            if rs not in plans:
+                plans.append(rs)
+            plan_index.append(plans.index(rs)); lengths.append(rs.out_length(e.frames))
+        win_s, win_v, T = plan_windows(lengths, target_len, window_selection, dataset_max_len, starts)
+        items, copy_bytes, total_bytes = pack_batch(entries, win_s, win_v, plan_index)
+        B = len(entries)
+        handles = (C.c_void_p * max(len(plans), 1))(*[p._h for p in plans])
+        ws_bytes = int(lib().avexhip_ingest_batch_workspace_bytes(items.ctypes.data, B, handles, len(plans), T))
+        if ws_bytes == 0:
+            raise ValueError(f"ingest_batch: {_capi.last_error()}")
+        bufs = _BATCH_BUFFERS.setdefault(dev.index, {})
+        if "copied" in bufs:
+            bufs["copied"].synchronize()                  # the last batch's copy still reads the staging buffer
+        host = _grown(bufs, "host", copy_bytes, pin_memory=True)
+        raw = _grown(bufs, "raw", total_bytes, device=dev)
+        ws = _grown(bufs, "ws", ws_bytes, device=dev)
+        hv = host.numpy()
+        hv[:items.nbytes] = items.view(np.uint8).reshape(-1)
+        for i, e in enumerate(entries):
+            if e.flac is None:
+                off = int(items["offset"][i])
+                hv[off:off + e.nbytes] = e.payload[:e.nbytes]
+        stream = torch.cuda.current_stream().cuda_stream
+        raw[:copy_bytes].copy_(host[:copy_bytes], non_blocking=True)
+        bufs.setdefault("copied", torch.cuda.Event()).record()
+        for i, e in enumerate(entries):
+            if e.flac is not None:
+                check(lib().avexhip_flac_decode_i32(e.flac._h, raw.data_ptr() + int(items["offset"][i]), 1, stream), "flac_decode_i32")
+                e.flac.close()
+        wav = torch.empty((B, T), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, T), dtype=torch.bool, device=dev)
+        check(lib().avexhip_ingest_batch(raw.data_ptr(), total_bytes, items.ctypes.data, raw.data_ptr(), B, handles, len(plans), T, wav.data_ptr(), T,
+                                         mask.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ingest_batch")
+    return wav, mask, torch.tensor(win_v, dtype=torch.int64)
+
+
+def load_batch(sources: Sequence[Any], target_sr: int = 16000, target_len: Optional[int] = None, window_selection: str = "start",
+               starts: Optional[Sequence[int]] = None, dataset_max_len: Optional[int] = None, res_type: Optional[str] = None,
+               device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Files -> ``(wav [B, T] float32, padding_mask [B, T] bool (True = padding), lengths [B] int64)``; wav and mask on the device, the
+    lengths (kept samples per row) on the host, where the windows are chosen.  ``sources`` mixes paths and bytes (WAV or FLAC) with
+    ``(T,)`` / ``(C, T)`` float arrays or tensors taken to be at ``target_sr``.  Each row is the window ``[start, start + T)`` of the
+    clip's mono resampling -- the bits :func:`load_audio` followed by a slice gives -- zero-padded behind its end; a float clip that
+    holds a NaN or an Inf becomes a zero row.  ``target_len=None`` pads to the longest item; ``dataset_max_len`` crops longer clips
+    first; windows are chosen by ``window_selection`` (``random`` | ``center`` | ``start``) or given in ``starts``; ``res_type`` as
+    :class:`Resampler` takes it.  One host-to-device copy, a memset and two launches per batch (plus one decode per FLAC stream); the
+staging, packed and workspace buffers are kept between calls and ordered by the current stream, so call it from one stream per device."""
+    if len(sources) == 0:
+        raise ValueError("empty batch")
+    return _ingest([_open_source(s, int(target_sr)) for s in sources], target_sr, target_len, window_selection, starts, dataset_max_len, res_type, device)
+
+
+def collate_labels(labels: Sequence[Any], num_labels: int) -> torch.Tensor:
+    """The label tensor of the reference's Collater (dataset.py:341-373): all-int labels -> one-hot rows, or a ``[B, 1]`` zero tensor
+    when ``num_labels == 0``; otherwise lists of class indices -> multi-hot rows, indices >= num_labels dropped."""
+    if all(isinstance(lbl, (int, np.integer)) for lbl in labels):
+        if num_labels > 0:
+            return torch.nn.functional.one_hot(torch.tensor([int(v) for v in labels], dtype=torch.long), num_classes=num_labels).float()
+        return torch.zeros((len(labels), 1), dtype=torch.float32)
+    rows = []
+    for lbl in labels:
+        if num_labels <= 0:
+            rows.append(torch.zeros(1, dtype=torch.float32))
+            continue
+        row = torch.zeros(num_labels, dtype=torch.float32)
+        idx = lbl.clone().detach().long() if isinstance(lbl, torch.Tensor) else torch.tensor(lbl, dtype=torch.long)
+        idx = idx[idx < num_labels]
+        if len(idx) > 0:
+            row[idx] = 1.0
+        rows.append(row)
+    return torch.stack(rows)
+
+
+class Collater:
+    """The reference's ``Collater`` (dataset.py:256-399) with the audio built on the device: ``__call__(batch)`` returns ``raw_wav``
+    ``[B, T]`` float32 and ``padding_mask`` ``[B, T]`` bool (True = padding) on ``device``, ``label`` (host, as the reference) and
+    ``text_label``.  An item's ``"audio"`` / ``"raw_wav"`` is an array at ``sr`` as in the reference, or a path / bytes of a WAV or
+    FLAC file, resampled to ``sr``.  Window starts are drawn on the host exactly as the reference draws them, so under
+    ``torch.manual_seed`` the windows are the reference's.  It touches the GPU: use it in the main process (``num_workers=0``).
+    Deviation: a file is tested for NaN / Inf as decoded, before resampling; for arrays given at ``sr`` that is the reference's test."""
+
+    def __init__(self, audio_max_length_seconds: int, sr: int, window_selection: str = "random", preprocessor: Optional[str] = None,
+                 device: str = "cuda", batch_aug_processor: Any = None, num_labels: int = 0,
+                 dataset_audio_max_length_seconds: Optional[int] = None) -> None:
+        if batch_aug_processor is not None:
+            raise NotImplementedError("batch_aug_processor (mixup) is a training-time augmentation; this Collater builds inference batches")
+        if window_selection not in WINDOW_SELECTIONS:
+            raise ValueError(f"Unknown window selection: {window_selection!r} (one of {WINDOW_SELECTIONS})")
+        self.audio_max_length_seconds = audio_max_length_seconds
+        self.dataset_audio_max_length_seconds = dataset_audio_max_length_seconds
+        self.window_selection = window_selection
+        self.preprocessor = preprocessor
+        self.sr = sr
+        self.device = device
+        self.batch_aug_processor = None
+        self.num_labels = num_labels
+
+    def windows(self, lengths: Sequence[int]) -> Tuple[List[int], List[int], int]:
+        """``plan_windows`` with this collater's limits (host only)."""
+        limit = None if self.dataset_audio_max_length_seconds is None else self.dataset_audio_max_length_seconds * self.sr
+        return plan_windows(lengths, self.audio_max_length_seconds * self.sr, self.window_selection, limit)
+
+    def __call__(self, batch: Sequence[Dict[str, Any]]) -> Dict[str, Any]:
+        if len(batch) == 0:
+            raise ValueError("empty batch")
+        entries, labels, text_labels = [], [], []
+        for item in batch:
+            entries.append(_open_source(item["audio" if "audio" in item else "raw_wav"], int(self.sr)))
+            labels.append(item["label"] if "label" in item else 0)
+            if "text_label" in item:
+                txt = item["text_label"]
+                if isinstance(txt, list) and len(txt) > 0:
+                    txt = random.choice(txt)
+                text_labels.append(txt)
+        limit = None if self.dataset_audio_max_length_seconds is None else self.dataset_audio_max_length_seconds * self.sr
+        wav, mask, _ = _ingest(entries, int(self.sr), self.audio_max_length_seconds * self.sr, self.window_selection, None, limit, None, self.device)
+        return {"raw_wav": wav, "padding_mask": mask, "label": collate_labels(labels, self.num_labels), "text_label": text_labels}

@@ -7,7 +7,7 @@ EVALUATION forward -- layer mixing (``_sum``), the 2-D / 3-D reshaping rules and
 kernels (``avexhip_layer_mix``, ``avexhip_dense_f32``, ``avexhip_mha_f32``, ``avexhip_layernorm``, ``avexhip_mean_pool``) with the
 reference's constructor arguments and ``state_dict`` key names, so a probe trained with the reference loads with
 ``load_state_dict`` and scores batches right behind the encoder.  Training (``.train()``) is refused loudly; embedding projectors
-(taps of different widths, base_probes.py:262-289) are not built: every model on this path has equal-width taps.
+(taps of different widths, base_probes.py:262-289) are built (``_analyze_and_create_projectors``, ``_project``).
 """
 from __future__ import annotations
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 12
+#define AVEXHIP_ABI_VERSION 13
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -155,6 +155,39 @@ int64_t avexhip_resample_out_length(const avexhip_resample_plan* plan, int64_t T
 int avexhip_resample_forward(const avexhip_resample_plan* plan, const float* x_dev, int B, int64_t T, int64_t x_stride, float* out_dev,
                              int64_t out_stride, void* stream);
 int avexhip_pcm_to_mono_f32(const void* raw_dev, int sample_format, int channels, int64_t frames, float* out_dev, void* stream);
+
+/* Batched ingest (ABI 13): B clips as their files hold them -> the padded batch a model takes, what the reference's Collater builds on the
+ * host (avex/data/dataset.py:256-399 on avex/data/audio_utils.py:16-73: channel mean, clips holding a NaN / Inf replaced by zeros, a window
+ * of the clip or zero padding up to the model length, padding_mask with True = padding).  A memset and two launches whatever B is.
+ *   raw_dev      every item's payload in ONE device buffer of raw_bytes bytes (one copy from one host staging buffer), 8-byte aligned;
+ *                a FLAC item is avexhip_flac_decode_i32(left_justify = 1) written at its offset, sample_format 32
+ *   items_host   the B descriptors, read here for the argument checks and the launch shapes
+ *   items_dev    the same descriptors in device memory, 8-byte aligned (they may ride at the head of raw_dev: no second copy); the kernels
+ *                read these, so they must equal items_host
+ *   plans        the resample plans the descriptors index (sinc or interpolating, at most 16 per batch)
+ *   wav_dev      [B, T_out] fp32, row stride wav_stride (<= 0: T_out): sample j of row b is sample start_b + j of the clip's full
+ *                resampling -- the same fmaf chains as avexhip_resample_forward, bit for bit -- for j < valid_b, and 0 behind it;
+ *                a row whose float32 / float64 payload holds a NaN or an Inf anywhere in the clip is all zero
+ *   mask_dev     [B, T_out] bytes, 1 where j >= valid_b
+ *   workspace    avexhip_ingest_batch_workspace_bytes(...) bytes, 16-byte aligned: the non-finite flags and, per item, the mono samples its
+ *                window and the filter halo read (integer PCM is decoded for that span only; float payloads are scanned whole)
+ * Refused with AVEXHIP_ERR_INVALID before anything is launched: B outside 1..65535, a payload that leaves the buffer or is misaligned, a plan
+ * index outside -1..n_plans-1, valid > T_out, a window that leaves the resampled clip; AVEXHIP_ERR_WORKSPACE for a workspace too small.
+ * Deviation: the reference tests the resampled clip for NaN / Inf, this tests the decoded input (the same for clips at the target rate). */
+typedef struct {
+    int64_t offset;          /* of the payload in raw_dev, bytes, a multiple of 8 */
+    int64_t frames;          /* interleaved [frames][channels] */
+    int64_t start;           /* first kept sample, counted at the target rate */
+    int32_t valid;           /* kept samples, <= T_out */
+    int32_t sample_format;   /* as avexhip_pcm_to_mono_f32 takes it */
+    int32_t channels;
+    int32_t plan;            /* index into plans, or -1: already at the target rate */
+} avexhip_ingest_item;
+size_t avexhip_ingest_batch_workspace_bytes(const avexhip_ingest_item* items_host, int B, const avexhip_resample_plan* const* plans, int n_plans,
+                                            int64_t T_out);      /* 0 (avexhip_last_error) for arguments avexhip_ingest_batch would refuse */
+int avexhip_ingest_batch(const void* raw_dev, size_t raw_bytes, const avexhip_ingest_item* items_host, const avexhip_ingest_item* items_dev, int B,
+                         const avexhip_resample_plan* const* plans, int n_plans, int64_t T_out, float* wav_dev, int64_t wav_stride,
+                         uint8_t* mask_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* FLAC decode (the reference reads its .flac samples through torchaudio.load / soundfile: augmentations.py:258-262,
  * tests/samples/animalspeak2/16khz).  avexhip_flac_open parses a whole stream held in host memory -- metadata, frame and
