@@ -25,6 +25,62 @@ def load_golden(golden_dir):
     return z, json.loads(str(z["meta"]))
 
 
+def load_wide(golden_dir):
+    """tests/golden/metrics_wide.npz (tests/golden/make_metrics_wide_goldens.py): the clustering cases under meta["cases"] and
+    "<case>/km_labels", "<case>/seeds0" as in clustering.npz, the silhouette cases under meta["silhouette"] and "sil/<case>/<metric>"."""
+    z = np.load(os.path.join(golden_dir, "metrics_wide.npz"))
+    return z, json.loads(str(z["meta"]))
+
+
+def separated(seed, k, per, d, sep=4.0):
+    """k well-separated classes of `per` points each, shuffled: rows = sep * N(0, 1) class means + N(0, 1), fp32.  With a few points per
+    class and as many centres as classes a point's nearest centre is nearer than the second by a margin, not by luck."""
+    rng = np.random.default_rng(seed)
+    lab = rng.permutation(np.repeat(np.arange(k), per))
+    means = sep * rng.standard_normal((k, d))
+    return (means[lab] + rng.standard_normal((k * per, d))).astype(np.float32), lab.astype(np.int64)
+
+
+def duplicate_init(x, k, copies, seed):
+    """[k, D] explicit init: k - copies + 1 distinct rows of x, the first of them `copies` times (at shuffled positions): after the first
+    assign copies - 1 clusters are empty, the first copy wins every tie."""
+    rng = np.random.default_rng(seed)
+    rows = rng.choice(x.shape[0], size=k - copies + 1, replace=False)
+    pick = rng.permutation(np.concatenate([np.full(copies, rows[0]), rows[1:]]))
+    return x[pick].copy()
+
+
+SCORES_TABLE = {"seed": 11, "n": 20000, "na": 300, "nb": 350}
+
+
+def label_pair(seed, n, na, nb):
+    """Two label vectors whose contingency table has about na x nb occupied classes: b follows a on 60 % of the points, the rest is uniform."""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, na, size=n)
+    b = np.where(rng.random(n) < 0.6, (a * 13 + 5) % nb, rng.integers(0, nb, size=n))
+    return a.astype(np.int64), b.astype(np.int64)
+
+
+def assign_margin(x, init, iters, tol=1e-4):
+    """The smallest over the first `iters` assigns of Lloyd's algorithm from `init` (the restatement's centres, distances in fp64) and
+    over the points of (second nearest - nearest squared distance) / nearest, bit-identical centres counted once; inf where the nearest is 0."""
+    xc, mean, _ = prepare(x, tol)
+    xnorm = np.einsum("ij,ij->i", xc, xc).astype(np.float32)
+    centres = (np.asarray(init, dtype=np.float32) - mean).astype(np.float32)
+    worst = np.inf
+    for _ in range(iters):
+        c64 = np.unique(centres, axis=0).astype(np.float64)
+        x64 = xc.astype(np.float64)
+        d2 = np.maximum((x64 ** 2).sum(axis=1)[:, None] - 2.0 * x64 @ c64.T + (c64 ** 2).sum(axis=1)[None, :], 0.0)
+        d2.sort(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(d2[:, 0] > 0.0, (d2[:, 1] - d2[:, 0]) / d2[:, 0], np.inf)
+        worst = min(worst, float(ratio.min()))
+        lab, part = assign(xc, centres)
+        centres, _ = update(xc, xnorm, centres, lab, part)
+    return worst
+
+
 def clustered(seed, n, d, classes, sep):
     """The generator of the large golden inputs: rows = sep * N(0, 1) class means + unit normal noise, fp32."""
     rng = np.random.default_rng(seed)

@@ -52,8 +52,9 @@ def u2_row(scores, rel):
     return int(lo.sum() + hi.sum()), int(pos.size), int(neg.size)
 
 
-def stats_from_sim(sim, rel, self_set, k):
-    """The per-query integers from a similarity matrix: what avex_amd.retrieval.retrieval_stats returns."""
+def stats_from_sim(sim, rel, self_set, k, row0=0):
+    """The per-query integers from a similarity matrix: what avex_amd.retrieval.retrieval_stats returns.  `row0`: the rows are queries
+    row0 .. row0 + nq - 1 of a self-set (the column a row leaves out is row0 + its index)."""
     nq, nd = sim.shape
     k = min(k, nd - 1 if self_set else nd)
     u2 = np.zeros(nq, dtype=np.int64)
@@ -62,7 +63,7 @@ def stats_from_sim(sim, rel, self_set, k):
     topk = np.zeros((nq, k), dtype=np.int64)
     cols = np.arange(nd)
     for i in range(nq):
-        keep = cols != i if self_set else np.ones(nd, dtype=bool)
+        keep = cols != row0 + i if self_set else np.ones(nd, dtype=bool)
         s, r = sim[i][keep] + 0.0, rel[i][keep]
         u2[i], n_pos[i], n_neg[i] = u2_row(s, r)
         valid_prec[i] = rel[i].sum() > 1 if self_set else n_pos[i] > 0
@@ -87,6 +88,37 @@ def self_stats(x, labels, k=1):
 
 def cross_stats(q, q_labels, d, d_labels, k=1):
     return stats_from_sim(np.matmul(normed(np.asarray(q)), normed(np.asarray(d)).T), relevance_cross(q_labels, d_labels), False, k)
+
+
+def chunked_case(n0=None, n_db=40001, d=40, per_class=10, seed=7):
+    """Cross-set inputs that drive the rank kernel through several sorted chunks (more than 16 384 keys on the smaller side of a query):
+    a database of n_db rows made of n_db // 4 distinct rows, each four times at shuffled positions (equal similarities in different
+    chunks) plus one more distinct row; class 0 on n0 rows (None: 48 %), class 2 on 30 rows, class 1 on the rest, class 3 on none; the
+    labels do not depend on the rows, so copies of a row sit on both sides of a query.  per_class queries of each of the classes 0 .. 3.
+    -> q [4 per_class, d] fp32, q_ids, db [n_db, d] fp32, db_ids (int64)."""
+    rng = np.random.default_rng(seed)
+    base = rng.standard_normal((n_db // 4 + 1, d)).astype(np.float32)
+    src = np.concatenate([np.repeat(np.arange(n_db // 4), 4), np.arange(n_db // 4, n_db // 4 + n_db % 4 + (n_db % 4 == 0))])[:n_db]
+    db = base[rng.permutation(src)]
+    n0 = int(round(0.48 * n_db)) if n0 is None else n0
+    ids = np.ones(n_db, dtype=np.int64)
+    where = rng.permutation(n_db)
+    ids[where[:n0]] = 0
+    ids[where[n0:n0 + 30]] = 2
+    q_ids = np.repeat(np.arange(4, dtype=np.int64), per_class)
+    centre = 0.5 * rng.standard_normal((4, d))                                # queries lean towards nothing in the database in particular
+    q = (centre[q_ids] + rng.standard_normal((q_ids.size, d))).astype(np.float32)
+    q[::3] = db[rng.integers(0, n_db, size=q[::3].shape[0])]                  # every third query IS a database row: similarity 1 with its four copies
+    return q, q_ids, db, ids
+
+
+def multihot_of(ids, extra_col, n_classes=70, columns=(0, 1, 65, 66)):
+    """Genuine multi-hot labels (two 64-bit words) with the relevance of the class ids: class c is column columns[c], and every fifth row
+    also carries `extra_col` -- give the queries one and the database another, so that it only keeps either matrix from being one-hot."""
+    m = np.zeros((ids.shape[0], n_classes), dtype=np.int64)
+    m[np.arange(ids.shape[0]), np.asarray(columns)[ids]] = 1
+    m[::5, extra_col] = 1
+    return m
 
 
 def load_golden(golden_dir):

@@ -102,8 +102,33 @@ CASES = {"c300": _c300, "c515_offset": _c515, "c1000_d768": _c1000, "c2000_d768"
 SAMPLED = {"c515_offset": [(200, 0), (200, 7)]}      # case -> (sample_size, random_state)
 
 
+# ---- past the shapes of silhouette.npz: D > 1024, hundreds of labels.  Expected values in tests/golden/metrics_wide.npz ("sil/<case>/<metric>")
+def _w2600():
+    return blobs(5, 2600, 1280, 200, sep=0.3)
+
+
+def _w400():
+    return blobs(6, 400, 1536, 6, sep=0.15)
+
+
+def _many_labels():
+    sizes = np.random.default_rng(7).integers(2, 5, size=1000).tolist() + [1] * 5      # 1000 labels of 2 - 4 points, five of one
+    return blobs(7, int(np.sum(sizes)), 24, len(sizes), sizes=sizes)
+
+
+WIDE_CASES = {"w2600_d1280_k200": _w2600, "w400_d1536": _w400, "many_labels_k1005": _many_labels}
+MFMA_MARGIN = 14.0      # what the tolerances leave over the emulation's error for the MFMA's summation order (tests/test_gpu_silhouette.py)
+
+
 def case_inputs(name):
-    return CASES[name]()
+    return (CASES[name] if name in CASES else WIDE_CASES[name])()
+
+
+def wide_bars(rec, metric):
+    """(per-sample bar, score bar) of a record of metrics_wide.npz: the constants where they leave MFMA_MARGIN x the recorded error of this
+    file's emulation against scikit-learn float64, MFMA_MARGIN x that error otherwise."""
+    es, ec = rec["restatement_max_err"][metric], rec["restatement_score_err"][metric]
+    return (TOL_SAMPLE if TOL_SAMPLE >= MFMA_MARGIN * es else MFMA_MARGIN * es), (TOL_SCORE if TOL_SCORE >= MFMA_MARGIN * ec else MFMA_MARGIN * ec)
 
 
 def sample_indices(n, sample_size, random_state):

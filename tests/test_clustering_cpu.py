@@ -114,6 +114,92 @@ def test_score_formulas_against_sklearn():
         assert max(abs(g - w) for g, w in zip(got, want)) <= 1e-12, (a[:8], b[:8], got, want)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+#  Past the shapes of clustering.npz (tests/golden/metrics_wide.npz): rows wider than 1024 columns, k above one 128-column assign tile,
+#  a contingency table of hundreds x hundreds of classes.  Every input the GPU tests of these shapes use is reproduced here first.
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def wide(golden_dir):
+    return CR.load_wide(golden_dir)
+
+
+def test_wide_golden_covers_the_cases(wide):
+    z, meta = wide
+    c = meta["cases"]
+    assert set(c) == {"wide8_d1280", "wide10_d1536", "set40_k150", "set20_k200"}
+    assert meta["max_unstable"] == 0 and meta["min_gap"] == 1e-5 and meta["noise"] == 1e-6 and len(meta["noise_seeds"]) == 3
+    assert (c["wide8_d1280"]["gen"]["d"], c["wide10_d1536"]["gen"]["d"]) == (1280, 1536)                  # dpad > 1024: two column blocks
+    assert (c["set40_k150"]["k"], c["set20_k200"]["k"]) == (150, 200)                                     # kpad 160 and 224
+    assert [K._trials(m["k"]) for m in c.values()] == [4, 4, 7, 7] and 10 * K._trials(150) > 64           # more than 64 seeding candidates
+    for name, m in c.items():
+        assert m["nearest_other_partition_gap"] is None or m["nearest_other_partition_gap"] >= meta["min_gap"], name
+        assert z[f"{name}/km_labels"].shape == (m["gen"]["n"],) and z[f"{name}/seeds0"].shape == (m["k"],)
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "metrics_wide.npz")) < 1 << 20
+
+
+@pytest.mark.parametrize("name", ["wide8_d1280", "wide10_d1536", "set40_k150", "set20_k200"])
+def test_restatement_reproduces_the_wide_cases(wide, name):
+    """As test_restatement_reproduces_the_reference_partition: scikit-learn's partition, n_iter, first-restart seed rows and inertia, and
+    the reference's three scores within 1e-12."""
+    z, meta = wide
+    c = meta["cases"][name]
+    x, lab = CR.case_inputs(z, meta, name)
+    mine = CR.kmeans(x, c["k"])
+    assert CR.scores(mine["labels"], z[f"{name}/km_labels"])[0] == 1.0 and CR.same_partition(mine["labels"], z[f"{name}/km_labels"])
+    assert mine["n_iter"] == c["n_iter"]
+    assert np.array_equal(mine["seed_indices"][0], z[f"{name}/seeds0"])
+    assert abs(mine["inertia"] - c["inertia"]) <= 1e-5 * c["inertia"]
+    assert mine["best_init"] == c["restatement_best_init"]
+    sc = CR.scores(CR.reduce_labels(lab), mine["labels"])
+    for key, v in zip(("clustering_ari", "clustering_nmi", "clustering_v_measure"), sc):
+        assert abs(v - c["eval_clustering"][key]) <= 1e-12, (key, v)
+
+
+def test_separated_sets_have_a_margin():
+    """The condition under which tests/test_gpu_clustering.py asks for label equality with NumPy on EVERY point: in each checked assign
+    (from the explicit init and after one and two updates) the fp64 gap between a point's nearest and second-nearest centre is at
+    least 1e-4 of the nearest squared distance.  The same for the k = 1100 set from either restart's seed rows, whose restarts' inertias
+    are far enough apart that both sides pick the same winner, and for the two relocation sets (bit-identical centres counted once)."""
+    for k, seed in {130: 130, 160: 160, 257: 258}.items():
+        x, lab = CR.separated(seed, k, 3, 16)
+        assert x.shape == (3 * k, 16) and np.bincount(lab).tolist() == [3] * k
+        init = x[np.random.default_rng(k).choice(x.shape[0], size=k, replace=False)]
+        assert CR.assign_margin(x, init, 3) >= 1e-4, k
+    x, _ = CR.separated(7, 1100, 3, 16)
+    km = CR.kmeans(x, 1100, n_init=2, max_iter=1)
+    assert K._trials(1100) == 9 and km["seed_indices"].shape == (2, 1100)
+    assert abs(km["inertias"][0] - km["inertias"][1]) >= 1e-4 * km["inertias"].min()
+    for r in range(2):
+        assert CR.assign_margin(x, x[km["seed_indices"][r]], 2) >= 1e-4, r
+    for k, copies, per, d, seed in ((160, 20, 5, 16, 99), (12, 3, 8, 1100, 98)):
+        x, _ = CR.separated(seed, k, per, d)
+        init = CR.duplicate_init(x, k, copies, 5)
+        assert np.unique(init, axis=0).shape[0] == k - copies + 1
+        assert CR.assign_margin(x, init, 4) >= 1e-4, k
+        trace = []
+        CR.kmeans(x, k, init=init, max_iter=3, trace=trace)
+        assert (np.bincount(trace[0], minlength=k) == 0).sum() == copies - 1      # the first copy wins every tie; the rest start empty
+
+
+def test_scores_on_a_large_table(wide):
+    """The restatement against sklearn.metrics on a table of 300 x 350 occupied classes: the values the generator recorded, and
+    scikit-learn itself where it is installed."""
+    _, meta = wide
+    rec = meta["scores_table"]
+    a, b = CR.label_pair(**rec["gen"])
+    assert CR.sha256(a, b) == rec["sha256"] and rec["gen"]["n"] == 20000
+    t = CR.contingency(a, b)
+    assert t.shape == (300, 350) == (rec["classes_true"], rec["classes_pred"]) and (t > 0).sum() > 5000      # the goldens: at most 30 x 30 cells
+    got = CR.scores(a, b)
+    assert max(abs(got[0] - rec["ari"]), abs(got[1] - rec["nmi"]), abs(got[2] - rec["v_measure"])) <= 1e-12, (got, rec)
+    try:
+        from sklearn import metrics
+    except ImportError:
+        return
+    want = (metrics.adjusted_rand_score(a, b), metrics.normalized_mutual_info_score(a, b), metrics.v_measure_score(a, b))
+    assert max(abs(g - w) for g, w in zip(got, want)) <= 1e-12, (got, want)
+
+
 def test_random_number_protocol():
     """The module's draws are the restatement's (which the golden pins to scikit-learn through the seed rows), they depend on (n, k,
     n_init, seed) only, and another seed gives other numbers."""

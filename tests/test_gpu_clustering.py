@@ -22,6 +22,14 @@ def golden(golden_dir):
 
 
 @pytest.fixture(scope="module")
+def wide(golden_dir):
+    return CR.load_wide(golden_dir)
+
+
+WIDE = ("wide8_d1280", "wide10_d1536", "set40_k150", "set20_k200")      # the clustering cases of tests/golden/metrics_wide.npz
+
+
+@pytest.fixture(scope="module")
 def K(built_lib):
     from avex_amd import clustering
     return clustering
@@ -31,11 +39,10 @@ def _np(t):
     return t.cpu().numpy()
 
 
-def test_every_golden_case_reproduces_the_reference(K, golden):
-    """eval_clustering on every golden case: the reference's three scores within 1e-12, and (through kmeans) its partition."""
-    z, meta = golden
+def _check_cases_reproduce_the_reference(K, z, meta, names):
     assert meta["max_unstable"] == 0
-    for name, c in meta["cases"].items():
+    for name in names:
+        c = meta["cases"][name]
         x, lab = CR.case_inputs(z, meta, name)
         got = K.eval_clustering(x, lab, n_clusters=c["n_clusters"])
         ref = c["eval_clustering"]
@@ -50,6 +57,24 @@ def test_every_golden_case_reproduces_the_reference(K, golden):
             assert km["n_iter"] == c["n_iter"], name
         for key in KEYS:
             assert abs(got[key] - ref[key]) <= 1e-12, (name, key, got[key], ref[key])
+
+
+def test_every_golden_case_reproduces_the_reference(K, golden):
+    """eval_clustering on every golden case: the reference's three scores within 1e-12, and (through kmeans) its partition."""
+    z, meta = golden
+    _check_cases_reproduce_the_reference(K, z, meta, list(meta["cases"]))
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_every_wide_case_reproduces_the_reference(K, wide, name):
+    """The same contract past the shapes of clustering.npz.  dpad = 1280 / 1536 > 1024: the second column block of clus_update_kernel
+    (blockIdx.y = 1) and the second trip of the col += 1024 loops of clus_seed_pick_kernel / clus_relocate_kernel and of the e += 1024
+    loop of clus_decide_kernel past one row.  k = 150 / 200 (kpad 160 / 224): a restart's centres span two 128-column tiles of
+    clus_assign_kernel and meet only in the 64-bit atomicMin, restart and tile boundaries fall at different columns, trials_of(k) = 7,
+    and clus_seed_dist_kernel sees 70 candidates (more than 64)."""
+    z, meta = wide
+    assert set(meta["cases"]) == set(WIDE)
+    _check_cases_reproduce_the_reference(K, z, meta, [name])
 
 
 def test_multiple_k_matches_the_reference(K, golden):
@@ -71,7 +96,19 @@ def test_seeding_matches_the_restatement_and_the_reference(K, golden):
     """k-means++ stage: the seed rows of EVERY restart against the restatement (same draws, same summation order: equal), and the first
     restart's against sklearn.cluster.kmeans_plusplus as recorded in the golden."""
     z, meta = golden
-    for name in ("set8", "set30_d100", "set12_k30", "label_minus1", "n6_k10"):
+    _check_seeding(K, z, meta, ("set8", "set30_d100", "set12_k30", "label_minus1", "n6_k10"))
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_seeding_of_the_wide_cases_matches_the_restatement_and_the_reference(K, wide, name):
+    """clus_seed_dist_kernel / clus_seed_pick_kernel at dpad > 1024 (the chosen row is copied into the centre table in two trips) and with
+    7 trials x 10 restarts = 70 candidates per step (five candidate groups of 16): all ten restarts' seed rows."""
+    z, meta = wide
+    _check_seeding(K, z, meta, (name,))
+
+
+def _check_seeding(K, z, meta, names):
+    for name in names:
         c = meta["cases"][name]
         x, _ = CR.case_inputs(z, meta, name)
         k = c["k"]
@@ -131,6 +168,91 @@ def test_assign_epilogue_paths_match_the_restatement(K, golden):
             assert float(one["inertias"][0]) == float(lock["inertias"][r]) and int(one["n_iters"][0]) == int(lock["n_iters"][r]), (k, r)
 
 
+EPILOGUE_WIDE = {130: 130, 160: 160, 257: 258}      # k -> data seed of CR.separated(seed, k, 3, 16); tests/test_clustering_cpu.py asserts the margin
+
+
+def test_assign_epilogue_paths_across_column_tiles(K):
+    """clus_assign_kernel with k > 128: kpad = 160 (k = 130, 160) and 288 (k = 257), so ONE restart's centres lie in two or three
+    128-column tiles, whose partial minima meet only in the 64-bit atomicMin, and with n_init = 4 the restart boundaries (multiples of
+    kpad) and the tile boundaries (multiples of 128) fall at different columns: waves with one_restart and waves that straddle two
+    restarts (rst[1]) in the same launch.  Labels after one and two iterations from an explicit init equal the restatement's on every
+    point (about three points per well-separated class: a margin of >= 1e-4 between nearest and second-nearest centre, asserted on the
+    CPU), and the lock-step restarts equal the same restarts run one at a time, bit for bit."""
+    for k, seed in EPILOGUE_WIDE.items():
+        x, _ = CR.separated(seed, k, 3, 16)
+        init = x[np.random.default_rng(k).choice(x.shape[0], size=k, replace=False)]
+        for m in (1, 2):
+            want, got = CR.kmeans(x, k, init=init, max_iter=m), K.kmeans(x, k, init=init, max_iter=m)
+            assert np.array_equal(_np(got["labels"]), want["labels"]), (k, m, int((_np(got["labels"]) != want["labels"]).sum()))
+            assert got["n_iter"] == want["n_iter"], (k, m)
+        lock = K.kmeans(x, k, n_init=4, max_iter=20)
+        rs = np.random.RandomState(42)
+        for r in range(4):
+            one = K.kmeans(x, k, n_init=1, max_iter=20, random_state=rs)
+            assert torch.equal(one["seed_indices"][0], lock["seed_indices"][r]), (k, r)
+            assert float(one["inertias"][0]) == float(lock["inertias"][r]) and int(one["n_iters"][0]) == int(lock["n_iters"][r]), (k, r)
+            if r == lock["best_init"]:
+                assert torch.equal(one["labels"], lock["labels"]) and torch.equal(one["centers"], lock["centers"]), (k, r)
+
+
+def test_k_1100_seeds_and_first_iteration(K):
+    """k = 1100 >= 1097: trials_of(k) = 9 (the largest count any test reaches), kpad = 1120 = 8.75 assign tiles per restart, two restarts
+    in lock-step.  Both restarts' seed rows equal the restatement's; the winner (the restatement's inertias are 1.4e-3 apart, asserted
+    on the CPU) and its labels after one iteration equal the restatement's, and so do the labels of either restart run alone from its
+    seed rows as an explicit init."""
+    k = 1100
+    x, _ = CR.separated(7, k, 3, 16)
+    want = CR.kmeans(x, k, n_init=2, max_iter=1)
+    got = K.kmeans(x, k, n_init=2, max_iter=1)
+    assert K._trials(k) == 9
+    seeds = _np(got["seed_indices"])
+    assert seeds.shape == (2, k) and np.array_equal(seeds, want["seed_indices"]), np.argwhere(seeds != want["seed_indices"])[:5]
+    rel = np.abs(_np(got["inertias"]) - want["inertias"]) / want["inertias"]
+    print(f"[clustering] k=1100: per-restart inertia, device - restatement (relative) {rel}, best_init {got['best_init']}")
+    assert got["best_init"] == want["best_init"] and (rel <= 1e-5).all()
+    assert np.array_equal(_np(got["labels"]), want["labels"]), int((_np(got["labels"]) != want["labels"]).sum())
+    for r in range(2):
+        alone = K.kmeans(x, k, init=x[want["seed_indices"][r]], max_iter=1)
+        assert np.array_equal(_np(alone["labels"]), want["all_labels"][r]), (r, int((_np(alone["labels"]) != want["all_labels"][r]).sum()))
+
+
+@pytest.mark.parametrize("k,copies,per,d,seed", [(160, 20, 5, 16, 99), (12, 3, 8, 1100, 98)])
+def test_relocation_of_many_empty_clusters(K, k, copies, per, d, seed):
+    """clus_relocate_kernel moving several points in one iteration: `copies` of the k explicit centres are the same data point, so after
+    the first assign copies - 1 clusters are empty (the first copy wins every tie) and as many points, farthest first, become centres.
+    At k = 160 that is 19 of 160 in one iteration (kpad = 160: two assign tiles); at D = 1100 (dpad 1120) the sums are moved in two trips
+    of the kernel's c += 1024 loop.  Labels, cluster sizes, n_iter and centres after iterations 1 - 3 against the restatement."""
+    x, _ = CR.separated(seed, k, per, d)
+    init = CR.duplicate_init(x, k, copies, 5)
+    xc, mean, _ = CR.prepare(x)
+    first_assign = CR.assign(xc, init - mean)[0]
+    assert (np.bincount(first_assign, minlength=k) == 0).sum() == copies - 1
+    for m in (1, 2, 3):
+        want, got = CR.kmeans(x, k, init=init, max_iter=m), K.kmeans(x, k, init=init, max_iter=m)
+        lab = _np(got["labels"])
+        assert np.array_equal(lab, want["labels"]), (m, int((lab != want["labels"]).sum()))
+        assert np.array_equal(np.bincount(lab, minlength=k), np.bincount(want["labels"], minlength=k)), m
+        assert got["n_iter"] == want["n_iter"] and got["best_init"] == 0
+        assert np.abs(_np(got["centers"]) - want["centers"]).max() <= 1e-5 * max(1.0, np.abs(want["centers"]).max()), m
+    assert np.bincount(_np(K.kmeans(x, k, init=init)["labels"]), minlength=k).min() > 0
+
+
+def test_scores_kernel_on_a_large_table(K, wide):
+    """clus_contingency_kernel / clus_scores_kernel on 20 000 labels with about 300 x 350 occupied classes (the goldens have at most
+    30 x 30): within 1e-12 of the restatement, which tests/test_clustering_cpu.py pins to sklearn.metrics on this very table."""
+    _, meta = wide
+    rec = meta["scores_table"]
+    a, b = CR.label_pair(**rec["gen"])
+    assert CR.sha256(a, b) == rec["sha256"] and (np.unique(a).size, np.unique(b).size) == (rec["classes_true"], rec["classes_pred"])
+    want = CR.scores(a, b)
+    for ta, tb in ((a, b), (torch.from_numpy(a).cuda(), torch.from_numpy(b.astype(np.int32)).cuda()), (a * 3 - 400, 10000 - 7 * b)):
+        got = K.clustering_scores(ta, tb)
+        err = max(abs(got["ari"] - want[0]), abs(got["nmi"] - want[1]), abs(got["v_measure"] - want[2]))
+        print(f"[clustering] scores on a {rec['classes_true']} x {rec['classes_pred']} table: device {got}, max error {err:.3e}")
+        assert err <= 1e-12, (got, want)
+        assert max(abs(got["ari"] - rec["ari"]), abs(got["nmi"] - rec["nmi"]), abs(got["v_measure"] - rec["v_measure"])) <= 1e-12
+
+
 def test_winning_restart_and_per_restart_results(K, golden):
     z, meta = golden
     for name in ("set8", "set12", "set30_d100"):
@@ -153,8 +275,18 @@ def test_inertia_against_fp64_recomputation(K, golden):
     in fp64, |error| <= (D + 2) u (1 + small).  The returned centres carry the mean again (one more rounding of |centre + mean| u per
     element), which moves each difference by at most u (|centre| + |mean|) and the total by sum 2 |diff| u (|centre| + |mean|)."""
     z, meta = golden
+    _check_inertia(K, z, meta, ("set8", "set20_d768", "set30_d100"))
+
+
+def test_inertia_of_the_wide_cases_against_fp64_recomputation(K, wide):
+    """clus_inertia_kernel and clus_export_kernel at D = 1280 and 1536; the bound above is already a function of D."""
+    z, meta = wide
+    _check_inertia(K, z, meta, ("wide8_d1280", "wide10_d1536"))
+
+
+def _check_inertia(K, z, meta, names):
     u = 2.0 ** -24
-    for name in ("set8", "set20_d768", "set30_d100"):
+    for name in names:
         c = meta["cases"][name]
         x, _ = CR.case_inputs(z, meta, name)
         km = K.kmeans(x, c["k"])

@@ -215,3 +215,118 @@ def test_working_memory_is_batch_by_n(R):
     print(f"[retrieval] N=32768 D=768: {m['seconds']:.3f} s, peak growth {m['growth'] / 2**20:.0f} MiB (budget {(m['inputs'] + m['budget']) / 2**20:.0f} MiB) {m['out']}")
     assert m["growth"] <= m["inputs"] + m["budget"], m
     assert 0.5 < m["out"]["retrieval_roc_auc"] <= 1.0 and 0.0 <= m["out"]["retrieval_precision_at_1"] <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+#  retr_rank_kernel, chunked U2: the smaller of {positives, negatives} of a query exceeds cap = 16 384 keys, so the kernel sorts it in
+#  column chunks of 16 384 (n_db = 40 001: three chunks, the last one 7 233 columns wide -- odd, no multiple of 64).  Per chunk it refills
+#  `keys`, resets `fill`, pads with +inf up to the next power of two and skips a chunk without keys.  RR.chunked_case puts into ONE launch
+#  queries with pos_small true (class 0: 48 % of the database) and false (class 1: 52 %), a row sorted as a single chunk (class 2: 30
+#  items) and a skipped row (class 3: P = 0); every database row exists four times, so equal
+#  similarities lie in different chunks and on both sides.  No golden: the reference is NumPy on the device's own similarities.
+# ------------------------------------------------------------------------------------------------------------------------------
+_INT_KEYS = ("u2", "n_pos", "n_neg", "valid_auc", "valid_prec", "topk_idx", "hits")
+
+
+def _assert_rank_stage(got, want, tag):
+    assert got["k"] == want["k"], tag
+    for key in _INT_KEYS:
+        g = got[key].cpu().numpy()
+        assert np.array_equal(g, want[key]), (tag, key, np.flatnonzero((g != want[key]).reshape(g.shape[0], -1).any(axis=1))[:8])
+    auc, prec = RR.metrics_from_stats(want)
+    assert abs(got["auc_sum"] / max(got["auc_count"], 1) - auc) <= 1e-13, tag
+    assert abs(got["prec_sum"] / max(got["prec_count"], 1) - prec) <= 1e-13, tag
+    assert got["auc_count"] == int(want["valid_auc"].sum()) and got["prec_count"] == int(want["valid_prec"].sum()), tag
+
+
+def test_chunked_rank_path_is_exact_for_the_device_similarities(R):
+    """Enters retr_rank_kernel's chunk loop with three chunks, pos_small in both senses, ties across chunk boundaries and a ragged last
+    chunk; class ids and, once, multi-hot labels of 70 classes (n_words = 2) through the same chunks.  U2, P, Q, the skip flags, the
+    top-k and the hits equal NumPy's on the device's own similarities, integer for integer, k in {1, 32}; the similarities meet the
+    bound of test_similarity_error_against_fp64 with the fp32 NumPy product of the same inputs as the yardstick."""
+    q, qi, db, di = RR.chunked_case()
+    assert db.shape == (40001, 40) and np.unique(db, axis=0).shape[0] == 10001
+    counts = np.bincount(di, minlength=4)
+    assert min(counts[0], counts[1]) > 16384 and counts[2] == 30 and counts[3] == 0      # both large classes chunk, whichever side is smaller
+    rel = RR.relevance_cross(qi, di)
+    want, base_sim = {}, None
+    for k in (1, 32):
+        got = R.retrieval_stats(q, qi, db, di, k=k, return_sim=True)
+        sim = got["sim"].cpu().numpy()
+        if base_sim is None:
+            base_sim = sim
+            row = np.sort(sim[0])
+            assert (row[1:] == row[:-1]).sum() >= 30000      # the copies of a row really tie, on the device too
+        assert np.array_equal(sim, base_sim)
+        want[k] = RR.stats_from_sim(sim, rel, False, k)
+        _assert_rank_stage(got, want[k], ("ids", k))
+    w = want[32]
+    assert (w["n_pos"][qi == 0] < w["n_neg"][qi == 0]).all() and (w["n_pos"][qi == 1] > w["n_neg"][qi == 1]).all()      # pos_small true / false
+    assert (w["n_pos"][qi == 2] == 30).all() and (w["n_pos"][qi == 3] == 0).all() and not w["valid_auc"][qi == 3].any()
+    sim64 = np.matmul(RR.normed(q.astype(np.float64)), RR.normed(db.astype(np.float64)).T)
+    ref_err = float(np.abs(np.matmul(RR.normed(q), RR.normed(db).T).astype(np.float64) - sim64).max())
+    err = float(np.abs(base_sim.astype(np.float64) - sim64).max())
+    print(f"[retrieval] chunked n_db=40001 D=40: similarity max abs error {err:.3e} (NumPy fp32 {ref_err:.3e}, bar {4.0 * ref_err:.3e})")
+    assert err <= 4.0 * ref_err, (err, ref_err)
+    # the same relevance as two label words per row
+    mq, md = RR.multihot_of(qi, 68), RR.multihot_of(di, 69)
+    assert RR.collapse_one_hot(mq).ndim == 2 and RR.collapse_one_hot(md).ndim == 2 and np.array_equal(RR.relevance_cross(mq, md), rel)
+    got = R.retrieval_stats(q, mq, db, md, k=32, return_sim=True)
+    assert np.array_equal(got["sim"].cpu().numpy(), base_sim)
+    _assert_rank_stage(got, want[32], ("words", 32))
+
+
+@pytest.mark.parametrize("n0", [16384, 16385])
+def test_chunked_rank_path_at_the_chunk_threshold(R, n0):
+    """The balanced class has exactly cap = 16 384 members (the last size sorted as one chunk: cw = the whole row) and 16 385 (the first
+    size sorted in chunks of 16 384 columns); the class-1 queries of both variants chunk with pos_small false."""
+    q, qi, db, di = RR.chunked_case(n0=n0, per_class=4)
+    assert np.bincount(di, minlength=4).tolist() == [n0, 40001 - n0 - 30, 30, 0]
+    rel = RR.relevance_cross(qi, di)
+    for k in (1, 32):
+        got = R.retrieval_stats(q, qi, db, di, k=k, return_sim=True)
+        want = RR.stats_from_sim(got["sim"].cpu().numpy(), rel, False, k)
+        assert (want["n_pos"][qi == 0] == n0).all() and (want["n_neg"][qi == 0] > n0).all()
+        _assert_rank_stage(got, want, (n0, k))
+
+
+def test_chunked_rank_path_self_set_through_the_c_entry(R, built_lib):
+    """Self-set rows of the 40 001-item database, 32 per launch, through avexhip_retrieval_prepare / avexhip_retrieval_batch as
+    retrieval_stats drives them (all 40 001 queries would need a 6 GB similarity matrix): q0 puts the column the rank kernel leaves out
+    at the end of chunk 0, at the start of chunk 1, across the boundary of chunks 1 and 2, and in the ragged last chunk."""
+    import ctypes as C
+    from avex_amd import _capi
+    _, _, db, di = RR.chunked_case()
+    n_db, d, nb, k = db.shape[0], db.shape[1], 32, 32
+    x = torch.from_numpy(db).cuda()
+    ids = torch.from_numpy(di.astype(np.int32)).cuda()
+    lib = built_lib
+    ws_bytes = int(lib.avexhip_retrieval_workspace_bytes(n_db, d, nb, 0))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    _capi.check(lib.avexhip_retrieval_prepare(x.data_ptr(), x.stride(0), n_db, d, nb, ws.data_ptr(), ws_bytes, s), "retrieval_prepare")
+    for q0 in (16352, 16384, 32752, 39969):
+        u2 = torch.empty((nb,), dtype=torch.int64, device="cuda")
+        stats = torch.empty((nb, 4), dtype=torch.int32, device="cuda")
+        topk = torch.empty((nb, R.MAX_K), dtype=torch.int32, device="cuda")
+        sim = torch.empty((nb, n_db), dtype=torch.float32, device="cuda")
+        a = _capi.RetrievalArgs()
+        a.n_db, a.d, a.batch, a.n_words, a.self_set, a.k, a.stages = n_db, d, nb, 0, 1, k, 3
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        a.db_ids, a.db_words, a.query_words = ids.data_ptr(), None, None
+        a.nb, a.q0, a.query, a.ld_query = nb, q0, None, 0
+        a.query_ids = ids.data_ptr() + 4 * q0
+        a.u2, a.stats, a.topk = u2.data_ptr(), stats.data_ptr(), topk.data_ptr()
+        a.sim_out, a.ld_sim = sim.data_ptr(), n_db
+        _capi.check(lib.avexhip_retrieval_batch(C.byref(a), s), "retrieval_batch")
+        torch.cuda.synchronize()
+        rel = di[q0:q0 + nb, None] == di[None, :]
+        want = RR.stats_from_sim(sim.cpu().numpy(), rel, True, k, row0=q0)
+        st = stats.cpu().numpy()
+        assert (np.minimum(want["n_pos"], want["n_neg"])[di[q0:q0 + nb] < 2] > 16384).all()      # these rows chunk
+        assert np.array_equal(u2.cpu().numpy(), want["u2"]), (q0, np.flatnonzero(u2.cpu().numpy() != want["u2"]))
+        assert np.array_equal(st[:, 0], want["n_pos"]) and np.array_equal(st[:, 1], want["n_neg"]), q0
+        assert np.array_equal(st[:, 2] > 1, want["valid_prec"]) and np.array_equal(st[:, 2], rel.sum(axis=1)), q0
+        assert np.array_equal(topk.cpu().numpy()[:, :k], want["topk_idx"]), q0
+        assert np.array_equal(st[:, 3], want["hits"]), q0
+        assert not (want["topk_idx"] == (q0 + np.arange(nb))[:, None]).any()                      # a row never retrieves itself

@@ -21,6 +21,11 @@ def golden(golden_dir):
 
 
 @pytest.fixture(scope="module")
+def wide(golden_dir):
+    return CR.load_wide(golden_dir)
+
+
+@pytest.fixture(scope="module")
 def K(built_lib):
     from avex_amd import clustering
     return clustering
@@ -131,6 +136,84 @@ def test_eval_clustering_with_silhouette(K, golden_dir):
     assert got["clustering_silhouette"] == K.silhouette_score(x, km["labels"])
     assert abs(got["clustering_silhouette"] - SR.silhouette_score(x, _np(km["labels"]))) <= SR.TOL_SCORE
     assert K.eval_clustering_silhouette(torch.from_numpy(x).cuda(), torch.from_numpy(lab).cuda()) == got
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+#  Past the shapes of silhouette.npz (SR.WIDE_CASES, expected values in tests/golden/metrics_wide.npz): D = 1280 and 1536 (the K loop of
+#  the shared fp32 tile runs 40 / 48 steps and the centring pass of clustering.hip takes its second column block), 200 and 1005 labels
+#  (n_slots grows by up to 31 padding slots per label: 3041 points occupy 32 256 slots, so most row tiles and column segments of the
+#  product are padding next to two to four live rows), and more than one batch at those sizes.  The bars follow the header's rule case by
+#  case: the constant where it leaves 14 x the recorded error of the NumPy emulation, 14 x that error otherwise (SR.wide_bars).
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("metric", SR.METRICS)
+@pytest.mark.parametrize("name", list(SR.WIDE_CASES))
+def test_wide_golden_case(K, wide, name, metric):
+    z, meta = wide
+    rec = meta["silhouette"]["cases"][name]
+    x, lab = SR.case_inputs(name)
+    assert (x.shape[0], x.shape[1], np.unique(lab).size) == (rec["n"], rec["d"], rec["k"])
+    bar, score_bar = SR.wide_bars(rec, metric)
+    got = K.silhouette_samples(x, lab, metric=metric)
+    assert got.is_cuda and got.dtype == torch.float64 and tuple(got.shape) == (x.shape[0],)
+    score = K.silhouette_score(x, lab, metric=metric)
+    err = float(np.abs(_np(got) - z[f"sil/{name}/{metric}"]).max())
+    score_err = abs(score - rec["score"][metric])
+    print(f"[silhouette] {name} {metric}: per sample {err:.3e} (bar {bar:.3e}, emulation {rec['restatement_max_err'][metric]:.3e}), "
+          f"score {score_err:.3e} (bar {score_bar:.3e}, emulation {rec['restatement_score_err'][metric]:.3e}, device {score!r})")
+    assert isinstance(score, float)
+    assert err <= bar, (name, metric, err, bar)
+    assert score_err <= score_bar, (name, metric, score_err, score_bar)
+
+
+@pytest.mark.parametrize("metric", SR.METRICS)
+def test_bit_for_bit_equal_at_200_labels_and_d1280(K, metric):
+    """2600 points, 200 labels, D = 1280 (about 7 400 slots): one batch (2048 slots and more), several (384) and many (128), host and
+    device inputs -- the integer sums make every one of them the same bits."""
+    x, lab = SR.case_inputs("w2600_d1280_k200")
+    base = K.silhouette_samples(x, lab, metric=metric)
+    base_score = K.silhouette_score(x, lab, metric=metric)
+    for batch_size in (128, 384, 2048):
+        other = K.silhouette_samples(x, lab, metric=metric, batch_size=batch_size)
+        assert torch.equal(base, other), (metric, batch_size, float((base - other).abs().max()))
+        assert K.silhouette_score(x, lab, metric=metric, batch_size=batch_size) == base_score
+    xd, labd = torch.from_numpy(x).cuda(), torch.from_numpy(lab).cuda()
+    assert torch.equal(base, K.silhouette_samples(xd, labd, metric=metric, batch_size=384))
+    assert torch.equal(base, K.silhouette_samples(xd, lab, metric=metric))
+    assert K.silhouette_score(xd, labd, metric=metric) == base_score
+
+
+@pytest.mark.parametrize("metric", SR.METRICS)
+def test_singletons_among_a_thousand_labels(K, wide, metric):
+    """1000 labels of two to four points and five of one: a point alone in its cluster scores exactly 0.0, every other one does not, and
+    several batches change nothing."""
+    z, _ = wide
+    x, lab = SR.case_inputs("many_labels_k1005")
+    s = _np(K.silhouette_samples(x, lab, metric=metric))
+    alone = np.bincount(lab)[lab] == 1
+    assert alone.sum() == 5 and (s[alone] == 0.0).all() and (s[~alone] != 0.0).all()
+    assert (z[f"sil/many_labels_k1005/{metric}"][alone] == 0.0).all()
+    assert np.array_equal(s, _np(K.silhouette_samples(x, lab, metric=metric, batch_size=4096)))
+
+
+def test_eval_clustering_with_silhouette_on_wide_rows(K, wide):
+    """eval_clustering_silhouette at D = 1280: the silhouette kernels read the rows the clustering kernels centred (ld = dpad = 1280).  The
+    three scores are the reference's within 1e-12; the silhouette column is scikit-learn's float64 score of scikit-learn's own k-means
+    partition -- the same partition, as test_gpu_clustering.py checks -- within the bar of its recorded emulation error."""
+    z, meta = wide
+    rec = meta["eval_silhouette"]
+    name = rec["case"]
+    x, lab = CR.case_inputs(z, meta, name)
+    got = K.eval_clustering_silhouette(x, lab)
+    print(f"[silhouette] eval_clustering_silhouette {name}: {got}")
+    for key, v in meta["cases"][name]["eval_clustering"].items():
+        assert abs(got[key] - v) <= 1e-12, (key, got[key], v)
+    _, score_bar = SR.wide_bars(rec, "euclidean")
+    err = abs(got["clustering_silhouette"] - rec["score"])
+    print(f"[silhouette] eval_clustering_silhouette {name}: silhouette error {err:.3e} (bar {score_bar:.3e}, emulation {rec['restatement_score_err']['euclidean']:.3e})")
+    assert err <= score_bar, (err, score_bar)
+    km = K.kmeans(x, meta["cases"][name]["k"])
+    assert CR.same_partition(_np(km["labels"]), z[f"{name}/km_labels"])
+    assert got["clustering_silhouette"] == K.silhouette_score(x, km["labels"])
 
 
 def test_eval_clustering_multiple_k_with_silhouette(K, golden_dir):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _clustering_ref as CR
 import _silhouette_ref as SR
 from avex_amd import _capi
 from avex_amd import clustering as K
@@ -61,6 +62,63 @@ def test_restatement_reproduces_every_golden(golden, metric):
         x, lab = SR.case_inputs(rec["case"])
         got = SR.silhouette_score(x, lab, metric, sample_size=rec["sample_size"], random_state=rec["random_state"])
         assert abs(got - rec["score"][metric]) <= SR.TOL_SCORE, (rec, metric, got)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+#  Past the shapes of silhouette.npz: SR.WIDE_CASES against tests/golden/metrics_wide.npz
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def wide(golden_dir):
+    return CR.load_wide(golden_dir)
+
+
+def test_wide_golden_covers_the_cases(wide):
+    z, meta = wide
+    sil = meta["silhouette"]
+    assert set(sil["cases"]) == set(SR.WIDE_CASES) and not set(SR.WIDE_CASES) & set(SR.CASES)
+    assert (sil["tol_sample"], sil["tol_score"], sil["mfma_margin"]) == (SR.TOL_SAMPLE, SR.TOL_SCORE, SR.MFMA_MARGIN) == (1e-6, 1e-7, 14.0)
+    shape = {name: (m["n"], m["d"], m["k"]) for name, m in sil["cases"].items()}
+    assert shape["w2600_d1280_k200"] == (2600, 1280, 200) and shape["w400_d1536"] == (400, 1536, 6) and shape["many_labels_k1005"][1:] == (24, 1005)
+    sizes = np.bincount(SR.case_inputs("many_labels_k1005")[1])
+    assert (sizes == 1).sum() == 5 and sizes.max() == 4 and ((sizes >= 2) & (sizes <= 4)).sum() == 1000
+    for name, m in sil["cases"].items():
+        assert m["conditions"]["min_separation_over_rms"] >= 1e-2 and m["conditions"]["mean_cosine_distance"] >= 0.5, name
+        for metric in SR.METRICS:
+            assert z[f"sil/{name}/{metric}"].dtype == np.float64 and z[f"sil/{name}/{metric}"].shape == (m["n"],)
+            # the bars are the constants, or 14 x the recorded emulation error where that is larger -- never below the constants
+            bar, score_bar = SR.wide_bars(m, metric)
+            assert bar == max(SR.TOL_SAMPLE, 14.0 * m["restatement_max_err"][metric]) and score_bar == max(SR.TOL_SCORE, 14.0 * m["restatement_score_err"][metric])
+    ev = meta["eval_silhouette"]
+    assert ev["case"] == "wide8_d1280" and meta["cases"][ev["case"]]["gen"]["d"] == 1280
+
+
+@pytest.mark.parametrize("metric", SR.METRICS)
+@pytest.mark.parametrize("name", list(SR.WIDE_CASES))
+def test_restatement_reproduces_the_wide_cases(wide, name, metric):
+    """The emulation's error against scikit-learn float64 IS what the generator recorded (the basis of the GPU tests' bars), and it is
+    inside the bar the device has to meet with the margin left over."""
+    z, meta = wide
+    m = meta["silhouette"]["cases"][name]
+    x, lab = SR.case_inputs(name)
+    got = SR.silhouette_samples(x, lab, metric)
+    err = float(np.abs(got - z[f"sil/{name}/{metric}"]).max())
+    score_err = abs(float(got.sum() / got.shape[0]) - m["score"][metric])
+    bar, score_bar = SR.wide_bars(m, metric)
+    print(f"[silhouette] restatement {name} {metric}: per sample {err:.2e} (bar {bar:.2e}), score {score_err:.2e} (bar {score_bar:.2e})")
+    # to 10 %: another BLAS may round a Gram entry the other way
+    assert abs(err - m["restatement_max_err"][metric]) <= 0.1 * err and abs(score_err - m["restatement_score_err"][metric]) <= 0.1 * score_err
+    assert SR.MFMA_MARGIN * err <= 1.1 * bar and SR.MFMA_MARGIN * score_err <= 1.1 * score_bar
+    alone = np.bincount(lab)[lab] == 1
+    assert (got[alone] == 0.0).all() and (z[f"sil/{name}/{metric}"][alone] == 0.0).all()
+
+
+def test_restatement_on_the_wide_clustering_partition(wide):
+    z, meta = wide
+    ev = meta["eval_silhouette"]
+    x, _ = CR.case_inputs(z, meta, ev["case"])
+    km = z[f"{ev['case']}/km_labels"].astype(np.int64)
+    err = abs(SR.silhouette_score(x, km) - ev["score"])
+    assert abs(err - ev["restatement_score_err"]["euclidean"]) <= 0.1 * err and err <= SR.TOL_SCORE / SR.MFMA_MARGIN
 
 
 def test_restatement_duplicates_and_singletons(golden):
