@@ -106,6 +106,10 @@ class SilhouetteArgs(C.Structure):
                 ("reserved", C.c_int32), ("samples_out", C.c_void_p)]
 
 
+class Window(C.Structure):
+    _fields_ = [("base", C.c_int64), ("n_samples", C.c_int64), ("start", C.c_int64), ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -137,6 +141,9 @@ SYMBOLS = {
     "avexhip_pcm_to_mono_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "avexhip_ingest_batch_workspace_bytes": (C.c_size_t, [_P, C.c_int, _P, C.c_int, C.c_int64]),
     "avexhip_ingest_batch": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "avexhip_window_stats": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "avexhip_window_select": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_float, _P, _P, _P]),
+    "avexhip_window_gather": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "avexhip_flac_open": (_P, [_P, C.c_size_t]),
     "avexhip_flac_close": (None, [_P]),
     "avexhip_flac_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), _P]),

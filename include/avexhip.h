@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 13
+#define AVEXHIP_ABI_VERSION 14
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -188,6 +188,42 @@ size_t avexhip_ingest_batch_workspace_bytes(const avexhip_ingest_item* items_hos
 int avexhip_ingest_batch(const void* raw_dev, size_t raw_bytes, const avexhip_ingest_item* items_host, const avexhip_ingest_item* items_dev, int B,
                          const avexhip_resample_plan* const* plans, int n_plans, int64_t T_out, float* wav_dev, int64_t wav_stride,
                          uint8_t* mask_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Whole-recording windows (ABI 14): every sliding window of one or more recordings from ONE resident fp32 waveform each -- what
+ * load_audio leaves on the device: decoded, mono, resampled once -- instead of one ingest per window.  The reference crops a long clip to
+ * a single window (avex/data/audio_utils.py:16-73) and names the step that would choose windows without building it
+ * (avex/preprocessing/activity_detector.py is empty).  A window row is pad_or_window(wav[start:], window_len, "start"): the samples, then
+ * zeros, padding_mask True on the zeros.
+ *   wav_dev      the recordings back to back in one buffer of wav_samples floats, 16-byte aligned
+ *   win_host     the window table, read here for the argument checks
+ *   win_dev      the same table in device memory, 8-byte aligned; the kernels read this one, so it must equal win_host
+ * avexhip_window_stats    per window w: peak_dev[w] = max |x| (fp32), energy_dev[w] = sum x^2 over its valid samples (fp64; x^2 of an fp32
+ *                         value is exact in fp64, so the additions are the only roundings).  One workgroup per window, sample j on thread
+ *                         (j / 4) % 256, lane sums and the workgroup tree in a fixed order: the two numbers of a window depend on its
+ *                         samples only, not on the other windows of the launch.  A NaN or Inf sample makes both NaN.
+ * avexhip_window_select   kept_dev[0 .. *count_dev) = the windows with valid > 0, energy >= thr_energy * valid and peak >= thr_peak, in
+ *                         increasing order (a prefix sum, no atomics); a threshold of -inf is off; NaN statistics are never kept.
+ *                         kept_dev holds n_win ints; entries from *count_dev on are left as they were.
+ * avexhip_window_gather   out_dev [B, window_len] fp32 (row stride out_stride, <= 0: window_len) and mask_dev [B, window_len] bytes
+ *                         (1 = padding) for the windows index_dev[0 .. B) (device ints, e.g. a piece of kept_dev), or first .. first + B - 1
+ *                         when index_dev is NULL.  A number outside 0 .. n_win - 1 in index_dev gives a zero row that is all padding.
+ * Refused with AVEXHIP_ERR_INVALID before anything is launched, the message naming the window: a recording that leaves wav_dev, valid
+ * outside 0 .. window_len, a window that leaves its recording.  stats and an indexed gather check the whole table, a contiguous gather
+ * the windows it reads.  No kernel reads outside [base, base + n_samples) of a window's recording. */
+typedef struct {
+    int64_t base;            /* first sample of the window's recording in wav_dev, counted in floats */
+    int64_t n_samples;       /* length of that recording */
+    int64_t start;           /* first sample of the window, counted inside the recording */
+    int32_t valid;           /* samples the window holds, <= window_len; the rest of its row is padding */
+    int32_t reserved;        /* 0 */
+} avexhip_window;
+int avexhip_window_stats(const float* wav_dev, int64_t wav_samples, const avexhip_window* win_host, const avexhip_window* win_dev, int n_win,
+                         int window_len, double* energy_dev, float* peak_dev, void* stream);
+int avexhip_window_select(const avexhip_window* win_dev, const double* energy_dev, const float* peak_dev, int n_win, double thr_energy,
+                          float thr_peak, int32_t* kept_dev, int32_t* count_dev, void* stream);
+int avexhip_window_gather(const float* wav_dev, int64_t wav_samples, const avexhip_window* win_host, const avexhip_window* win_dev, int n_win,
+                          const int32_t* index_dev, int first, int B, int window_len, float* out_dev, int64_t out_stride, uint8_t* mask_dev,
+                          void* stream);
 
 /* FLAC decode (the reference reads its .flac samples through torchaudio.load / soundfile: augmentations.py:258-262,
  * tests/samples/animalspeak2/16khz).  avexhip_flac_open parses a whole stream held in host memory -- metadata, frame and
