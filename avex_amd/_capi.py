@@ -110,6 +110,20 @@ class Window(C.Structure):
     _fields_ = [("base", C.c_int64), ("n_samples", C.c_int64), ("start", C.c_int64), ("valid", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SearchArgs(C.Structure):
+    _fields_ = [("query", C.c_void_p), ("ld_query", C.c_int64), ("nb", C.c_int32), ("d", C.c_int32), ("batch", C.c_int32), ("k", C.c_int32),
+                ("chunk_rows", C.c_int32), ("normalise", C.c_int32), ("stages", C.c_int32), ("exclude", C.c_int32), ("chunk", C.c_void_p),
+                ("row0", C.c_int64), ("n_rows", C.c_int32), ("reserved", C.c_int32), ("skip_row", C.c_void_p), ("query_recording", C.c_void_p),
+                ("query_start", C.c_void_p), ("query_end", C.c_void_p), ("db_recording", C.c_void_p), ("db_start", C.c_void_p),
+                ("db_end", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("sim_out", C.c_void_p), ("ld_sim", C.c_int64)]
+
+
+class SearchResult(C.Structure):
+    _fields_ = [("k", C.c_int32), ("nms", C.c_int32), ("max_overlap", C.c_double), ("n_rows", C.c_int64), ("db_recording", C.c_void_p),
+                ("db_start", C.c_void_p), ("db_end", C.c_void_p), ("scores", C.c_void_p), ("rows", C.c_void_p), ("count", C.c_void_p),
+                ("recording", C.c_void_p), ("start_s", C.c_void_p), ("end_s", C.c_void_p)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -232,6 +246,12 @@ SYMBOLS = {
     "avexhip_retrieval_prepare": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "avexhip_retrieval_batch": (C.c_int, [C.POINTER(RetrievalArgs), _P]),
     "avexhip_retrieval_finalize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "avexhip_search_max_k": (C.c_int, []),
+    "avexhip_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "avexhip_search_prepare_rows": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "avexhip_search_begin": (C.c_int, [C.POINTER(SearchArgs), _P]),
+    "avexhip_search_chunk": (C.c_int, [C.POINTER(SearchArgs), _P]),
+    "avexhip_search_finish": (C.c_int, [C.POINTER(SearchArgs), C.POINTER(SearchResult), _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

@@ -1,6 +1,6 @@
 // The fp32 product of the evaluation metrics: a 128 x 128 x 32 tile of A B^T on v_mfma_f32_32x32x2_f32 (fp32 operands, one rounding per
-// product), shared by retr_sim_kernel (retrieval.hip) and clus_assign_kernel (clustering.hip), with the small helpers both files use
-// around it.  Not for the f16 GEMM or the attention kernels: their tiles and staging differ.
+// product), shared by retr_sim_kernel (retrieval.hip), srch_sim_kernel (search.hip) and clus_assign_kernel (clustering.hip), with the small
+// helpers those files use around it.  Not for the f16 GEMM or the attention kernels: their tiles and staging differ.
 #pragma once
 #include "common.h"
 
@@ -111,6 +111,51 @@ static __device__ __forceinline__ int f32_tile_row(int i, int reg) {
 static __device__ __forceinline__ int f32_tile_col(int j) {
     const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
     return wc * 64 + j * 32 + (lane & 31);
+}
+
+// The bodies of the two kernels that retrieval.hip and search.hip both run, written once so that "the same arithmetic" is the same code.
+//
+// Rows for the product, one wave per row and 4 rows per workgroup of 256 threads: out[row] = dpad floats, zero beyond d; divided by
+// max(||row||_2, 1e-12) in fp32 when `normalise`, copied when not.
+static __device__ __forceinline__ void f32_prepare_rows(const float* __restrict__ x, int64_t ldx, int n, int d, int dpad, bool normalise,
+                                                        float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float* r = x + (int64_t)row * ldx;
+    if (!normalise) {
+        float* o = out + (int64_t)row * dpad;
+        for (int c = lane; c < dpad; c += 64) o[c] = c < d ? r[c] : 0.f;
+        return;
+    }
+    float ss = 0.f;
+    for (int c = lane; c < d; c += 64) ss = __builtin_fmaf(r[c], r[c], ss);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) ss += __shfl_xor(ss, s);
+    float nrm = __builtin_sqrtf(ss);
+    nrm = nrm < 1e-12f ? 1e-12f : nrm;
+    float* o = out + (int64_t)row * dpad;
+    for (int c = lane; c < dpad; c += 64) o[c] = c < d ? r[c] / nrm : 0.f;
+}
+
+// S[q][n] = Q[q] . D[n] for the 128 x 128 tile (blockIdx.y, blockIdx.x) of q in [0, nq), n in [0, nd): f32_tile_product with a store.  Q and
+// D are prepared rows of dpad floats; S has lds_ floats per row.  The launch needs FT_LDS_BYTES of dynamic LDS.
+static __device__ __forceinline__ void f32_tile_store_product(const float* __restrict__ Q, int nq, const float* __restrict__ D, int nd, int dpad,
+                                                              float* __restrict__ S, int64_t lds_) {
+    const int n0 = blockIdx.x * FT_BN, q0 = blockIdx.y * FT_BM;
+    f32x16 acc[2][2];
+    f32_tile_product(Q, nq, q0, D, nd, n0, dpad, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + f32_tile_col(j);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int q = q0 + f32_tile_row(i, r);
+                if (q < nq && n < nd) S[(int64_t)q * lds_ + n] = acc[i][j][r];
+            }
+        }
 }
 
 }  // namespace

@@ -23,19 +23,9 @@ constexpr int RETR_MAX_DB = 1 << 19;               // relevance bits of one row:
 static inline int64_t ldsim_of(int64_t n_db) { return (n_db + 63) / 64 * 64; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// rows / max(||row||_2, 1e-12): f32_prepare_rows (f32_tile.h), which search.hip runs too
 __global__ __launch_bounds__(256) void retr_normalize_kernel(const float* __restrict__ x, int64_t ldx, int n, int d, int dpad, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    const float* r = x + (int64_t)row * ldx;
-    float ss = 0.f;
-    for (int c = lane; c < d; c += 64) ss = __builtin_fmaf(r[c], r[c], ss);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    float nrm = __builtin_sqrtf(ss);
-    nrm = nrm < 1e-12f ? 1e-12f : nrm;
-    float* o = out + (int64_t)row * dpad;
-    for (int c = lane; c < dpad; c += 64) o[c] = c < d ? r[c] / nrm : 0.f;
+    f32_prepare_rows(x, ldx, n, d, dpad, true, out);
 }
 
 __global__ __launch_bounds__(256) void retr_pack_kernel(const uint8_t* __restrict__ hot, int n, int c, int n_words, unsigned long long* __restrict__ words) {
@@ -51,23 +41,10 @@ __global__ __launch_bounds__(256) void retr_pack_kernel(const uint8_t* __restric
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // S[q][n] for q in [0, nq), n in [0, nd): Q and D are normalised rows of dpad floats (dpad % 32 == 0, zero beyond d).  The product is
-// f32_tile_product (f32_tile.h); this kernel adds the store.
+// f32_tile_product with a store: f32_tile_store_product (f32_tile.h), which search.hip runs too.
 __global__ __launch_bounds__(256) void retr_sim_kernel(const float* __restrict__ Q, int nq, const float* __restrict__ D, int nd, int dpad,
                                                         float* __restrict__ S, int64_t lds_) {
-    const int n0 = blockIdx.x * FT_BN, q0 = blockIdx.y * FT_BM;
-    f32x16 acc[2][2];
-    f32_tile_product(Q, nq, q0, D, nd, n0, dpad, acc);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + f32_tile_col(j);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int q = q0 + f32_tile_row(i, r);
-                if (q < nq && n < nd) S[(int64_t)q * lds_ + n] = acc[i][j][r];
-            }
-        }
+    f32_tile_store_product(Q, nq, D, nd, dpad, S, lds_);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 14
+#define AVEXHIP_ABI_VERSION 15
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -463,6 +463,79 @@ int avexhip_retrieval_batch(const avexhip_retrieval_args* args, void* stream);
  * number, sum of precision@k, its number (retrieval.py:262-284, 386-399, 470-486, 640-660 for who is valid). */
 int avexhip_retrieval_finalize(const int64_t* u2_dev, const int32_t* stats_dev, int n_query, int self_set, int k, double* out_dev,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Query-by-example search (ABI 15): the exact top-k of a query batch against embeddings that are already on the device, with scores,
+ * for an index of any size that fits in HBM.  The database is a list of chunks of at most chunk_rows rows, each a buffer of rows
+ * prepared once by avexhip_search_prepare_rows: dpad = ceil(d / 32) * 32 floats per row, zero beyond d, divided by max(||row||, 1e-12)
+ * (normalise = 1, cosine; the arithmetic of avexhip_retrieval_prepare) or copied (normalise = 0, dot product).  A search walks the chunks:
+ *   1. avexhip_search_begin   prepares the batch's query rows into the workspace and empties its running lists;
+ *   2. avexhip_search_chunk   one call per chunk, in any order: similarities of the batch against the chunk on the fp32 MFMA (a
+ *                             similarity depends on its two rows only, not on the chunk, the batch or the tile it falls in), then per
+ *                             query the running list of the k best keys merged with them.  key = (mono32(sim + 0.0f) << 32) |
+ *                             (0xFFFFFFFF - global row): higher similarity first, then lower row; keys are unique, so the list after
+ *                             the last chunk is one set in one order whatever the chunking.  A column is dropped when its similarity
+ *                             is NaN, when it is the query's skip_row, or under the exclusion rule: exclude = 1 drops the rows of the
+ *                             query's recording (>= 0), exclude = 2 those of them whose span overlaps the query's by a positive amount,
+ *                             min(end) > max(start).  Selection is a radix select on the key (O(rows) per pass, at most 8 passes) and
+ *                             a sort of the k survivors: no cost but the sort grows with k.
+ *   3. avexhip_search_finish  lists -> scores (the similarity's bits, -0 folded onto +0), rows, the hits' recording / start / end; past
+ *                             count[b]: -inf, -1, -1, NaN, NaN.  With nms = 1 the lists hold k' >= k candidates and a greedy pass
+ *                             takes them best first: a candidate falls when a hit already kept has its recording (>= 0) and
+ *                             min(end) - max(start) > max_overlap * min(length_a, length_b), all in fp64 with each side of the compare
+ *                             rounded on its own; it stops at k kept hits.  In both rules min and max carry a NaN span as NumPy's
+ *                             do, and every compare with it is false: a row with a recording and no span takes part in neither.
+ * Working memory is O(batch x chunk_rows + batch x k) and does not depend on the number of indexed rows.  Nothing here allocates or
+ * synchronises; no float atomics, no global atomics: a search is bit-reproducible.  k <= 1024, fewer than 2^31 rows.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float* query;             /* begin: [nb, d] fp32 rows of this batch (row stride ld_query) */
+    int64_t ld_query;
+    int32_t nb;                     /* queries in this batch, 1 .. batch */
+    int32_t d, batch, k, chunk_rows; /* as given to avexhip_search_workspace_bytes; k = depth of the running lists, 1 .. 1024 */
+    int32_t normalise;              /* begin: 1 = divide the query rows by their norm (cosine), 0 = copy them (dot; rows already prepared) */
+    int32_t stages;                 /* chunk: 0 or 3: similarity + select; 1: similarity only; 2: select only (of the similarities in the workspace) */
+    int32_t exclude;                /* chunk: 0 none, 1 the query's recording, 2 rows of it that overlap the query's span */
+    const float* chunk;             /* chunk: [n_rows, dpad] prepared rows */
+    int64_t row0;                   /* chunk: global row of the chunk's first row */
+    int32_t n_rows;                 /* chunk: rows the chunk holds, 1 .. chunk_rows */
+    int32_t reserved;
+    const int64_t* skip_row;        /* chunk: [nb] global row never returned to query b (-1: none), or NULL */
+    const int32_t* query_recording; /* chunk: [nb] (exclude >= 1); -1 = no recording, nothing excluded */
+    const double* query_start;      /* chunk: [nb] seconds (exclude == 2) */
+    const double* query_end;
+    const int32_t* db_recording;    /* chunk: [n_rows] of this chunk's rows (exclude >= 1) */
+    const double* db_start;         /* chunk: [n_rows] (exclude == 2) */
+    const double* db_end;
+    void* workspace;
+    size_t workspace_bytes;
+    float* sim_out;                 /* chunk: optional [nb, n_rows] copy of the similarities (row stride ld_sim), for tests */
+    int64_t ld_sim;
+} avexhip_search_args;
+
+typedef struct {
+    int32_t k;                      /* hits per query, 1 .. the depth of the lists (equal to it when nms = 0) */
+    int32_t nms;                    /* 1: greedy temporal suppression over the lists' candidates */
+    double max_overlap;             /* [0, 1) */
+    int64_t n_rows;                 /* rows of the whole index: the length of the three arrays below */
+    const int32_t* db_recording;    /* [n_rows] recording of every indexed row, -1 = none; NULL: no metadata at all */
+    const double* db_start;         /* [n_rows] seconds */
+    const double* db_end;
+    float* scores;                  /* out [nb, k] */
+    int64_t* rows;                  /* out [nb, k] */
+    int32_t* count;                 /* out [nb] */
+    int32_t* recording;             /* out [nb, k] */
+    double* start_s;                /* out [nb, k] */
+    double* end_s;                  /* out [nb, k] */
+} avexhip_search_result;
+
+int avexhip_search_max_k(void);         /* 1024 */
+size_t avexhip_search_workspace_bytes(int64_t chunk_rows, int d, int batch, int k);      /* 0 for a bad shape; no database size */
+/* rows_dev [n, d] fp32 (row stride ld_rows) -> out_dev [n, dpad]: database rows into their chunk, or query rows */
+int avexhip_search_prepare_rows(const float* rows_dev, int64_t ld_rows, int n, int d, int normalise, float* out_dev, void* stream);
+int avexhip_search_begin(const avexhip_search_args* args, void* stream);
+int avexhip_search_chunk(const avexhip_search_args* args, void* stream);
+int avexhip_search_finish(const avexhip_search_args* args, const avexhip_search_result* result, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Clustering metrics (ABI 11): what avex/evaluation/clustering.py computes from cached embeddings -- scikit-learn's
