@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from _attention_ref import attention_ref as _attention_ref, plain_attention_ref as _plain_attention_ref, toeplitz as _toeplitz
 from _util import max_abs, rel_l2, round_half
 from avex_amd import synth
 from oracle import beats_oracle as O
@@ -368,37 +369,6 @@ def test_mean_pool(built_lib):
     assert max_abs(out, x.mean(axis=1, dtype=np.float64)) < 1e-6
 
 
-def _attention_ref(qkv, B, T, H, table, gw, gb, ga, key_pad=None):
-    E = H * 64
-    q, k, v = [qkv[:, i * E:(i + 1) * E].reshape(B, T, H, 64).transpose(0, 2, 1, 3).astype(np.float64) for i in range(3)]
-    s = q @ k.transpose(0, 1, 3, 2) * 0.125
-    if table is not None:
-        bias = O.position_bias(table, T, table.shape[0], 800 if table.shape[0] == 320 else 64).astype(np.float64)
-        if gw is not None:
-            g8 = q @ gw.T.astype(np.float64) + gb
-            g2 = g8.reshape(B, H, T, 2, 4).sum(-1)
-            sg = 1.0 / (1.0 + np.exp(-g2))
-            gate = sg[..., 0:1] * (sg[..., 1:2] * ga.reshape(1, H, 1, 1) - 1.0) + 2.0
-            s = s + gate * bias[None]
-        else:
-            s = s + bias[None]
-    if key_pad is not None:
-        s = np.where(key_pad[:, None, None, :], -np.inf, s)
-    s = s - s.max(-1, keepdims=True)
-    e = np.exp(s)
-    o = (e / e.sum(-1, keepdims=True)) @ v
-    return o.transpose(0, 2, 1, 3).reshape(B * T, E)
-
-
-def _toeplitz(table, T, nb, md):
-    from avex_amd import kernels as K
-    H = table.shape[1]
-    tab = np.empty((H, 2 * T - 1), np.float32)
-    for r in range(2 * T - 1):
-        tab[:, r] = table[K.rel_bucket(r - (T - 1), nb, md)]
-    return tab
-
-
 @pytest.mark.parametrize("variant", ["1", "2", "3"])
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("T", [496, 48, 384, 33, 512, 1, 17, 257, 300])
@@ -417,18 +387,6 @@ def test_attention(built_lib, dtype, T, variant, monkeypatch):
     # f16 ~ 2^-11 per element, bf16 ~ 2^-8
     tol = 1.5e-3 if dtype == "f16" else 1.2e-2
     assert rel_l2(out.float().cpu().numpy(), ref) < tol
-
-
-def _plain_attention_ref(qkv, B, T, H, D, key_pad=None):
-    E = H * D
-    q, k, v = [qkv[:, i * E:(i + 1) * E].reshape(B, T, H, D).transpose(0, 2, 1, 3).astype(np.float64) for i in range(3)]
-    s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(D)
-    if key_pad is not None:
-        s = np.where(key_pad[:, None, None, :], -np.inf, s)
-    s = s - s.max(-1, keepdims=True)
-    e = np.exp(s)
-    o = (e / e.sum(-1, keepdims=True)) @ v
-    return o.transpose(0, 2, 1, 3).reshape(B * T, E)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
