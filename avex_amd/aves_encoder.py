@@ -18,7 +18,6 @@ behind a URL; the checker is ``oracle/aves_oracle.py`` on
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Iterable, List, Mapping, Optional, Sequence
 
 import numpy as np
@@ -50,7 +49,7 @@ def conv_frame_plan(T: int, convs: Sequence[Sequence[int]]):
         pad += 1
 
 
-class AvesEncoder:
+class AvesEncoder(K.ResidualPairHandle):
     """``[B, T]`` fp32 waveforms on the GPU -> last-layer features ``[B, T', 768]`` / hook taps / pooled embeddings.
     A thin wrapper over the ``avexhip_aves`` handle (csrc/encoders.cpp): the library owns the weights, this class the output tensors
     and the workspace."""
@@ -62,9 +61,7 @@ class AvesEncoder:
         hooks return, aves_model.py:129-150), the operand-type stream for token-mean outputs only.  Two library handles then, each built
         on first use."""
         _capi.require_gpu()
-        self.residual = str(residual or "auto").lower()
-        if self.residual != "auto":
-            K.residual_code(self.residual)      # validates
+        self._set_residual(residual)
         self.cfg = dict(cfg)
         self.dtype = operand_dtype
         self.convs = [tuple(int(v) for v in c) for c in cfg["extractor_conv_layer_config"]]
@@ -82,31 +79,9 @@ class AvesEncoder:
             c.conv_kernel[i], c.conv_stride[i] = k, st
         c.operand_dtype = _capi.dtype_code(operand_dtype)
         c.max_chunk_clips = int(max_chunk_clips)
-        self._c, self._batch_invariant = c, bool(batch_invariant)
-        self._sub = {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)} if prefix else dict(state)
-        self._handles: Dict[str, int] = {}      # residual mode ("half" / "f32") -> library handle
-        self._profiling = False
-        self._h = self._handle_for(frames=self.residual in ("auto", "f32", "fp32", "float32"))      # a bad checkpoint fails here, not in the first forward
-        self._ws: Optional[torch.Tensor] = None
+        self._open("aves", c, {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)} if prefix else dict(state), batch_invariant)
         self._state, self._prefix = state, prefix
         self._conv_weights = None
-
-    def _handle_for(self, frames: bool) -> int:
-        """The handle whose residual stream this call wants (``frames``: it returns un-averaged rows); ``self._h`` = the last one used."""
-        mode = ("f32" if frames else "half") if self.residual == "auto" else ("half" if K.residual_code(self.residual) & 1 else "f32")
-        h = self._handles.get(mode)
-        if h is None:
-            self._c.residual_dtype = K.residual_code(mode, self._batch_invariant)
-            arr, n, keep = K.tensor_table(self._sub)
-            h = _capi.lib().avexhip_aves_create(C.byref(self._c), arr, n)
-            del keep
-            if not h:
-                raise K.AvexHipError(f"aves_create failed: {_capi.last_error()}")
-            self._handles[mode] = h
-            if self._profiling:
-                _capi.check(_capi.lib().avexhip_aves_set_profiling(h, 1), "aves_set_profiling")
-        self._h = h
-        return h
 
     def num_tokens(self, T: int) -> int:
         return conv_frame_plan(T, self.convs)[0][-1]
@@ -152,19 +127,13 @@ class AvesEncoder:
         E = self.E
         hook_layers = list(hook_layers)
         self._handle_for(frames=bool(want_features or (hook_layers and K.pool_code(hook_pooled) != 1)))      # anything but token means
-        need = int(_capi.lib().avexhip_aves_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        hooks: Dict[int, torch.Tensor] = {}
-        ptrs = (C.c_void_p * max(self.L, 1))()
-        mask = 0
-        for i in sorted(set(int(x) for x in hook_layers)):
+        ws = self._workspace(int(_capi.lib().avexhip_aves_workspace_bytes(self._h, B, T)), dev)
+        hook_layers = sorted(set(int(x) for x in hook_layers))
+        for i in hook_layers:
             if not 0 <= i < self.L:
                 raise ValueError(f"hook layer {i} out of range 0..{self.L - 1}")
-            hooks[i] = torch.empty((B, E) if K.pool_code(hook_pooled) else (B, Tt, E), dtype=torch.float32, device=dev)      # sized by the code the library gets
-            ptrs[i] = int(hooks[i].data_ptr())
-            mask |= 1 << i
+        shape = (B, E) if K.pool_code(hook_pooled) else (B, Tt, E)      # sized by the code the library gets
+        hooks, ptrs, mask = self.hook_buffers(hook_layers, self.L, lambda i: shape, dev)
         feats = torch.empty((B, Tt, E), dtype=torch.float32, device=dev) if want_features else None
         pooled = torch.empty((B, E), dtype=torch.float32, device=dev) if want_pooled else None
         pad = None
@@ -173,39 +142,10 @@ class AvesEncoder:
             if pad.shape != (B, Tt):
                 raise ValueError(f"frame_pad must be [B={B}, T'={Tt}], got {tuple(pad.shape)}")
         _capi.check(_capi.lib().avexhip_aves_forward(self._h, K._ptr(wav), B, T, wav.stride(0), K._ptr(pad), mask, ptrs, K.pool_code(hook_pooled), K._ptr(feats),
-                                                     K._ptr(pooled), K._ptr(self._ws), self._ws.numel(), K._stream()), "aves_forward")
+                                                     K._ptr(pooled), K._ptr(ws), ws.numel(), K._stream()), "aves_forward")
         out: Dict[str, object] = {"hooks": hooks}
         if want_features:
             out["features"] = feats
         if want_pooled:
             out["pooled"] = pooled
         return out
-
-    def overflow_events(self, sync: bool = True) -> int:
-        total = 0
-        for h in self._handles.values():
-            n = C.c_uint32(0)
-            _capi.check(_capi.lib().avexhip_aves_overflow_count(h, C.byref(n), K._stream(), int(bool(sync))), "aves_overflow_count")
-            total += int(n.value)
-        return total
-
-    def set_profiling(self, enabled: bool) -> None:
-        self._profiling = bool(enabled)
-        for h in self._handles.values():
-            _capi.check(_capi.lib().avexhip_aves_set_profiling(h, int(enabled)), "aves_set_profiling")
-
-    def last_profile(self):
-        return K.handle_profile(_capi.lib().avexhip_aves_last_profile, self._h)
-
-    def close(self) -> None:
-        for h in getattr(self, "_handles", {}).values():
-            _capi.lib().avexhip_aves_destroy(h)
-        self._handles = {}
-        self._h = None
-        self._ws = None
-
-    def __del__(self) -> None:
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass

@@ -172,56 +172,25 @@ using avxh::Table;
 
 namespace {
 
-// window / mel bank as the reference builds them (beats.py:75,82-118), fp32 arithmetic
+// BEATs' Povey window (beats.py:75): the shared Hann window to the power 0.85, fp32
 void default_window(int win, std::vector<float>& w) {
-    w.resize(win);
-    for (int n = 0; n < win; ++n) {
-        // torch.hann_window(periodic=False) op for op in fp32
-        const float hann = cosf((float)n * (float)(M_PI * 2.0 / (double)(win - 1))) * -0.5f + 0.5f;
-        w[n] = powf(hann, 0.85f);
-    }
-}
-void default_mel(int n_fft, int n_mels, float sr, float low, float high, std::vector<float>& fb) {
-    const int nb = n_fft / 2;
-    const float bin_w = sr / (float)n_fft;
-    const float mel_low = (float)(1127.0 * log(1.0 + (double)low / 700.0));
-    const float mel_high = (float)(1127.0 * log(1.0 + (double)high / 700.0));
-    const float delta = (float)(((double)mel_high - (double)mel_low) / (double)(n_mels + 1));
-    fb.assign((size_t)(nb + 1) * n_mels, 0.f);
-    for (int m = 0; m < n_mels; ++m) {
-        const float left = mel_low + (float)m * delta;
-        const float center = mel_low + ((float)m + 1.0f) * delta;
-        const float right = mel_low + ((float)m + 2.0f) * delta;
-        for (int k = 0; k < nb; ++k) {
-            const float f = bin_w * (float)k;
-            const float mel = 1127.0f * logf(1.0f + f / 700.0f);
-            const float up = (mel - left) / (center - left);
-            const float down = (right - mel) / (right - center);
-            const float v = fmaxf(0.f, fminf(up, down));
-            fb[(size_t)k * n_mels + m] = v;
-        }
-    }
+    avxh::hann_window(win, w);
+    for (float& v : w) v = powf(v, 0.85f);
 }
 
 }  // namespace
 
 struct avexhip_beats : avxh::HandleBase {
     avexhip_beats_config cfg;
-    int E = 0, F = 0, H = 0, L = 0, D = 0, P = 0, NM = 0, chunk = 256;
-    bool fast = false;   // residual stream / pre-LN sums in the operand type
-    bool batch_invariant = false;  // residual_dtype bit 1: see CoreCfg::batch_invariant
-    bool ln_fold = false;  // fast mode: LayerNorms between the GEMMs folded into their epilogues
-    int ln_fold_min_rows = 0;   // ... for chunks of at least this many rows (avxh::fold_policy)
+    CoreCfg core;        // the layer loop's parameters (E, F, H, L, DeepNorm alpha, residual mode, fold, activation ...), fixed at creation
+    int D = 0, P = 0, NM = 0, chunk = 256;
     int nstreams = 1;    // chunks of one forward run concurrently on this many streams (caller's + side streams)
     bool capturing = false;    // a forward being recorded into a hipGraph: one lane, no lazily created objects
     bool fe_in_lane = true;    // frontend of a chunk on the chunk's own lane stream (AVEX_AMD_FRONTEND_IN_LANE=0: all frontends before the fork)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-    float alpha = 1.f;
     avexhip_fbank_plan* fb = nullptr;
     void* w_patch = nullptr; float* b_patch = nullptr;      // b_patch: conv_bias=True (beats.py:263-269), else NULL
-    bool pre_ln = false; int act = 1; bool glu = false;     // layer_norm_first / activation_fn of the config (CoreCfg)
-    int hidden_shift = 0;                                   // avexhip_beats_config::hidden_shift (CoreCfg)
     float* ln0_w = nullptr; float* ln0_b = nullptr;
     void* w_post = nullptr; float* b_post = nullptr;
     void* w_pc = nullptr; float* b_pc = nullptr;
@@ -242,12 +211,6 @@ struct avexhip_beats : avxh::HandleBase {
     std::map<int, BiasTab> bias_tabs;
     std::mutex bias_mu;
 
-    CoreCfg core() const {
-        CoreCfg c;
-        c.E = E; c.F = F; c.H = H; c.L = L; c.alpha = alpha; c.eps = 1e-5f; c.hook_site = 0; c.fast = fast; c.fold = ln_fold;
-        c.fold_min_rows = ln_fold_min_rows; c.batch_invariant = batch_invariant; c.act = act; c.glu = glu; c.hidden_shift = hidden_shift; c.pre_ln = pre_ln; c.final_ln_w = lnE_w; c.final_ln_b = lnE_b;
-        return c;
-    }
     ~avexhip_beats() override {
         for (auto& kv : bias_tabs) if (kv.second.ready) (void)hipEventDestroy(kv.second.ready);
         if (bias_arena) (void)hipFree(bias_arena);
@@ -270,9 +233,7 @@ const avxh::LayerNames BEATS_NAMES = {nullptr, "encoder.layers.%d.self_attn.q_pr
 int build(avexhip_beats* h, const avexhip_tensor* tensors, int n) {
     const avexhip_beats_config& c = h->cfg;
     const Table tb{tensors, n};
-    const int E = h->E, F = h->F, H = h->H, D = h->D, P = h->P;
-    int rc;
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
+    const int E = h->core.E, H = h->core.H, L = h->core.L, D = h->D, P = h->P;
 
     // frontend plan: the checkpoint's persistent buffers when present, else the reference's formulas
     {
@@ -292,7 +253,7 @@ int build(avexhip_beats* h, const avexhip_tensor* tensors, int n) {
             hm.resize((size_t)257 * c.num_mel_bins);
             AVX_HIP_CHECK(hipMemcpy(hm.data(), tm->data, sizeof(float) * hm.size(), hipMemcpyDefault));
         } else {
-            default_mel(512, c.num_mel_bins, c.sample_frequency, 20.0f, c.sample_frequency / 2.0f, hm);
+            avxh::kaldi_mel(512, c.num_mel_bins, c.sample_frequency, 20.0f, c.sample_frequency / 2.0f, hm);
         }
         avexhip_fbank_config fc;
         fc.win_length = win; fc.hop_length = hop; fc.n_mels = c.num_mel_bins;
@@ -302,34 +263,25 @@ int build(avexhip_beats* h, const avexhip_tensor* tensors, int n) {
         if (!h->fb) return AVEXHIP_ERR_HIP;
     }
 
-    RC(dev_half(h, tb, "patch_embedding.weight", (int64_t)D * P * P, &h->w_patch));
-    if (c.conv_bias) RC(dev_f32(h, tb, "patch_embedding.bias", D, &h->b_patch));
-    RC(dev_f32(h, tb, "layer_norm.weight", D, &h->ln0_w));
-    RC(dev_f32(h, tb, "layer_norm.bias", D, &h->ln0_b));
+    AVXH_TRY(dev_half(h, tb, "patch_embedding.weight", (int64_t)D * P * P, &h->w_patch));
+    if (c.conv_bias) AVXH_TRY(dev_f32(h, tb, "patch_embedding.bias", D, &h->b_patch));
+    AVXH_TRY(dev_f32(h, tb, "layer_norm.weight", D, &h->ln0_w));
+    AVXH_TRY(dev_f32(h, tb, "layer_norm.bias", D, &h->ln0_b));
     if (D != E || tb.find("post_extract_proj.weight")) {
-        RC(dev_half(h, tb, "post_extract_proj.weight", (int64_t)E * D, &h->w_post));
-        RC(dev_f32(h, tb, "post_extract_proj.bias", E, &h->b_post));
+        AVXH_TRY(dev_half(h, tb, "post_extract_proj.weight", (int64_t)E * D, &h->w_post));
+        AVXH_TRY(dev_f32(h, tb, "post_extract_proj.bias", E, &h->b_post));
     }
-    // positional conv: fold weight-norm and repack
-    {
-        const int K = c.conv_pos, G = c.conv_pos_groups, cg = E / G;
-        float *g = nullptr, *v = nullptr;
-        RC(dev_f32(h, tb, "encoder.pos_conv.0.parametrizations.weight.original0", K, &g));
-        RC(dev_f32(h, tb, "encoder.pos_conv.0.parametrizations.weight.original1", (int64_t)E * cg * K, &v));
-        AVX_HIP_CHECK(hipMalloc(&h->w_pc, 2 * (size_t)E * cg * K));
-        h->allocs.push_back(h->w_pc);
-        RC(avx::posconv_pack(g, v, E, G, K, h->w_pc, h->dtype, nullptr));
-        RC(dev_f32(h, tb, "encoder.pos_conv.0.bias", E, &h->b_pc));
-    }
-    RC(dev_f32(h, tb, "encoder.layer_norm.weight", E, &h->lnE_w));
-    RC(dev_f32(h, tb, "encoder.layer_norm.bias", E, &h->lnE_b));
+    AVXH_TRY(avxh::pack_posconv(h, tb, "encoder.pos_conv.0.parametrizations.weight.original0", "encoder.pos_conv.0.parametrizations.weight.original1",
+                                "encoder.pos_conv.0.bias", E, c.conv_pos_groups, c.conv_pos, &h->w_pc, &h->b_pc));
+    AVXH_TRY(dev_f32(h, tb, "encoder.layer_norm.weight", E, &h->lnE_w));
+    AVXH_TRY(dev_f32(h, tb, "encoder.layer_norm.bias", E, &h->lnE_b));
 
-    h->layers.resize(h->L);
+    h->core.final_ln_w = h->lnE_w; h->core.final_ln_b = h->lnE_b;
+    h->layers.resize(L);
     {
         avxh::LayerNames nm = BEATS_NAMES;
         if (!c.gru_rel_pos) { nm.grep_linear = nullptr; nm.grep_a = nullptr; }
-        const CoreCfg cc = h->core();
-        for (int i = 0; i < h->L; ++i) RC(avxh::build_layer(h, tb, nm, cc, h->layers, i));
+        for (int i = 0; i < L; ++i) AVXH_TRY(avxh::build_layer(h, tb, nm, h->core, h->layers, i));
     }
     // shared relative-position table (owned by layer 0, backbone.py:100-103)
     if (c.num_buckets > 0) {
@@ -368,14 +320,13 @@ int build(avexhip_beats* h, const avexhip_tensor* tensors, int n) {
         h->bias_arena_bytes = (size_t)arena_mb << 20;
         if (h->bias_arena_bytes) AVX_HIP_CHECK(hipMalloc((void**)&h->bias_arena, h->bias_arena_bytes));
     }
-#undef RC
     AVX_HIP_CHECK(hipDeviceSynchronize());
     return AVEXHIP_OK;
 }
 
 // [H, 2T-1] Toeplitz rows of compute_bias (backbone.py:475-492) for a forward on stream `s`: the arena's table of this token count (built
 // on `s` the first time it is asked for), or -- arena full -- a table built into `fallback` (the caller's workspace) for this forward only.
-size_t bias_tab_bytes(const avexhip_beats* h, int T) { return h->rel_table.empty() ? 0 : sizeof(float) * (size_t)h->H * (size_t)(2 * T - 1); }
+size_t bias_tab_bytes(const avexhip_beats* h, int T) { return h->rel_table.empty() ? 0 : sizeof(float) * (size_t)h->core.H * (size_t)(2 * T - 1); }
 
 int bias_tab_for(avexhip_beats* h, int T, hipStream_t s, float* fallback, float** out) {
     *out = nullptr;
@@ -405,7 +356,7 @@ int bias_tab_for(avexhip_beats* h, int T, hipStream_t s, float* fallback, float*
     if (use_arena && h->bias_arena_used + need <= h->bias_arena_bytes && !capturing()) {
         avexhip_beats::BiasTab e{(float*)(h->bias_arena + h->bias_arena_used), nullptr, s, false};
         AVX_HIP_CHECK(hipEventCreateWithFlags(&e.ready, hipEventDisableTiming));
-        const int rc = avx::bias_toeplitz(h->d_rel_table, h->d_bucket_lut, h->lut_maxd, T, h->H, e.ptr, s);
+        const int rc = avx::bias_toeplitz(h->d_rel_table, h->d_bucket_lut, h->lut_maxd, T, h->core.H, e.ptr, s);
         if (rc != AVEXHIP_OK) { (void)hipEventDestroy(e.ready); return rc; }
         AVX_HIP_CHECK(hipEventRecord(e.ready, s));
         h->bias_arena_used += need;
@@ -414,7 +365,7 @@ int bias_tab_for(avexhip_beats* h, int T, hipStream_t s, float* fallback, float*
         return AVEXHIP_OK;
     }
     AVX_REQUIRE(fallback, "beats_forward: no room for the relative position bias table (T=%d)", T);
-    const int rc = avx::bias_toeplitz(h->d_rel_table, h->d_bucket_lut, h->lut_maxd, T, h->H, fallback, s);
+    const int rc = avx::bias_toeplitz(h->d_rel_table, h->d_bucket_lut, h->lut_maxd, T, h->core.H, fallback, s);
     if (rc != AVEXHIP_OK) return rc;
     *out = fallback;
     return AVEXHIP_OK;
@@ -430,17 +381,17 @@ Ws carve(const avexhip_beats* h, char* base, int Bc, int Tt) {
     const size_t M = (size_t)Bc * Tt;
     const size_t PP = (size_t)h->P * h->P;
     Ws w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-    w.patches = take(M * PP * 2);
-    w.f0 = (float*)take(M * h->D * 4);
-    w.h0 = take(M * h->D * 2);
-    w.core = avxh::carve_core(h->core(), M, take);
-    w.total = off;
+    avxh::Carver cv{base};
+    w.patches = cv.take(M * PP * 2);
+    w.f0 = (float*)cv.take(M * h->D * 4);
+    w.h0 = cv.take(M * h->D * 2);
+    w.core = avxh::carve_core(h->core, M, cv);
+    w.total = cv.off;
     return w;
 }
 
-// how a batch is split: chunk size and number of concurrent lanes (streams)
+// how a batch is split: chunk size and number of concurrent lanes (streams).  BEATs' own, not encoders.cpp's chunk_for: the threshold is
+// 512 tokens (a 10 s clip has 496; chunk_for's 520 exists for EAT's 513), and only this handle spreads chunks over lanes
 void plan_chunks(const avexhip_beats* h, int B, int Tt, int* chunk, int* lanes) {
     // max_chunk_clips is sized for 10 s clips (<= 512 tokens); longer clips keep the same number of TOKEN rows per pass
     int cap = h->chunk;
@@ -459,13 +410,14 @@ void plan_chunks(const avexhip_beats* h, int B, int Tt, int* chunk, int* lanes) 
 int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int B, int64_t T, int64_t stride, int frames,
                  const uint8_t* frame_pad, uint32_t hook_mask, float* const* hook_out, int hook_pooled,
                  float* features_out, float* pooled_out, void* workspace, size_t ws_bytes, hipStream_t s) {
-    const int E = h->E, F = h->F, H = h->H, D = h->D, P = h->P, L = h->L, NM = h->NM, dt = h->dtype;
+    const int E = h->core.E, D = h->D, P = h->P, L = h->core.L, NM = h->NM, dt = h->dtype;
     const int nt = frames / P, nf = NM / P;
     const int Tt = nt * nf;
     AVX_REQUIRE(Tt >= 1, "beats_forward: input too short (%d frames -> 0 tokens)", frames);
     AVX_REQUIRE(hook_mask == 0 || hook_out, "beats_forward: hook_mask set but hook_out is NULL");
     AVX_REQUIRE(hook_pooled >= 0 && hook_pooled <= 3, "beats_forward: hook_pooled = %d (0 full taps, 1 mean, 2 max, 3 first token)", hook_pooled);
     AVX_REQUIRE((hook_mask >> (L + 1)) == 0, "beats_forward: hook_mask has bits beyond layer %d", L);
+    // (written out, not avxh::check_hooks: the hook_pooled and hook-0 refusals stand between the shared three, and their order is kept)
     // hook 0 is post_extract_proj's output; a model with embed_dim == encoder_embed_dim has no such layer (beats.py:357-358)
     AVX_REQUIRE(!(hook_mask & 1u) || h->w_post, "beats_forward: hook 0 (post_extract_proj) requested but this model has no post_extract_proj");
     for (int i = 0; i <= L; ++i)
@@ -474,18 +426,13 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
     plan_chunks(h, B, Tt, &chunk, &lanes);
     const Ws need = carve(h, nullptr, chunk, Tt);
     const size_t ws_need = need.total * (size_t)lanes + align_up(bias_tab_bytes(h, Tt));
-    if (!workspace || ws_bytes < ws_need) {
-        avexhip_set_error("beats_forward: workspace too small (%zu bytes given, %zu needed)", ws_bytes, ws_need);
-        return AVEXHIP_ERR_WORKSPACE;
-    }
+    AVXH_TRY(avxh::check_workspace("beats_forward", workspace, ws_bytes, ws_need));
     float* bias_fallback = bias_tab_bytes(h, Tt) ? (float*)((char*)workspace + need.total * (size_t)lanes) : nullptr;
     if (h->profiling || h->capturing) lanes = 1;   // per-kernel event timing needs the kernels alone on the device; a captured forward is one stream
     float* bias_tab = nullptr;
-    int rc = bias_tab_for(h, Tt, s, bias_fallback, &bias_tab);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(bias_tab_for(h, Tt, s, bias_fallback, &bias_tab));
     const avx::FbankDev* fbd = avexhip_fbank_plan_dev(h->fb);
     Prof prof{h, s};
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
 
     // Chunks are processed in rounds of `lanes`; each chunk's whole pipeline, frontend included, runs on its lane's stream.
     // (Round 1 kept the frontends in front of the fork because the FFT kernel computed wrong values beside another lane's GEMMs.
@@ -497,11 +444,11 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
         const double Md = (double)Bc * Tt;
         if (wav) {
             prof.begin("fbank", Md / Tt * frames * (5.0 * 512 * 9 + 2.0 * 504));
-            RC(avx::fbank(*fbd, wav + (size_t)c0 * stride, Bc, T, stride, frames, nullptr, w.patches, P, dt, fs));
+            AVXH_TRY(avx::fbank(*fbd, wav + (size_t)c0 * stride, Bc, T, stride, frames, nullptr, w.patches, P, dt, fs));
             prof.end();
         } else {
             prof.begin("patchify", 0.0);
-            RC(avx::patchify(fbank_in + (size_t)c0 * frames * NM, Bc, frames, NM, P, w.patches, dt, fs));
+            AVXH_TRY(avx::patchify(fbank_in + (size_t)c0 * frames * NM, Bc, frames, NM, P, w.patches, dt, fs));
             prof.end();
         }
         return AVEXHIP_OK;
@@ -512,7 +459,7 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
             const int c0 = r0 + li * chunk;
             if (c0 >= B) break;
             const int Bc = (B - c0) < chunk ? (B - c0) : chunk;
-            RC(frontend(c0, Bc, carve(h, (char*)workspace + (size_t)li * need.total, chunk, Tt), s));
+            AVXH_TRY(frontend(c0, Bc, carve(h, (char*)workspace + (size_t)li * need.total, chunk, Tt), s));
         }
     }
     if (lanes > 1) {
@@ -532,53 +479,53 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
         const Ws w = carve(h, (char*)workspace + (size_t)lane_id * need.total, chunk, Tt);
         const uint8_t* pad = frame_pad ? frame_pad + (size_t)c0 * Tt : nullptr;
         const double Md = (double)M;
-        if (h->fe_in_lane) RC(frontend(c0, Bc, w, cs));
+        if (h->fe_in_lane) AVXH_TRY(frontend(c0, Bc, w, cs));
 
         // 2. patch embedding (Conv2d as GEMM) -> LayerNorm(D) -> post_extract_proj
         // "fast" keeps the residual stream (post-LN x) and the pre-LN sums in the operand type between
         // kernels; otherwise they are fp32.  x32 / pre32 / preh below are NULL when unused.
-        const bool fast = h->fast;
+        const bool fast = h->core.fast;
         float* x32 = w.core.x;                       // fp32 x (precise mode; in fast mode only hook 0 / final output scratch)
         float* pre32 = fast ? nullptr : w.core.pre;
         void* preh = fast ? w.core.preh : nullptr;
         const bool hook0 = (hook_mask & 1u) != 0;
         avx::GemmArgs g;
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        avxh::gemm_init(g, h);
         g.A = w.patches; g.lda = P * P; g.W = h->w_patch; g.ldw = P * P; g.M = M; g.N = D; g.K = P * P; g.bias = h->b_patch;
         if (fast) { g.out_half = w.h0; g.ldh = D; } else { g.out_f32 = w.f0; g.ldo = D; }
         prof.begin("gemm.patch_embed", 2.0 * Md * D * P * P);
-        RC(avx::gemm(g, dt, cs));
+        AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
         prof.begin("layernorm", 0.0);
         if (h->w_post) {
-            RC(avx::layernorm(fast ? nullptr : w.f0, fast ? w.h0 : nullptr, D, h->ln0_w, h->ln0_b, 1e-5f, M, D, nullptr, D, w.h0, D, dt, cs));
+            AVXH_TRY(avx::layernorm(fast ? nullptr : w.f0, fast ? w.h0 : nullptr, D, h->ln0_w, h->ln0_b, 1e-5f, M, D, nullptr, D, w.h0, D, dt, cs));
         } else {   // embed_dim == encoder_embed_dim: the LayerNorm output is x itself; padded tokens are zeroed here (backbone.py:169-170)
-            RC(avx::layernorm(fast ? nullptr : w.f0, fast ? w.h0 : nullptr, D, h->ln0_w, h->ln0_b, 1e-5f, M, D, fast ? nullptr : x32, E, w.core.xh, E, dt, cs));
-            RC(avx::zero_rows(fast ? nullptr : x32, E, w.core.xh, E, M, E, pad, cs));
+            AVXH_TRY(avx::layernorm(fast ? nullptr : w.f0, fast ? w.h0 : nullptr, D, h->ln0_w, h->ln0_b, 1e-5f, M, D, fast ? nullptr : x32, E, w.core.xh, E, dt, cs));
+            AVXH_TRY(avx::zero_rows(fast ? nullptr : x32, E, w.core.xh, E, M, E, pad, cs));
         }
         prof.end();
         if (h->w_post) {
-            memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+            avxh::gemm_init(g, h);
             g.A = w.h0; g.lda = D; g.W = h->w_post; g.ldw = D; g.M = M; g.N = E; g.K = D; g.bias = h->b_post;
             g.out_half = w.core.xh; g.ldh = E; g.row_zero = pad;
             if (!fast || hook0) { g.out_f32 = x32; g.ldo = E; }
             prof.begin("gemm.post_extract_proj", 2.0 * Md * E * D);
-            RC(avx::gemm(g, dt, cs));
+            AVXH_TRY(avx::gemm(g, dt, cs));
             prof.end();
         }
         if (hook0 && h->w_post) {
             // the reference's hook holds the tensor that the encoder then zeroes in place at padded tokens
             // (beats.py:359-361 + backbone.py:169-170), so the tap equals x after masking
-            if (hook_pooled) RC(avx::agg_pool(x32, Bc, Tt, E, hook_pooled, hook_out[0] + (size_t)c0 * E, cs));
+            if (hook_pooled) AVXH_TRY(avx::agg_pool(x32, Bc, Tt, E, hook_pooled, hook_out[0] + (size_t)c0 * E, cs));
             else AVX_HIP_CHECK(hipMemcpyAsync(hook_out[0] + (size_t)c0 * Tt * E, x32, sizeof(float) * (size_t)M * E, hipMemcpyDeviceToDevice, cs));
         }
         // 3. convolutional positional embedding + residual, encoder LayerNorm
         prof.begin("posconv", 2.0 * Md * E * (E / h->cfg.conv_pos_groups) * h->cfg.conv_pos);
-        RC(avx::posconv(w.core.xh, fast ? nullptr : x32, h->w_pc, h->b_pc, Bc, Tt, E, h->cfg.conv_pos_groups, h->cfg.conv_pos, pre32, preh, dt, cs));
+        AVXH_TRY(avx::posconv(w.core.xh, fast ? nullptr : x32, h->w_pc, h->b_pc, Bc, Tt, E, h->cfg.conv_pos_groups, h->cfg.conv_pos, pre32, preh, dt, cs));
         prof.end();
-        if (!h->pre_ln) {      // pre-LN models normalise after the stack instead (backbone.py:146-147, 176-177); their stream stays in pre32 / preh
+        if (!h->core.pre_ln) {      // pre-LN models normalise after the stack instead (backbone.py:146-147, 176-177); their stream stays in pre32 / preh
             prof.begin("layernorm", 0.0);
-            RC(avx::layernorm(pre32, preh, E, h->lnE_w, h->lnE_b, 1e-5f, M, E, fast ? nullptr : x32, E, w.core.xh, E, dt, cs));
+            AVXH_TRY(avx::layernorm(pre32, preh, E, h->lnE_w, h->lnE_b, 1e-5f, M, E, fast ? nullptr : x32, E, w.core.xh, E, dt, cs));
             prof.end();
         }
 
@@ -586,13 +533,13 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
         CoreIo io;
         io.Bc = Bc; io.Tt = Tt; io.c0 = (size_t)c0; io.bias_tab = bias_tab; io.pad = pad; io.hook_mask = hook_mask; io.hook_bit0 = 1;
         io.hook_out = hook_out; io.hook_pooled = hook_pooled; io.features_out = features_out; io.pooled_out = pooled_out;
-        RC(avxh::run_layers(h, h->core(), h->layers, w.core, io, prof, cs));
+        AVXH_TRY(avxh::run_layers(h, h->core, h->layers, w.core, io, prof, cs));
         if (L == 0) {
             // no layers: features = encoder LayerNorm output; recompute it in fp32 for the outputs
             if (features_out || pooled_out) {
                 float* xo = features_out ? features_out + (size_t)c0 * Tt * E : x32;
-                RC(avx::layernorm(pre32, preh, E, h->lnE_w, h->lnE_b, 1e-5f, M, E, xo, E, nullptr, E, dt, cs));
-                if (pooled_out) RC(avx::mean_pool(xo, Bc, Tt, E, nullptr, pooled_out + (size_t)c0 * E, cs));
+                AVXH_TRY(avx::layernorm(pre32, preh, E, h->lnE_w, h->lnE_b, 1e-5f, M, E, xo, E, nullptr, E, dt, cs));
+                if (pooled_out) AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, nullptr, pooled_out + (size_t)c0 * E, cs));
             }
         }
     }
@@ -605,28 +552,16 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
         }
     }
     }   // rounds
-#undef RC
-    { const int rc2 = h->mirror_alarm(s); if (rc2 != AVEXHIP_OK) return rc2; }
-    return prof.collect();
+    return avxh::finish_forward(h, prof, s);
 }
 
 
 }  // namespace
 
 extern "C" avexhip_beats* avexhip_beats_create(const avexhip_beats_config* cfg, const avexhip_tensor* tensors, int n_tensors) {
-    if (!cfg || !tensors || n_tensors <= 0) {
-        avexhip_set_error("beats_create: null config or empty weight table");
-        return nullptr;
-    }
-    if (avexhip_device_count() <= 0) {
-        avexhip_set_error("beats_create: no HIP device visible (this path has no CPU fallback)");
-        return nullptr;
-    }
+    if (!avxh::check_create_common("beats_create", cfg, tensors, n_tensors)) return nullptr;
     const avexhip_beats_config& c = *cfg;
-    if (c.encoder_attention_heads <= 0 || c.encoder_embed_dim != 64 * c.encoder_attention_heads) {
-        avexhip_set_error("beats_create: head_dim must be 64 (E=%d, H=%d)", c.encoder_embed_dim, c.encoder_attention_heads);
-        return nullptr;
-    }
+    if (!avxh::check_head64("beats_create", c.encoder_embed_dim, c.encoder_attention_heads)) return nullptr;
     if (c.encoder_embed_dim % 128 || c.encoder_ffn_embed_dim % 128 || c.embed_dim % 128 ||
         (c.input_patch_size * c.input_patch_size) % 64 || c.num_mel_bins % c.input_patch_size) {
         avexhip_set_error("beats_create: dims must be MFMA-tile multiples (E=%d F=%d D=%d P=%d mel=%d)", c.encoder_embed_dim,
@@ -649,10 +584,7 @@ extern "C" avexhip_beats* avexhip_beats_create(const avexhip_beats_config* cfg, 
         avexhip_set_error("beats_create: encoder_layers=%d out of range", c.encoder_layers);
         return nullptr;
     }
-    if (c.operand_dtype != AVEXHIP_F16 && c.operand_dtype != AVEXHIP_BF16) {
-        avexhip_set_error("beats_create: unknown operand dtype %d", c.operand_dtype);
-        return nullptr;
-    }
+    if (!avxh::check_operand_dtype("beats_create", c.operand_dtype)) return nullptr;
     if (c.hidden_shift < 0 || c.hidden_shift > 24 || (c.hidden_shift > 0 && c.activation_fn == AVEXHIP_FFN_GLU)) {
         avexhip_set_error("beats_create: hidden_shift must be 0..24 and is not built for the GLU feed-forward (got %d)", c.hidden_shift);
         return nullptr;
@@ -660,28 +592,27 @@ extern "C" avexhip_beats* avexhip_beats_create(const avexhip_beats_config* cfg, 
     avexhip_beats* h = new avexhip_beats();
     h->cfg = c;
     h->dtype = c.operand_dtype;
-    h->E = c.encoder_embed_dim; h->F = c.encoder_ffn_embed_dim; h->H = c.encoder_attention_heads;
-    h->L = c.encoder_layers; h->D = c.embed_dim; h->P = c.input_patch_size; h->NM = c.num_mel_bins;
+    CoreCfg& core = h->core;      // (eps 1e-5 and hook site fc2 are CoreCfg's defaults)
+    core.E = c.encoder_embed_dim; core.F = c.encoder_ffn_embed_dim; core.H = c.encoder_attention_heads; core.L = c.encoder_layers;
+    h->D = c.embed_dim; h->P = c.input_patch_size; h->NM = c.num_mel_bins;
     h->chunk = c.max_chunk_clips > 0 ? c.max_chunk_clips : 256;
-    h->fast = avxh::cfg_fast(c.residual_dtype);
-    h->batch_invariant = avxh::cfg_batch_invariant(c.residual_dtype);
     {
         // The encoder's LayerNorms are folded into the GEMM epilogues around them (GemmArgs) unless AVEX_AMD_LN_FOLD=0: 24 LayerNorm
         // launches and 9 GB of traffic per 256-clip step disappear, +2.7 % (9 367 -> 9 623 clips/s alternating inside one process,
         // profiles/r03a_ln_fold.txt) and one rounding of the residual stream less per sublayer.  Built for post-LN blocks with a GELU FFN.
-        avxh::fold_policy(h->fast, c.encoder_embed_dim, c.encoder_ffn_embed_dim, &h->ln_fold, &h->ln_fold_min_rows, h->batch_invariant);
-        if (c.layer_norm_first || c.activation_fn != AVEXHIP_FFN_GELU) h->ln_fold = false;
+        avxh::core_from_residual(core, c.residual_dtype, core.E, core.F);
+        if (c.layer_norm_first || c.activation_fn != AVEXHIP_FFN_GELU) core.fold = false;
     }
-    h->pre_ln = c.layer_norm_first != 0;
-    h->glu = c.activation_fn == AVEXHIP_FFN_GLU;
-    h->hidden_shift = c.hidden_shift;
-    if (h->hidden_shift > 0) h->ln_fold = false;      // the folded epilogues are the fast ones, which do not scale (GemmArgs::half_scale)
+    core.pre_ln = c.layer_norm_first != 0;
+    core.glu = c.activation_fn == AVEXHIP_FFN_GLU;
+    core.hidden_shift = c.hidden_shift;
+    if (core.hidden_shift > 0) core.fold = false;      // the folded epilogues are the fast ones, which do not scale (GemmArgs::half_scale)
     switch (c.activation_fn) {      // GemmArgs::gelu codes
-        case AVEXHIP_FFN_GELU: h->act = 1; break;
-        case AVEXHIP_FFN_RELU: h->act = 3; break;
-        case AVEXHIP_FFN_GELU_TANH: h->act = 4; break;
-        case AVEXHIP_FFN_TANH: h->act = 5; break;
-        default: h->act = 0; break;      // linear; glu applies its own gate after fc1
+        case AVEXHIP_FFN_GELU: core.act = 1; break;
+        case AVEXHIP_FFN_RELU: core.act = 3; break;
+        case AVEXHIP_FFN_GELU_TANH: core.act = 4; break;
+        case AVEXHIP_FFN_TANH: core.act = 5; break;
+        default: core.act = 0; break;      // linear; glu applies its own gate after fc1
     }
     {
         // Independent chunks of a batch can overlap on several HIP streams: one chunk's HBM-bound kernels
@@ -710,7 +641,7 @@ extern "C" avexhip_beats* avexhip_beats_create(const avexhip_beats_config* cfg, 
         delete h;
         return nullptr;
     }
-    h->alpha = c.deep_norm ? powf(2.0f * (float)c.encoder_layers, 0.25f) : 1.0f;
+    core.alpha = c.deep_norm ? powf(2.0f * (float)c.encoder_layers, 0.25f) : 1.0f;
     if (build(h, tensors, n_tensors) != AVEXHIP_OK || h->weights_fit() != AVEXHIP_OK) {
         delete h;
         return nullptr;
@@ -833,8 +764,7 @@ extern "C" int avexhip_beats_graph_nodes(const avexhip_beats_graph* g) { return 
 extern "C" void avexhip_beats_graph_destroy(avexhip_beats_graph* g) { delete g; }
 
 extern "C" int avexhip_beats_overflow_count(avexhip_beats* h, uint32_t* events, void* sync_stream, int synchronize) {
-    AVX_REQUIRE(h && events, "overflow_count: null argument");
-    return h->overflow_count(events, (hipStream_t)sync_stream, synchronize);
+    return avxh::HandleBase::overflow_count(h, "overflow_count", events, sync_stream, synchronize);
 }
 
 extern "C" int avexhip_beats_overflow_reset(avexhip_beats* h, void* stream) {
@@ -843,17 +773,10 @@ extern "C" int avexhip_beats_overflow_reset(avexhip_beats* h, void* stream) {
 }
 
 extern "C" int avexhip_beats_set_profiling(avexhip_beats* h, int enabled) {
-    AVX_REQUIRE(h, "set_profiling: null handle");
-    h->profiling = enabled != 0;
-    return AVEXHIP_OK;
+    return avxh::HandleBase::set_profiling(h, "set_profiling", enabled);
 }
 
 extern "C" int avexhip_beats_last_profile(const avexhip_beats* h, const char* const** names, const float** ms,
                                           const double** flops, int* count) {
-    AVX_REQUIRE(h && names && ms && flops && count, "last_profile: null argument");
-    *names = h->prof_name_ptrs.data();
-    *ms = h->prof_ms.data();
-    *flops = h->prof_flops.data();
-    *count = (int)h->prof_name_ptrs.size();
-    return AVEXHIP_OK;
+    return avxh::HandleBase::last_profile(h, "last_profile", names, ms, flops, count);
 }

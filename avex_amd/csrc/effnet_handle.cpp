@@ -103,10 +103,10 @@ int upload_f32(avexhip_effnet* h, const std::vector<float>& v, float** out) {
 // eval-mode BatchNorm as an affine map: y = x * scale + shift
 int bn_fold(avexhip_effnet* h, const Table& tb, const std::string& name, int C, std::vector<float>& scale, std::vector<float>& shift) {
     std::vector<float> w, b, m, v;
-    int rc;
-    if ((rc = avxh::host_f32(h, tb, name + ".weight", C, w)) != AVEXHIP_OK || (rc = avxh::host_f32(h, tb, name + ".bias", C, b)) != AVEXHIP_OK ||
-        (rc = avxh::host_f32(h, tb, name + ".running_mean", C, m)) != AVEXHIP_OK || (rc = avxh::host_f32(h, tb, name + ".running_var", C, v)) != AVEXHIP_OK)
-        return rc;
+    AVXH_TRY(avxh::host_f32(h, tb, name + ".weight", C, w));
+    AVXH_TRY(avxh::host_f32(h, tb, name + ".bias", C, b));
+    AVXH_TRY(avxh::host_f32(h, tb, name + ".running_mean", C, m));
+    AVXH_TRY(avxh::host_f32(h, tb, name + ".running_var", C, v));
     scale.resize(C); shift.resize(C);
     for (int c = 0; c < C; ++c) {
         scale[c] = w[c] / sqrtf(v[c] + h->cfg.bn_eps);
@@ -119,9 +119,8 @@ int bn_fold(avexhip_effnet* h, const Table& tb, const std::string& name, int C, 
 int pointwise(avexhip_effnet* h, const Table& tb, const std::string& conv, const std::string& bn, int N, int K, int Kp, void** w_out, float** b_out,
               std::vector<float>* scale_out, std::vector<float>* shift_out) {
     std::vector<float> w, sc, sh;
-    int rc;
-    if ((rc = avxh::host_f32(h, tb, conv + ".weight", (int64_t)N * K, w)) != AVEXHIP_OK) return rc;
-    if ((rc = bn_fold(h, tb, bn, N, sc, sh)) != AVEXHIP_OK) return rc;
+    AVXH_TRY(avxh::host_f32(h, tb, conv + ".weight", (int64_t)N * K, w));
+    AVXH_TRY(bn_fold(h, tb, bn, N, sc, sh));
     const int Np = pad128(N);
     std::vector<float> wp((size_t)Np * Kp, 0.f), bp(Np, 0.f);
     for (int n = 0; n < N; ++n) {
@@ -130,8 +129,8 @@ int pointwise(avexhip_effnet* h, const Table& tb, const std::string& conv, const
     }
     AVX_HIP_CHECK(hipMalloc(w_out, 2 * wp.size()));
     h->allocs.push_back(*w_out);
-    if ((rc = avxh::upload_half(h, wp.data(), (int64_t)wp.size(), *w_out, conv.c_str())) != AVEXHIP_OK) return rc;
-    if ((rc = upload_f32(h, bp, b_out)) != AVEXHIP_OK) return rc;
+    AVXH_TRY(avxh::upload_half(h, wp.data(), (int64_t)wp.size(), *w_out, conv.c_str()));
+    AVXH_TRY(upload_f32(h, bp, b_out));
     if (scale_out) { *scale_out = sc; *shift_out = sh; }
     return AVEXHIP_OK;
 }
@@ -140,8 +139,6 @@ int effnet_build(avexhip_effnet* h, const avexhip_tensor* tensors, int n) {
     const avexhip_effnet_config& c = h->cfg;
     Table tb{tensors, n};
     tb.strip1 = "model."; tb.strip2 = nullptr;
-    int rc;
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
     // May the tensor that block `idx` reads (the stem's output for idx = 0, else block idx - 1's) be 32 channels wide in memory?  Every
     // consumer must take K = 32: the fused block front and the skinny GEMM do, the 128-tile kernels (K % 64) do not.  The head reads through
     // the 128-tile kernel; a block without an expansion feeds its 32 channels to its projection, which is skinny only up to 256 columns.
@@ -166,8 +163,8 @@ int effnet_build(avexhip_effnet* h, const avexhip_tensor* tensors, int n) {
     h->cp0 = narrow_ok(0, h->c0) ? 32 : ((h->c0 + 63) / 64) * 64;
     {   // stem: Conv2d(3, c0, 3, s2) on three copies of one image = a 1-channel 3x3 convolution with channel-summed weights; [9, cp0]
         std::vector<float> w, sc, sh;
-        RC(avxh::host_f32(h, tb, "features.0.0.weight", (int64_t)h->c0 * 3 * 9, w));
-        RC(bn_fold(h, tb, "features.0.1", h->c0, sc, sh));
+        AVXH_TRY(avxh::host_f32(h, tb, "features.0.0.weight", (int64_t)h->c0 * 3 * 9, w));
+        AVXH_TRY(bn_fold(h, tb, "features.0.1", h->c0, sc, sh));
         std::vector<float> ws((size_t)9 * h->cp0, 0.f), bs(h->cp0, 0.f);
         for (int o = 0; o < h->c0; ++o) {
             for (int t = 0; t < 9; ++t) {
@@ -176,8 +173,8 @@ int effnet_build(avexhip_effnet* h, const avexhip_tensor* tensors, int n) {
             }
             bs[o] = sh[o];
         }
-        RC(upload_f32(h, ws, &h->w_stem)); RC(upload_f32(h, bs, &h->b_stem));
-        RC(upload_f32(h, sc, &h->stem_scale)); RC(upload_f32(h, sh, &h->stem_shift));
+        AVXH_TRY(upload_f32(h, ws, &h->w_stem)); AVXH_TRY(upload_f32(h, bs, &h->b_stem));
+        AVXH_TRY(upload_f32(h, sc, &h->stem_scale)); AVXH_TRY(upload_f32(h, sh, &h->stem_shift));
     }
     int cp = h->cp0;
     h->n_taps = 1;
@@ -192,39 +189,39 @@ int effnet_build(avexhip_effnet* h, const avexhip_tensor* tensors, int n) {
             const std::string p = "features." + std::to_string(si + 1) + "." + std::to_string(j) + ".block.";
             const int d = b.has_expand ? 1 : 0;
             if (b.has_expand) {
-                RC(pointwise(h, tb, p + "0.0", p + "0.1", b.cexp, b.cin, cp, &b.w_exp, &b.b_exp, nullptr, nullptr));
+                AVXH_TRY(pointwise(h, tb, p + "0.0", p + "0.1", b.cexp, b.cin, cp, &b.w_exp, &b.b_exp, nullptr, nullptr));
                 cp = padx(b.cexp);
             }
             b.cp_exp = cp;
             {   // depthwise k x k + BN: [k*k, cp]
                 std::vector<float> w, sc, sh;
-                RC(avxh::host_f32(h, tb, p + std::to_string(d) + ".0.weight", (int64_t)b.cexp * k * k, w));
-                RC(bn_fold(h, tb, p + std::to_string(d) + ".1", b.cexp, sc, sh));
+                AVXH_TRY(avxh::host_f32(h, tb, p + std::to_string(d) + ".0.weight", (int64_t)b.cexp * k * k, w));
+                AVXH_TRY(bn_fold(h, tb, p + std::to_string(d) + ".1", b.cexp, sc, sh));
                 std::vector<float> wd((size_t)k * k * cp, 0.f), bd(cp, 0.f);
                 for (int ch = 0; ch < b.cexp; ++ch) {
                     for (int t = 0; t < k * k; ++t) wd[(size_t)t * cp + ch] = w[(size_t)ch * k * k + t] * sc[ch];
                     bd[ch] = sh[ch];
                 }
-                RC(upload_f32(h, wd, &b.w_dw)); RC(upload_f32(h, bd, &b.b_dw));
+                AVXH_TRY(upload_f32(h, wd, &b.w_dw)); AVXH_TRY(upload_f32(h, bd, &b.b_dw));
             }
             {   // squeeze-excitation: fc1 [cs, cexp, 1, 1], fc2 [cexp, cs, 1, 1]
                 const std::string se = p + std::to_string(d + 1) + ".";
                 const avexhip_tensor* t1 = tb.find(se + "fc1.bias");
                 if (!t1 || t1->numel <= 0) { avexhip_set_error("effnet_create: tensor '%sfc1.bias' missing", se.c_str()); return AVEXHIP_ERR_MISSING; }
                 b.cs = (int)t1->numel;
-                RC(avxh::dev_f32(h, tb, se + "fc1.weight", (int64_t)b.cs * b.cexp, &b.se_w1)); RC(avxh::dev_f32(h, tb, se + "fc1.bias", b.cs, &b.se_b1));
+                AVXH_TRY(avxh::dev_f32(h, tb, se + "fc1.weight", (int64_t)b.cs * b.cexp, &b.se_w1)); AVXH_TRY(avxh::dev_f32(h, tb, se + "fc1.bias", b.cs, &b.se_b1));
                 {   // second layer transposed [cs][cexp]: coalesced in avx::se_from_parts
                     std::vector<float> w2, w2t((size_t)b.cs * b.cexp);
-                    RC(avxh::host_f32(h, tb, se + "fc2.weight", (int64_t)b.cexp * b.cs, w2));
+                    AVXH_TRY(avxh::host_f32(h, tb, se + "fc2.weight", (int64_t)b.cexp * b.cs, w2));
                     for (int ch = 0; ch < b.cexp; ++ch)
                         for (int j = 0; j < b.cs; ++j) w2t[(size_t)j * b.cexp + ch] = w2[(size_t)ch * b.cs + j];
-                    RC(upload_f32(h, w2t, &b.se_w2));
+                    AVXH_TRY(upload_f32(h, w2t, &b.se_w2));
                 }
-                RC(avxh::dev_f32(h, tb, se + "fc2.bias", b.cexp, &b.se_b2));
+                AVXH_TRY(avxh::dev_f32(h, tb, se + "fc2.bias", b.cexp, &b.se_b2));
             }
             std::vector<float> scp, shp;
-            RC(pointwise(h, tb, p + std::to_string(d + 2) + ".0", p + std::to_string(d + 2) + ".1", b.cout, b.cexp, cp, &b.w_proj, &b.b_proj, &scp, &shp));
-            RC(upload_f32(h, scp, &b.proj_scale)); RC(upload_f32(h, shp, &b.proj_shift));
+            AVXH_TRY(pointwise(h, tb, p + std::to_string(d + 2) + ".0", p + std::to_string(d + 2) + ".1", b.cout, b.cexp, cp, &b.w_proj, &b.b_proj, &scp, &shp));
+            AVXH_TRY(upload_f32(h, scp, &b.proj_scale)); AVXH_TRY(upload_f32(h, shp, &b.proj_shift));
             cp = narrow_ok(bi + 1, b.cout) ? 32 : padc(b.cout);
             b.cp_out = cp;
             ++bi;
@@ -236,11 +233,10 @@ int effnet_build(avexhip_effnet* h, const avexhip_tensor* tensors, int n) {
     {
         const std::string hn = "features." + std::to_string(c.n_stages + 1);
         std::vector<float> sc, sh;
-        RC(pointwise(h, tb, hn + ".0", hn + ".1", h->head, h->blocks.back().cout, cp, &h->w_head, &h->b_head, &sc, &sh));
-        RC(upload_f32(h, sc, &h->head_scale)); RC(upload_f32(h, sh, &h->head_shift));
+        AVXH_TRY(pointwise(h, tb, hn + ".0", hn + ".1", h->head, h->blocks.back().cout, cp, &h->w_head, &h->b_head, &sc, &sh));
+        AVXH_TRY(upload_f32(h, sc, &h->head_scale)); AVXH_TRY(upload_f32(h, sh, &h->head_shift));
         ++h->n_taps;
     }
-#undef RC
     AVX_REQUIRE(h->n_taps <= 32, "effnet_create: %d hookable layers (at most 32 fit the hook mask)", h->n_taps);
     AVX_HIP_CHECK(hipDeviceSynchronize());
     return AVEXHIP_OK;
@@ -281,24 +277,22 @@ EffWs eff_carve(const avexhip_effnet* h, char* base, int Bc, int H, int W) {
     const size_t headf = (size_t)hh * ww * pad128(h->head) * 4;
     if (headf > max_raw) max_raw = headf;
     EffWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-    for (int i = 0; i < 4; ++i) w.act[i] = take((size_t)Bc * max_act);
-    w.raw = (float*)take((size_t)Bc * max_raw);
-    w.pool = (float*)take((size_t)Bc * cpmax * 4);
-    w.scale = (float*)take((size_t)Bc * cpmax * 4);
-    w.headf = (float*)take((size_t)Bc * headf);
-    w.part = (float*)take(max_part);
+    avxh::Carver cv{base};
+    for (int i = 0; i < 4; ++i) w.act[i] = cv.take((size_t)Bc * max_act);
+    w.raw = (float*)cv.take((size_t)Bc * max_raw);
+    w.pool = (float*)cv.take((size_t)Bc * cpmax * 4);
+    w.scale = (float*)cv.take((size_t)Bc * cpmax * 4);
+    w.headf = (float*)cv.take((size_t)Bc * headf);
+    w.part = (float*)cv.take(max_part);
     w.part_bytes = max_part;
-    w.total = off;
+    w.total = cv.off;
     return w;
 }
 
 }  // namespace
 
 extern "C" avexhip_effnet* avexhip_effnet_create(const avexhip_effnet_config* cfg, const avexhip_tensor* tensors, int n_tensors) {
-    if (!cfg || !tensors || n_tensors <= 0) { avexhip_set_error("effnet_create: null config or empty weight table"); return nullptr; }
-    if (avexhip_device_count() <= 0) { avexhip_set_error("effnet_create: no HIP device visible (this path has no CPU fallback)"); return nullptr; }
+    if (!avxh::check_create_common("effnet_create", cfg, tensors, n_tensors)) return nullptr;
     const avexhip_effnet_config& c = *cfg;
     if (c.n_stages < 1 || c.n_stages > 8 || c.stem_channels <= 0 || c.stem_channels > 64 || c.head_channels <= 0) {
         avexhip_set_error("effnet_create: bad layout (stages %d, stem %d, head %d)", c.n_stages, c.stem_channels, c.head_channels);
@@ -312,7 +306,7 @@ extern "C" avexhip_effnet* avexhip_effnet_create(const avexhip_effnet_config* cf
             return nullptr;
         }
     }
-    if (c.operand_dtype != AVEXHIP_F16 && c.operand_dtype != AVEXHIP_BF16) { avexhip_set_error("effnet_create: unknown operand dtype %d", c.operand_dtype); return nullptr; }
+    if (!avxh::check_operand_dtype("effnet_create", c.operand_dtype)) return nullptr;
     avexhip_effnet* h = new avexhip_effnet();
     h->who = "effnet_create";
     h->cfg = c;
@@ -352,20 +346,13 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
                                       float* features_out, float* pooled_out, void* workspace, size_t ws_bytes, void* stream) {
     AVX_REQUIRE(h && mel, "effnet_forward: null handle or input");
     AVX_REQUIRE(B > 0 && H >= 32 && W >= 32, "effnet_forward: image %d x %d x %d (at least 32 x 32: five stride-2 stages)", B, H, W);
-    AVX_REQUIRE(hook_mask == 0 || hook_out, "effnet_forward: hook_mask set but hook_out is NULL");
-    AVX_REQUIRE(h->n_taps >= 32 || (hook_mask >> h->n_taps) == 0, "effnet_forward: hook_mask has bits beyond tap %d", h->n_taps - 1);
-    for (int i = 0; i < h->n_taps; ++i) AVX_REQUIRE(!((hook_mask >> i) & 1u) || hook_out[i], "effnet_forward: tap %d selected but hook_out[%d] is NULL", i, i);
+    AVXH_TRY(avxh::check_hooks("effnet_forward", "tap", hook_mask, hook_out, h->n_taps, "tap"));
     hipStream_t s = (hipStream_t)stream;
     const int dt = h->dtype;
-    const int chunk = B < h->chunk ? B : h->chunk;
+    const int chunk = B < h->chunk ? B : h->chunk;      // by clips only: an image has no token count for encoders.cpp's chunk_for to scale by
     const EffWs need = eff_carve(h, nullptr, chunk, H, W);
-    if (!workspace || ws_bytes < need.total) {
-        avexhip_set_error("effnet_forward: workspace too small (%zu bytes given, %zu needed)", ws_bytes, need.total);
-        return AVEXHIP_ERR_WORKSPACE;
-    }
+    AVXH_TRY(avxh::check_workspace("effnet_forward", workspace, ws_bytes, need.total));
     Prof prof{h, s};
-    int rc;
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
     for (int c0 = 0; c0 < B; c0 += chunk) {
         const int Bc = (B - c0) < chunk ? (B - c0) : chunk;
         const EffWs w = eff_carve(h, (char*)workspace, chunk, H, W);
@@ -374,9 +361,9 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
         // stem (+ its tap: the kernel's raw output is the BatchNorm output before SiLU)
         const bool tap0 = hook_mask & 1u;
         prof.begin("stem", 2.0 * Bc * hh * ww * (double)h->c0 * 9);
-        RC(avexhip_effnet_stem(mel + (size_t)c0 * H * W, Bc, H, W, h->w_stem, h->b_stem, h->cp0, w.act[cur], tap0 ? w.raw : nullptr, dt, s));
+        AVXH_TRY(avexhip_effnet_stem(mel + (size_t)c0 * H * W, Bc, H, W, h->w_stem, h->b_stem, h->cp0, w.act[cur], tap0 ? w.raw : nullptr, dt, s));
         prof.end();
-        if (tap0) RC(avx::nhwc_to_nchw(w.raw, h->cp0, Bc, hh * ww, h->c0, h->stem_scale, h->stem_shift, hook_out[0] + (size_t)c0 * h->c0 * hh * ww, s));
+        if (tap0) AVXH_TRY(avx::nhwc_to_nchw(w.raw, h->cp0, Bc, hh * ww, h->c0, h->stem_scale, h->stem_shift, hook_out[0] + (size_t)c0 * h->c0 * hh * ww, s));
         int tap = 0;
         for (const Block& b : h->blocks) {
             const int in_buf = cur;
@@ -386,14 +373,14 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
             const int kin = fused_kin(b);
             if (b.has_expand && kin < 0) {
                 const int o = (in_buf + 1) & 3;
-                memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+                avxh::gemm_init(g, h);
                 g.A = w.act[in_buf]; g.lda = b.cp_in; g.W = b.w_exp; g.ldw = b.cp_in; g.M = M_in; g.N = pad128(b.cexp); g.K = b.cp_in; g.bias = b.b_exp; g.gelu = 2;
                 g.out_half = w.act[o]; g.ldh = b.cp_exp; g.n_store = b.cp_exp < g.N ? b.cp_exp : 0;
                 if (skinny_enabled() && skinny_dim(b.cp_in) && skinny_dim(b.cp_exp) && b.cp_exp != 32 && b.cp_exp * b.cp_in <= 32768) {
                     g.N = b.cp_exp; g.n_store = 0; g.variant = 7;      // whatever the row count: the 128-tile kernels take neither K = 32 nor 96 / 160 columns
                 }
                 prof.begin("gemm.expand", 2.0 * M_in * (double)b.cexp * b.cin);
-                RC(avx::gemm(g, dt, s));
+                AVXH_TRY(avx::gemm(g, dt, s));
                 prof.end();
                 x = o;
             }
@@ -402,14 +389,14 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
             int64_t part_rows = 0;                       // rows of squeeze partials per clip the depthwise kernel left
             if (kin >= 0) {
                 prof.begin("mbconv.front", 2.0 * Bc * h2 * w2 * (double)b.cexp * b.k * b.k + (b.has_expand ? 2.0 * M_in * (double)b.cexp * b.cin : 0.0));
-                RC(avx::mbconv_front(w.act[in_buf], Bc, hh, ww, b.cp_in, kin, b.w_exp, b.cp_in, b.b_exp, b.k, b.stride, b.w_dw, b.b_dw, b.cp_exp, w.act[dw],
+                AVXH_TRY(avx::mbconv_front(w.act[in_buf], Bc, hh, ww, b.cp_in, kin, b.w_exp, b.cp_in, b.b_exp, b.k, b.stride, b.w_dw, b.b_dw, b.cp_exp, w.act[dw],
                                      nullptr, w.part, w.part_bytes, h->d_ovf, dt, s));
                 part_rows = avx::mbconv_front_tiles(hh, ww, b.k, b.stride, kin);
                 prof.end();
             } else {
                 prof.begin("dwconv", 2.0 * Bc * h2 * w2 * (double)b.cexp * b.k * b.k);
-                if (dw_lds(b, hh)) RC(avx::dwconv_lds_parts(w.act[x], Bc, hh, ww, b.cp_exp, b.k, b.stride, b.w_dw, b.b_dw, w.act[dw], w.part, w.part_bytes, &part_rows, dt, s));
-                else RC(avx::dwconv_parts(w.act[x], Bc, hh, ww, b.cp_exp, b.k, b.stride, b.w_dw, b.b_dw, w.act[dw], w.part, w.part_bytes, &part_rows, dt, s));
+                if (dw_lds(b, hh)) AVXH_TRY(avx::dwconv_lds_parts(w.act[x], Bc, hh, ww, b.cp_exp, b.k, b.stride, b.w_dw, b.b_dw, w.act[dw], w.part, w.part_bytes, &part_rows, dt, s));
+                else AVXH_TRY(avx::dwconv_parts(w.act[x], Bc, hh, ww, b.cp_exp, b.k, b.stride, b.w_dw, b.b_dw, w.act[dw], w.part, w.part_bytes, &part_rows, dt, s));
                 prof.end();
             }
             const int M2 = Bc * h2 * w2;
@@ -425,9 +412,9 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
             const bool wide_fold = !skinny_proj && !no_se_fold && se_fold_wide && b.cp_exp % 64 == 0;
             se_fold = se_fold || wide_fold;
             prof.begin("se", 0.0);
-            RC(avx::se_from_parts(w.part, part_rows, Bc, (int64_t)h2 * w2, b.cexp, b.cp_exp, b.cs, b.se_w1, b.se_b1, b.se_w2, b.se_b2, w.scale, se_fold ? nullptr : w.act[dw], dt, s));
+            AVXH_TRY(avx::se_from_parts(w.part, part_rows, Bc, (int64_t)h2 * w2, b.cexp, b.cp_exp, b.cs, b.se_w1, b.se_b1, b.se_w2, b.se_b2, w.scale, se_fold ? nullptr : w.act[dw], dt, s));
             prof.end();
-            memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+            avxh::gemm_init(g, h);
             g.A = w.act[dw]; g.lda = b.cp_exp; g.W = b.w_proj; g.ldw = b.cp_exp; g.M = M2; g.N = pad128(b.cout); g.K = b.cp_exp; g.bias = b.b_proj; g.alpha = 1.0f;
             g.n_store = b.cp_out < g.N ? b.cp_out : 0;
             if (skinny_proj) {      // whatever the row count: the 128-tile kernels do not take K = 32 or 64 columns
@@ -440,12 +427,12 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
             g.out_half = w.act[out]; g.ldh = b.cp_out;
             if (hooked) { g.out_raw = w.raw; g.ldraw = b.cp_out; }
             prof.begin("gemm.project", 2.0 * M2 * (double)b.cout * b.cexp);
-            RC(avx::gemm(g, dt, s));
+            AVXH_TRY(avx::gemm(g, dt, s));
             prof.end();
             if (b.tap) {
                 ++tap;
                 // out_raw = conv * bn_scale + bn_shift (before the residual): the tap is the convolution before its BatchNorm
-                if (hooked) RC(avx::nhwc_to_nchw(w.raw, b.cp_out, Bc, h2 * w2, b.cout, b.proj_scale, b.proj_shift, hook_out[tap] + (size_t)c0 * b.cout * h2 * w2, s));
+                if (hooked) AVXH_TRY(avx::nhwc_to_nchw(w.raw, b.cp_out, Bc, h2 * w2, b.cout, b.proj_scale, b.proj_shift, hook_out[tap] + (size_t)c0 * b.cout * h2 * w2, s));
             }
             cur = out; hh = h2; ww = w2;
         }
@@ -453,36 +440,29 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
         const int M = Bc * hh * ww, Np = pad128(h->head);
         const bool tap_head = (hook_mask >> (h->n_taps - 1)) & 1u;
         avx::GemmArgs g;
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        avxh::gemm_init(g, h);
         g.A = w.act[cur]; g.lda = h->cp_last; g.W = h->w_head; g.ldw = h->cp_last; g.M = M; g.N = Np; g.K = h->cp_last; g.bias = h->b_head; g.gelu = 2;
         g.out_f32 = w.headf; g.ldo = Np;
         if (tap_head) { g.out_raw = w.raw; g.ldraw = Np; }
         prof.begin("gemm.head", 2.0 * M * (double)h->head * h->blocks.back().cout);
-        RC(avx::gemm(g, dt, s));
+        AVXH_TRY(avx::gemm(g, dt, s));
         prof.end();
-        if (tap_head) RC(avx::nhwc_to_nchw(w.raw, Np, Bc, hh * ww, h->head, h->head_scale, h->head_shift, hook_out[h->n_taps - 1] + (size_t)c0 * h->head * hh * ww, s));
-        if (features_out) RC(avx::nhwc_to_nchw(w.headf, Np, Bc, hh * ww, h->head, nullptr, nullptr, features_out + (size_t)c0 * h->head * hh * ww, s));
+        if (tap_head) AVXH_TRY(avx::nhwc_to_nchw(w.raw, Np, Bc, hh * ww, h->head, h->head_scale, h->head_shift, hook_out[h->n_taps - 1] + (size_t)c0 * h->head * hh * ww, s));
+        if (features_out) AVXH_TRY(avx::nhwc_to_nchw(w.headf, Np, Bc, hh * ww, h->head, nullptr, nullptr, features_out + (size_t)c0 * h->head * hh * ww, s));
         if (pooled_out) {
             AVX_REQUIRE(Np == h->head, "effnet_forward: pooled output needs a head width that is a multiple of 128 (%d)", h->head);
-            RC(avx::mean_pool(w.headf, Bc, hh * ww, h->head, nullptr, pooled_out + (size_t)c0 * h->head, s));
+            AVXH_TRY(avx::mean_pool(w.headf, Bc, hh * ww, h->head, nullptr, pooled_out + (size_t)c0 * h->head, s));
         }
     }
-#undef RC
-    { const int rc2 = h->mirror_alarm(s); if (rc2 != AVEXHIP_OK) return rc2; }
-    return prof.collect();
+    return avxh::finish_forward(h, prof, s);
 }
 
 extern "C" int avexhip_effnet_overflow_count(avexhip_effnet* h, uint32_t* events, void* sync_stream, int synchronize) {
-    AVX_REQUIRE(h && events, "effnet_overflow_count: null argument");
-    return h->overflow_count(events, (hipStream_t)sync_stream, synchronize);
+    return avxh::HandleBase::overflow_count(h, "effnet_overflow_count", events, sync_stream, synchronize);
 }
 extern "C" int avexhip_effnet_set_profiling(avexhip_effnet* h, int enabled) {
-    AVX_REQUIRE(h, "effnet_set_profiling: null handle");
-    h->profiling = enabled != 0;
-    return AVEXHIP_OK;
+    return avxh::HandleBase::set_profiling(h, "effnet_set_profiling", enabled);
 }
 extern "C" int avexhip_effnet_last_profile(const avexhip_effnet* h, const char* const** names, const float** ms, const double** flops, int* count) {
-    AVX_REQUIRE(h && names && ms && flops && count, "effnet_last_profile: null argument");
-    *names = h->prof_name_ptrs.data(); *ms = h->prof_ms.data(); *flops = h->prof_flops.data(); *count = (int)h->prof_name_ptrs.size();
-    return AVEXHIP_OK;
+    return avxh::HandleBase::last_profile(h, "effnet_last_profile", names, ms, flops, count);
 }

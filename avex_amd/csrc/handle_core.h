@@ -1,8 +1,11 @@
-// What the encoder handles (avexhip_beats in api.cpp; avexhip_eat / avexhip_aves in encoders.cpp) share: the weight-table helpers,
-// the per-layer parameter block, and the post-LN transformer layer loop on the GEMM / attention / LayerNorm kernels -- with the
-// LayerNorms folded into the GEMM epilogues (GemmArgs) when the residual stream is kept in the operand type.
+// What the five encoder handles share (avexhip_beats in api.cpp; avexhip_eat / avexhip_aves / avexhip_stack in encoders.cpp;
+// avexhip_effnet in effnet_handle.cpp).  All five: HandleBase (range alarm, profiling, the exported accessors' bodies), the argument
+// checks of *_create / *_forward, the workspace Carver, the weight-table helpers and the tail of a forward.  The four transformer
+// handles also: the frontend's window / mel bank, the positional-convolution packing, the per-layer parameter block, and the post-LN
+// transformer layer loop on the GEMM / attention / LayerNorm kernels -- with the LayerNorms folded into the GEMM epilogues (GemmArgs)
+// when the residual stream is kept in the operand type.
 //
-// The three encoders differ only in what surrounds the loop (frontend, positional scheme) and in four parameters of it:
+// The transformer encoders differ only in what surrounds the loop (frontend, positional scheme) and in four parameters of it:
 //   alpha     DeepNorm residual scale (BEATs: (2 L)^(1/4), backbone.py:304-308; EAT, wav2vec2: 1)
 //   eps       LayerNorm epsilon (BEATs / wav2vec2 1e-5, EAT 1e-6)
 //   bias/gate relative-position bias table + gate (BEATs only)
@@ -18,9 +21,19 @@
 
 #include "common.h"
 
+// return the first AVEXHIP_* code that is not OK (its message is already set)
+#define AVXH_TRY(x) do { const int rc_ = (x); if (rc_ != AVEXHIP_OK) return rc_; } while (0)
+
 namespace avxh {
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// hands out consecutive aligned pieces of a caller-provided workspace (NULL base: sizes only); `off` ends as the bytes needed
+struct Carver {
+    char* base;
+    size_t off = 0;
+    char* take(size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; }
+};
 
 struct StageRec {
     std::string name;
@@ -61,9 +74,25 @@ struct HandleBase {
         if (d_ovf && h_ovf) AVX_HIP_CHECK(hipMemcpyAsync(h_ovf, d_ovf, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
         return AVEXHIP_OK;
     }
-    int overflow_count(uint32_t* events, hipStream_t s, int synchronize) {
-        if (synchronize) AVX_HIP_CHECK(hipStreamSynchronize(s));
-        *events = h_ovf ? *(volatile unsigned int*)h_ovf : 0u;
+    // The bodies of the exported *_overflow_count / *_set_profiling / *_last_profile; `who` is the exported symbol's own message prefix
+    // (BEATs' say "overflow_count", the later families' "eat_overflow_count").
+    static int overflow_count(HandleBase* h, const char* who, uint32_t* events, void* sync_stream, int synchronize) {
+        AVX_REQUIRE(h && events, "%s: null argument", who);
+        if (synchronize) AVX_HIP_CHECK(hipStreamSynchronize((hipStream_t)sync_stream));
+        *events = h->h_ovf ? *(volatile unsigned int*)h->h_ovf : 0u;
+        return AVEXHIP_OK;
+    }
+    static int set_profiling(HandleBase* h, const char* who, int enabled) {
+        AVX_REQUIRE(h, "%s: null handle", who);
+        h->profiling = enabled != 0;
+        return AVEXHIP_OK;
+    }
+    static int last_profile(const HandleBase* h, const char* who, const char* const** names, const float** ms, const double** flops, int* count) {
+        AVX_REQUIRE(h && names && ms && flops && count, "%s: null argument", who);
+        *names = h->prof_name_ptrs.data();
+        *ms = h->prof_ms.data();
+        *flops = h->prof_flops.data();
+        *count = (int)h->prof_name_ptrs.size();
         return AVEXHIP_OK;
     }
     int overflow_reset(hipStream_t s) {
@@ -138,6 +167,85 @@ struct Prof {
         return AVEXHIP_OK;
     }
 };
+
+// the tail of every forward: mirror the range alarm to the host, then (profiling mode only) read the events back
+inline int finish_forward(HandleBase* h, Prof& prof, hipStream_t s) {
+    AVXH_TRY(h->mirror_alarm(s));
+    return prof.collect();
+}
+
+// GemmArgs of a product inside a forward: all zero but the handle's range alarm
+inline void gemm_init(avx::GemmArgs& g, const HandleBase* h) {
+    memset(&g, 0, sizeof(g));
+    g.ovf = h->d_ovf;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Argument checks the families share; `who` is the entry point's message prefix ("eat_create", "aves_forward").  The *_create ones
+// return false with the message set (a create returns NULL, not a code).  Each family calls them where its own checks stood, so
+// which refusal comes first for several bad arguments is unchanged.
+// ---------------------------------------------------------------------------------------------
+inline bool check_create_common(const char* who, const void* cfg, const avexhip_tensor* tensors, int n_tensors) {
+    if (!cfg || !tensors || n_tensors <= 0) { avexhip_set_error("%s: null config or empty weight table", who); return false; }
+    if (avexhip_device_count() <= 0) { avexhip_set_error("%s: no HIP device visible (this path has no CPU fallback)", who); return false; }
+    return true;
+}
+inline bool check_operand_dtype(const char* who, int dtype) {
+    if (dtype == AVEXHIP_F16 || dtype == AVEXHIP_BF16) return true;
+    avexhip_set_error("%s: unknown operand dtype %d", who, dtype);
+    return false;
+}
+inline bool check_head64(const char* who, int E, int H) {      // avx::attention is built for 64-wide heads
+    if (H > 0 && E == 64 * H) return true;
+    avexhip_set_error("%s: head_dim must be 64 (E=%d, H=%d)", who, E, H);
+    return false;
+}
+inline bool check_tile_dims(const char* who, int E, int F) {
+    if (E % 128 == 0 && F % 128 == 0) return true;
+    avexhip_set_error("%s: dims must be MFMA-tile multiples (E=%d F=%d)", who, E, F);
+    return false;
+}
+// hook_mask / hook_out of a forward with hooks 0 .. n_hooks - 1; `noun` names what the bits count ("layer", "block", "tap"), `item` what
+// a selected one is called ("hook"; EfficientNet: "tap")
+inline int check_hooks(const char* who, const char* noun, uint32_t mask, float* const* out, int n_hooks, const char* item = "hook") {
+    AVX_REQUIRE(mask == 0 || out, "%s: hook_mask set but hook_out is NULL", who);
+    AVX_REQUIRE(n_hooks >= 32 || (mask >> n_hooks) == 0, "%s: hook_mask has bits beyond %s %d", who, noun, n_hooks - 1);
+    for (int i = 0; i < n_hooks; ++i) AVX_REQUIRE(!((mask >> i) & 1u) || out[i], "%s: %s %d selected but hook_out[%d] is NULL", who, item, i, i);
+    return AVEXHIP_OK;
+}
+inline int check_workspace(const char* who, const void* workspace, size_t given, size_t need) {
+    if (workspace && given >= need) return AVEXHIP_OK;
+    avexhip_set_error("%s: workspace too small (%zu bytes given, %zu needed)", who, given, need);
+    return AVEXHIP_ERR_WORKSPACE;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The kaldi filterbank's window and mel bank as the reference builds them (beats.py:75,82-118), fp32 arithmetic
+// ---------------------------------------------------------------------------------------------
+inline void hann_window(int win, std::vector<float>& w) {      // torch.hann_window(win, periodic=False), the kaldi "hanning" window
+    w.resize(win);
+    for (int n = 0; n < win; ++n) w[n] = 0.5f - 0.5f * cosf((float)n * (float)(M_PI * 2.0 / (double)(win - 1)));
+}
+inline void kaldi_mel(int n_fft, int n_mels, float sr, float low, float high, std::vector<float>& fb) {
+    const int nb = n_fft / 2;
+    const float bin_w = sr / (float)n_fft;
+    const float mel_low = (float)(1127.0 * log(1.0 + (double)low / 700.0));
+    const float mel_high = (float)(1127.0 * log(1.0 + (double)high / 700.0));
+    const float delta = (float)(((double)mel_high - (double)mel_low) / (double)(n_mels + 1));
+    fb.assign((size_t)(nb + 1) * n_mels, 0.f);
+    for (int m = 0; m < n_mels; ++m) {
+        const float left = mel_low + (float)m * delta;
+        const float center = mel_low + ((float)m + 1.0f) * delta;
+        const float right = mel_low + ((float)m + 2.0f) * delta;
+        for (int k = 0; k < nb; ++k) {
+            const float f = bin_w * (float)k;
+            const float mel = 1127.0f * logf(1.0f + f / 700.0f);
+            const float up = (mel - left) / (center - left);
+            const float down = (right - mel) / (right - center);
+            fb[(size_t)k * n_mels + m] = fmaxf(0.f, fminf(up, down));
+        }
+    }
+}
 
 // name -> fp32 tensor table handed to *_create; a key matches with or without the wrapper prefixes of the reference's state dicts
 struct Table {
@@ -230,6 +338,19 @@ inline int dev_half(HandleBase* h, const Table& tb, const std::string& name, int
     h->allocs.push_back(d);
     *out = d;
     return dev_half_into(h, tb, name, numel, d);
+}
+
+// the weight-normed grouped positional convolution (K taps, G groups over E channels): fold g / v into one weight, packed for avx::posconv
+inline int pack_posconv(HandleBase* h, const Table& tb, const std::string& name_g, const std::string& name_v, const std::string& name_bias, int E, int G,
+                        int K, void** w_out, float** b_out) {
+    const int cg = E / G;
+    float *g = nullptr, *v = nullptr;
+    AVXH_TRY(dev_f32(h, tb, name_g, K, &g));
+    AVXH_TRY(dev_f32(h, tb, name_v, (int64_t)E * cg * K, &v));
+    AVX_HIP_CHECK(hipMalloc(w_out, 2 * (size_t)E * cg * K));
+    h->allocs.push_back(*w_out);
+    AVXH_TRY(avx::posconv_pack(g, v, E, G, K, *w_out, h->dtype, nullptr));
+    return dev_f32(h, tb, name_bias, E, b_out);
 }
 
 // W' = half(W * diag(gamma)), b' = b + W beta, s[n] = sum_k float(W'[n][k]) for a consumer of LayerNorm(y; gamma, beta)
@@ -344,26 +465,30 @@ inline void fold_policy(bool fast, int E, int F, bool* fold, int* min_rows, bool
     if (e && is_auto) { const char* c = strchr(e, ':'); if (c && atoi(c + 1) > 0) rows = atoi(c + 1); }      // "auto:4096": another threshold (experiments)
     *min_rows = is_auto && !batch_invariant ? rows : 0;
 }
+// a config's residual_dtype -> the CoreCfg fields it decides (reads AVEX_AMD_BATCH_INVARIANT, then AVEX_AMD_LN_FOLD: once, at create time)
+inline void core_from_residual(CoreCfg& c, int residual_dtype, int E, int F) {
+    c.fast = cfg_fast(residual_dtype);
+    c.batch_invariant = cfg_batch_invariant(residual_dtype);
+    fold_policy(c.fast, E, F, &c.fold, &c.fold_min_rows, c.batch_invariant);
+}
 
 // upload layer i (and, with the fold, its LayerNorm-folded copies; layer i - 1 must have been built)
 inline int build_layer(HandleBase* h, const Table& tb, const LayerNames& nm, const CoreCfg& c, std::vector<Layer>& layers, int i) {
     const int E = c.E, F = c.F, H = c.H;
     Layer& ly = layers[i];
-    int rc;
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
     AVX_HIP_CHECK(hipMalloc(&ly.w_qkv, 2 * (size_t)3 * E * E));
     h->allocs.push_back(ly.w_qkv);
     AVX_HIP_CHECK(hipMalloc((void**)&ly.b_qkv, sizeof(float) * 3 * E));
     h->allocs.push_back(ly.b_qkv);
     std::vector<float> Wqkv, bqkv;          // host copies: rows [0, E) are W_q (scaled by log2(e) here, in fp32), kept for the LayerNorm fold
     if (nm.qkv_fused) {
-        RC(host_f32(h, tb, fmt_name(nm.qkv_fused, i, ".weight"), (int64_t)3 * E * E, Wqkv));
-        RC(host_f32(h, tb, fmt_name(nm.qkv_fused, i, ".bias"), 3 * E, bqkv));
+        AVXH_TRY(host_f32(h, tb, fmt_name(nm.qkv_fused, i, ".weight"), (int64_t)3 * E * E, Wqkv));
+        AVXH_TRY(host_f32(h, tb, fmt_name(nm.qkv_fused, i, ".bias"), 3 * E, bqkv));
     } else {
         const char* part[3] = {nm.q, nm.k, nm.v};
         for (int j = 0; j < 3; ++j) {
-            RC(host_f32(h, tb, fmt_name(part[j], i, ".weight"), (int64_t)E * E, Wqkv));
-            RC(host_f32(h, tb, fmt_name(part[j], i, ".bias"), E, bqkv));
+            AVXH_TRY(host_f32(h, tb, fmt_name(part[j], i, ".weight"), (int64_t)E * E, Wqkv));
+            AVXH_TRY(host_f32(h, tb, fmt_name(part[j], i, ".bias"), E, bqkv));
         }
     }
     if (h->q_log2e) {
@@ -371,25 +496,25 @@ inline int build_layer(HandleBase* h, const Table& tb, const LayerNames& nm, con
         for (size_t j = 0; j < (size_t)E * E; ++j) Wqkv[j] *= l2e;
         for (int j = 0; j < E; ++j) bqkv[j] *= l2e;
     }
-    RC(upload_half(h, Wqkv.data(), (int64_t)3 * E * E, ly.w_qkv, "qkv.weight"));
+    AVXH_TRY(upload_half(h, Wqkv.data(), (int64_t)3 * E * E, ly.w_qkv, "qkv.weight"));
     AVX_HIP_CHECK(hipMemcpy(ly.b_qkv, bqkv.data(), sizeof(float) * 3 * E, hipMemcpyHostToDevice));
-    RC(dev_half(h, tb, fmt_name(nm.out_proj, i, ".weight"), (int64_t)E * E, &ly.w_o));
-    RC(dev_f32(h, tb, fmt_name(nm.out_proj, i, ".bias"), E, &ly.b_o));
+    AVXH_TRY(dev_half(h, tb, fmt_name(nm.out_proj, i, ".weight"), (int64_t)E * E, &ly.w_o));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.out_proj, i, ".bias"), E, &ly.b_o));
     if (nm.grep_linear) {
-        RC(dev_f32(h, tb, fmt_name(nm.grep_linear, i, ".weight"), 8 * (E / H), &ly.grep_w));
-        RC(dev_f32(h, tb, fmt_name(nm.grep_linear, i, ".bias"), 8, &ly.grep_b));
-        RC(dev_f32(h, tb, fmt_name(nm.grep_a, i, ""), H, &ly.grep_a));
+        AVXH_TRY(dev_f32(h, tb, fmt_name(nm.grep_linear, i, ".weight"), 8 * (E / H), &ly.grep_w));
+        AVXH_TRY(dev_f32(h, tb, fmt_name(nm.grep_linear, i, ".bias"), 8, &ly.grep_b));
+        AVXH_TRY(dev_f32(h, tb, fmt_name(nm.grep_a, i, ""), H, &ly.grep_a));
     }
-    RC(dev_f32(h, tb, fmt_name(nm.ln1, i, ".weight"), E, &ly.ln1_w));
-    RC(dev_f32(h, tb, fmt_name(nm.ln1, i, ".bias"), E, &ly.ln1_b));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.ln1, i, ".weight"), E, &ly.ln1_w));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.ln1, i, ".bias"), E, &ly.ln1_b));
     if (F == 0) return AVEXHIP_OK;         // attention-only block
     const int F1 = c.glu ? 2 * F : F;      // GLU_Linear keeps its Linear(E, 2F) under ".linear"
-    RC(dev_half(h, tb, fmt_name(nm.fc1, i, c.glu ? ".linear.weight" : ".weight"), (int64_t)F1 * E, &ly.w_fc1));
-    RC(dev_f32(h, tb, fmt_name(nm.fc1, i, c.glu ? ".linear.bias" : ".bias"), F1, &ly.b_fc1));
+    AVXH_TRY(dev_half(h, tb, fmt_name(nm.fc1, i, c.glu ? ".linear.weight" : ".weight"), (int64_t)F1 * E, &ly.w_fc1));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.fc1, i, c.glu ? ".linear.bias" : ".bias"), F1, &ly.b_fc1));
     if (c.hidden_shift > 0) {
         // fc2's weights x 2^shift: the power of two is exact in fp32 and in the operand type unless a weight leaves its range
         std::vector<float> W2;
-        RC(host_f32(h, tb, fmt_name(nm.fc2, i, ".weight"), (int64_t)E * F, W2));
+        AVXH_TRY(host_f32(h, tb, fmt_name(nm.fc2, i, ".weight"), (int64_t)E * F, W2));
         const float sc = ldexpf(1.0f, c.hidden_shift);
         float mx = 0.f;
         for (float& v : W2) { v *= sc; mx = fabsf(v) > mx ? fabsf(v) : mx; }
@@ -399,13 +524,13 @@ inline int build_layer(HandleBase* h, const Table& tb, const LayerNames& nm, con
         }
         AVX_HIP_CHECK(hipMalloc(&ly.w_fc2, 2 * (size_t)E * F));
         h->allocs.push_back(ly.w_fc2);
-        RC(upload_half(h, W2.data(), (int64_t)E * F, ly.w_fc2, "fc2.weight x 2^shift"));
+        AVXH_TRY(upload_half(h, W2.data(), (int64_t)E * F, ly.w_fc2, "fc2.weight x 2^shift"));
     } else {
-        RC(dev_half(h, tb, fmt_name(nm.fc2, i, ".weight"), (int64_t)E * F, &ly.w_fc2));
+        AVXH_TRY(dev_half(h, tb, fmt_name(nm.fc2, i, ".weight"), (int64_t)E * F, &ly.w_fc2));
     }
-    RC(dev_f32(h, tb, fmt_name(nm.fc2, i, ".bias"), E, &ly.b_fc2));
-    RC(dev_f32(h, tb, fmt_name(nm.ln2, i, ".weight"), E, &ly.ln2_w));
-    RC(dev_f32(h, tb, fmt_name(nm.ln2, i, ".bias"), E, &ly.ln2_b));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.fc2, i, ".bias"), E, &ly.b_fc2));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.ln2, i, ".weight"), E, &ly.ln2_w));
+    AVXH_TRY(dev_f32(h, tb, fmt_name(nm.ln2, i, ".bias"), E, &ly.ln2_b));
     if (c.fold) {
         auto two = [&](float** ga, float** bb) -> int {
             AVX_HIP_CHECK(hipMalloc((void**)ga, sizeof(float) * 2 * (size_t)E));
@@ -413,20 +538,19 @@ inline int build_layer(HandleBase* h, const Table& tb, const LayerNames& nm, con
             *bb = *ga + E;
             return AVEXHIP_OK;
         };
-        RC(two(&ly.ga_fc2, &ly.bb_fc2));
-        RC(avx::lnr_fold(ly.ln1_w, ly.ln1_b, ly.b_fc2, c.alpha, E, ly.ga_fc2, ly.bb_fc2, nullptr));
+        AVXH_TRY(two(&ly.ga_fc2, &ly.bb_fc2));
+        AVXH_TRY(avx::lnr_fold(ly.ln1_w, ly.ln1_b, ly.b_fc2, c.alpha, E, ly.ga_fc2, ly.bb_fc2, nullptr));
         std::vector<float> Wh, bh;
-        RC(host_f32(h, tb, fmt_name(nm.fc1, i, ".weight"), (int64_t)F * E, Wh));
-        RC(host_f32(h, tb, fmt_name(nm.fc1, i, ".bias"), F, bh));
-        RC(fold_ln(h, Wh, bh, F, E, ly.ln1_w, ly.ln1_b, &ly.w_fc1_f, &ly.b_fc1_f, &ly.s_fc1));
+        AVXH_TRY(host_f32(h, tb, fmt_name(nm.fc1, i, ".weight"), (int64_t)F * E, Wh));
+        AVXH_TRY(host_f32(h, tb, fmt_name(nm.fc1, i, ".bias"), F, bh));
+        AVXH_TRY(fold_ln(h, Wh, bh, F, E, ly.ln1_w, ly.ln1_b, &ly.w_fc1_f, &ly.b_fc1_f, &ly.s_fc1));
         if (i > 0) {   // QKV and out_proj of layer i read LN2 of layer i - 1
             const Layer& prev = layers[i - 1];
-            RC(two(&ly.ga_o, &ly.bb_o));
-            RC(avx::lnr_fold(prev.ln2_w, prev.ln2_b, ly.b_o, c.alpha, E, ly.ga_o, ly.bb_o, nullptr));
-            RC(fold_ln(h, Wqkv, bqkv, 3 * E, E, prev.ln2_w, prev.ln2_b, &ly.w_qkv_f, &ly.b_qkv_f, &ly.s_qkv));
+            AVXH_TRY(two(&ly.ga_o, &ly.bb_o));
+            AVXH_TRY(avx::lnr_fold(prev.ln2_w, prev.ln2_b, ly.b_o, c.alpha, E, ly.ga_o, ly.bb_o, nullptr));
+            AVXH_TRY(fold_ln(h, Wqkv, bqkv, 3 * E, E, prev.ln2_w, prev.ln2_b, &ly.w_qkv_f, &ly.b_qkv_f, &ly.s_qkv));
         }
     }
-#undef RC
     return AVEXHIP_OK;
 }
 
@@ -442,26 +566,24 @@ struct CoreWs {
     float* r1; float* r2;     // ... reduced to (rstd, -mu rstd) per row by avx::ln_rowstats
 };
 
-// `take(bytes)` hands out consecutive aligned pieces of the workspace (NULL base: sizes only)
-template <typename Take>
-inline CoreWs carve_core(const CoreCfg& c, size_t M, Take&& take) {
+inline CoreWs carve_core(const CoreCfg& c, size_t M, Carver& cv) {
     CoreWs w;
-    w.x = (float*)take(M * c.E * 4);
-    w.xh = (char*)take(M * c.E * 2);
-    w.pre = (float*)take(c.fast ? 256 : M * c.E * 4);
-    w.preh = (char*)take(c.fast ? M * c.E * 2 : 256);
-    w.qkv = (char*)take(M * 3 * c.E * 2);
-    w.ah = (char*)take(M * c.E * 2);
-    w.hh = (char*)take(M * c.F * 2);
-    w.hh2 = (char*)take(c.glu ? M * c.F * 4 : 256);
-    w.pool = (float*)take(((M + 63) / 64) * 2 * (size_t)c.E * 4);
+    w.x = (float*)cv.take(M * c.E * 4);
+    w.xh = (char*)cv.take(M * c.E * 2);
+    w.pre = (float*)cv.take(c.fast ? 256 : M * c.E * 4);
+    w.preh = (char*)cv.take(c.fast ? M * c.E * 2 : 256);
+    w.qkv = (char*)cv.take(M * 3 * c.E * 2);
+    w.ah = (char*)cv.take(M * c.E * 2);
+    w.hh = (char*)cv.take(M * c.F * 2);
+    w.hh2 = (char*)cv.take(c.glu ? M * c.F * 4 : 256);
+    w.pool = (float*)cv.take(((M + 63) / 64) * 2 * (size_t)c.E * 4);
     w.splitk_bytes = (8 * M < 16384 ? 8 * M : 16384) * (size_t)c.E * 4;      // 8 splits up to 2 048 rows, 2 up to 8 192
-    w.splitk = (float*)take(w.splitk_bytes);
-    w.raw = (float*)take(M * c.E * 4);
-    w.st1 = (float*)take(c.fold ? M * (c.E / 64) * 8 : 256);
-    w.st2 = (float*)take(c.fold ? M * (c.E / 64) * 8 : 256);
-    w.r1 = (float*)take(c.fold ? (M + 256) * 8 : 256);
-    w.r2 = (float*)take(c.fold ? (M + 256) * 8 : 256);
+    w.splitk = (float*)cv.take(w.splitk_bytes);
+    w.raw = (float*)cv.take(M * c.E * 4);
+    w.st1 = (float*)cv.take(c.fold ? M * (c.E / 64) * 8 : 256);
+    w.st2 = (float*)cv.take(c.fold ? M * (c.E / 64) * 8 : 256);
+    w.r1 = (float*)cv.take(c.fold ? (M + 256) * 8 : 256);
+    w.r2 = (float*)cv.take(c.fold ? (M + 256) * 8 : 256);
     return w;
 }
 
@@ -550,42 +672,40 @@ inline int run_layers_pre_ln(HandleBase* h, const CoreCfg& c, const std::vector<
     const bool fast = c.fast;
     float* s0_32 = fast ? nullptr : w.pre;  void* s0_h = fast ? w.preh : nullptr;      // stream at layer boundaries
     float* s1_32 = fast ? nullptr : w.x;    void* s1_h = fast ? w.xh : nullptr;        // stream after the attention block
-    int rc;
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
     avx::GemmArgs g;
     io.final_f32 = nullptr;
     for (int i = 0; i < L; ++i) {
         const Layer& ly = layers[i];
         prof.begin("layernorm", 0.0);
-        RC(avx::layernorm(s0_32, s0_h, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
+        AVXH_TRY(avx::layernorm(s0_32, s0_h, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
         prof.end();
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.ah; g.lda = E; g.W = ly.w_qkv; g.ldw = E; g.M = M; g.N = 3 * E; g.K = E; g.bias = ly.b_qkv;
         g.out_half = w.qkv; g.ldh = 3 * E;
         prof.begin("gemm.qkv", 2.0 * Md * 3 * E * E);
-        pin_kernel(c, g); RC(avx::gemm(g, dt, cs));
+        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
         prof.begin("attention", 4.0 * Md * Tt * E + (ly.grep_w ? 2.0 * Md * 8 * (E / H) * H : 0.0));
-        RC(self_attention(h, c, ly, w, io, cs));
+        AVXH_TRY(self_attention(h, c, ly, w, io, cs));
         prof.end();
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.ah; g.lda = E; g.W = ly.w_o; g.ldw = E; g.M = M; g.N = E; g.K = E; g.bias = ly.b_o; g.alpha = c.alpha;
         if (fast) { g.resid_half = s0_h; g.ldrh = E; g.out_half = s1_h; g.ldh = E; }
         else { g.resid = s0_32; g.ldr = E; g.out_f32 = s1_32; g.ldo = E; }
         Tap tap_o;
         if (c.hook_site == 1) tap_o = tap_begin(c, w, io, i, g);
         prof.begin("gemm.out_proj", 2.0 * Md * E * E);
-        pin_kernel(c, g); RC(avx::gemm(g, dt, cs));
+        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
-        RC(tap_finish(tap_o, c, w, io, cs));
+        AVXH_TRY(tap_finish(tap_o, c, w, io, cs));
         prof.begin("layernorm", 0.0);
-        RC(avx::layernorm(s1_32, s1_h, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
+        AVXH_TRY(avx::layernorm(s1_32, s1_h, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
         prof.end();
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.ah; g.lda = E; g.W = ly.w_fc1; g.ldw = E; g.M = M; g.N = F; g.K = E; g.bias = ly.b_fc1; g.gelu = c.act;
         g.out_half = w.hh; g.ldh = F;
-        RC(ffn_hidden(h, c, w, g, M, prof, cs));
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        AVXH_TRY(ffn_hidden(h, c, w, g, M, prof, cs));
+        gemm_init(g, h);
         g.A = w.hh; g.lda = F; g.W = ly.w_fc2; g.ldw = F; g.M = M; g.N = E; g.K = F; g.bias = ly.b_fc2; g.alpha = c.alpha;
         if (M <= 8192 && !c.batch_invariant) { g.splitk_ws = w.splitk; g.splitk_bytes = w.splitk_bytes; }
         if (fast) { g.resid_half = s1_h; g.ldrh = E; g.out_half = s0_h; g.ldh = E; }
@@ -593,30 +713,29 @@ inline int run_layers_pre_ln(HandleBase* h, const CoreCfg& c, const std::vector<
         Tap tap_f;
         if (c.hook_site == 0) tap_f = tap_begin(c, w, io, i, g);
         prof.begin("gemm.fc2", 2.0 * Md * E * F);
-        pin_kernel(c, g); RC(avx::gemm(g, dt, cs));
+        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
-        RC(tap_finish(tap_f, c, w, io, cs));
+        AVXH_TRY(tap_finish(tap_f, c, w, io, cs));
     }
     if (L > 0 && (io.features_out || io.pooled_out)) {      // the encoder's LayerNorm after the stack (backbone.py:146-147)
         const bool fused_pool = io.pooled_out && !io.features_out && fast && E % 8 == 0 && E <= 768 && (Bc >= 32 || c.batch_invariant);
         if (fused_pool) {
             prof.begin("layernorm+mean_pool", 0.0);
-            RC(avx::layernorm_pool(s0_h, E, c.final_ln_w, c.final_ln_b, c.eps, Bc, Tt, E, io.pooled_out + io.c0 * E, dt, cs));
+            AVXH_TRY(avx::layernorm_pool(s0_h, E, c.final_ln_w, c.final_ln_b, c.eps, Bc, Tt, E, io.pooled_out + io.c0 * E, dt, cs));
             prof.end();
         } else {
             float* xo = io.features_out ? io.features_out + io.c0 * Tt * E : w.x;
             prof.begin("layernorm", 0.0);
-            RC(avx::layernorm(s0_32, s0_h, E, c.final_ln_w, c.final_ln_b, c.eps, M, E, xo, E, nullptr, E, dt, cs));
+            AVXH_TRY(avx::layernorm(s0_32, s0_h, E, c.final_ln_w, c.final_ln_b, c.eps, M, E, xo, E, nullptr, E, dt, cs));
             prof.end();
             io.final_f32 = xo;
             if (io.pooled_out) {
                 prof.begin("mean_pool", 0.0);
-                RC(avx::mean_pool(xo, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
+                AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
                 prof.end();
             }
         }
     }
-#undef RC
     return AVEXHIP_OK;
 }
 
@@ -630,8 +749,6 @@ inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>&
     float* x32 = w.x;
     float* pre32 = fast ? nullptr : w.pre;
     void* preh = fast ? w.preh : nullptr;
-    int rc;
-#define RC(x) do { rc = (x); if (rc != AVEXHIP_OK) return rc; } while (0)
     // "fold": the two LayerNorms of a layer never run as kernels.  y1 = x*alpha + attn (preh) and y2 = x1*alpha + ffn (xh) stay raw
     // in the operand type with per-row partial statistics from the epilogue that wrote them; fc1 / the next QKV read them
     // through LayerNorm-folded weights, out_proj / fc2 apply LayerNorm to their residual on the fly (GemmArgs, gemm.hip).
@@ -642,17 +759,17 @@ inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>&
     for (int i = 0; i < L; ++i) {
         const Layer& ly = layers[i];
         const bool raw_in = fold && i > 0;      // xh holds y2 of layer i-1 (raw) instead of its LayerNorm
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.xh; g.lda = E; g.W = ly.w_qkv; g.ldw = E; g.M = M; g.N = 3 * E; g.K = E; g.bias = ly.b_qkv;
         g.out_half = w.qkv; g.ldh = 3 * E;
         if (raw_in) { g.W = ly.w_qkv_f; g.bias = ly.b_qkv_f; g.ln_rows = w.r2; g.ln_s = ly.s_qkv; }
         prof.begin("gemm.qkv", 2.0 * Md * 3 * E * E);
-        pin_kernel(c, g); RC(avx::gemm(g, dt, cs));
+        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
         prof.begin("attention", 4.0 * Md * Tt * E + (ly.grep_w ? 2.0 * Md * 8 * (E / H) * H : 0.0));
-        RC(self_attention(h, c, ly, w, io, cs));
+        AVXH_TRY(self_attention(h, c, ly, w, io, cs));
         prof.end();
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.ah; g.lda = E; g.W = ly.w_o; g.ldw = E; g.M = M; g.N = E; g.K = E; g.bias = ly.b_o; g.alpha = c.alpha;
         if (fast) { g.resid_half = w.xh; g.ldrh = E; g.out_half = preh; g.ldh = E; }
         else { g.resid = x32; g.ldr = E; g.out_f32 = pre32; g.ldo = E; }
@@ -678,20 +795,20 @@ inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>&
             } else { g.splitk_ws = nullptr; g.splitk_bytes = 0; }
         }
         prof.begin("gemm.out_proj", 2.0 * Md * E * E);
-        pin_kernel(c, g); RC(avx::gemm(g, dt, cs));
+        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
-        RC(tap_finish(tap_o, c, w, io, cs));
+        AVXH_TRY(tap_finish(tap_o, c, w, io, cs));
         if (F == 0) {      // attention-only block: LN1 closes it
             const bool last_a = i == L - 1;
             float* xa = last_a ? (io.features_out ? io.features_out + io.c0 * Tt * E : x32) : (fast ? nullptr : x32);
             prof.begin("layernorm", 0.0);
-            RC(avx::layernorm(pre32, preh, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, xa, E, last_a ? nullptr : w.xh, E, dt, cs));
+            AVXH_TRY(avx::layernorm(pre32, preh, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, xa, E, last_a ? nullptr : w.xh, E, dt, cs));
             prof.end();
             if (last_a) {
                 io.final_f32 = xa;
                 if (io.pooled_out) {
                     prof.begin("mean_pool", 0.0);
-                    RC(avx::mean_pool(xa, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
+                    AVXH_TRY(avx::mean_pool(xa, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
                     prof.end();
                 }
             }
@@ -701,16 +818,16 @@ inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>&
             // (w.r1 = LN1's (rstd, -mu rstd) came out of the product: GemmArgs::rows_out)
         } else if (!ln1_fused) {
             prof.begin("layernorm", 0.0);
-            RC(avx::layernorm(pre32, preh, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, fast ? nullptr : x32, E, w.xh, E, dt, cs));
+            AVXH_TRY(avx::layernorm(pre32, preh, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, fast ? nullptr : x32, E, w.xh, E, dt, cs));
             prof.end();
         }
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.xh; g.lda = E; g.W = ly.w_fc1; g.ldw = E; g.M = M; g.N = F; g.K = E; g.bias = ly.b_fc1; g.gelu = c.act;
         g.out_half = w.hh; g.ldh = F;
         if (fold) { g.A = preh; g.W = ly.w_fc1_f; g.bias = ly.b_fc1_f; g.ln_rows = w.r1; g.ln_s = ly.s_fc1; }
-        RC(ffn_hidden(h, c, w, g, M, prof, cs));
+        AVXH_TRY(ffn_hidden(h, c, w, g, M, prof, cs));
         const bool last = i == L - 1;
-        memset(&g, 0, sizeof(g)); g.ovf = h->d_ovf;
+        gemm_init(g, h);
         g.A = w.hh; g.lda = F; g.W = ly.w_fc2; g.ldw = F; g.M = M; g.N = E; g.K = F; g.bias = ly.b_fc2; g.alpha = c.alpha;
         if (M <= 8192 && !c.batch_invariant) { g.splitk_ws = w.splitk; g.splitk_bytes = w.splitk_bytes; }      // (split-K adds in another order than one pass over K)
         if (fast) { g.resid_half = w.xh; g.ldrh = E; g.out_half = preh; g.ldh = E; }
@@ -736,35 +853,34 @@ inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>&
             ln2_fused = true;
         }
         prof.begin("gemm.fc2", 2.0 * Md * E * F);
-        pin_kernel(c, g); RC(avx::gemm(g, dt, cs));
+        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
         prof.end();
-        RC(tap_finish(tap_f, c, w, io, cs));
+        AVXH_TRY(tap_finish(tap_f, c, w, io, cs));
         if (fold && !last) {
             prof.begin("ln_rowstats", 0.0);
-            RC(avx::ln_rowstats(w.st2, M, nseg, c.eps, w.r2, cs));
+            AVXH_TRY(avx::ln_rowstats(w.st2, M, nseg, c.eps, w.r2, cs));
             prof.end();
         }
         if (fused_pool) {      // the pre-LayerNorm sums y2 sit in preh, with the fold in xh
             prof.begin("layernorm+mean_pool", 0.0);
-            RC(avx::layernorm_pool(fold ? w.xh : preh, E, ly.ln2_w, ly.ln2_b, c.eps, Bc, Tt, E, io.pooled_out + io.c0 * E, dt, cs));
+            AVXH_TRY(avx::layernorm_pool(fold ? w.xh : preh, E, ly.ln2_w, ly.ln2_b, c.eps, Bc, Tt, E, io.pooled_out + io.c0 * E, dt, cs));
             prof.end();
         } else if (!fold) {
             prof.begin("layernorm", 0.0);
-            if ((xo || !last) && !ln2_fused) RC(avx::layernorm(pre32, preh, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, xo, E, last ? nullptr : w.xh, E, dt, cs));
+            if ((xo || !last) && !ln2_fused) AVXH_TRY(avx::layernorm(pre32, preh, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, xo, E, last ? nullptr : w.xh, E, dt, cs));
             prof.end();
         } else if (last && xo) {   // the only LayerNorm of the layer stack that still runs: fp32 features from the raw y2
             prof.begin("layernorm", 0.0);
-            RC(avx::layernorm(nullptr, w.xh, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, xo, E, nullptr, E, dt, cs));
+            AVXH_TRY(avx::layernorm(nullptr, w.xh, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, xo, E, nullptr, E, dt, cs));
             prof.end();
         }
         if (last) io.final_f32 = xo;
         if (last && io.pooled_out && !fused_pool) {
             prof.begin("mean_pool", 0.0);
-            RC(avx::mean_pool(xo, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
+            AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
             prof.end();
         }
     }
-#undef RC
     return AVEXHIP_OK;
 }
 

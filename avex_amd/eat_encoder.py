@@ -18,7 +18,6 @@ BEATs path.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Iterable, Mapping, Optional
 
 import torch
@@ -29,7 +28,7 @@ from . import kernels as K
 __all__ = ["EatEncoder"]
 
 
-class EatEncoder:
+class EatEncoder(K.ResidualPairHandle):
     """``[B, T]`` fp32 waveforms (or a ``[B, 1024, 128]`` log-mel image) on the GPU -> ``[B, 513, 768]`` features / hook taps.
     A thin wrapper over the ``avexhip_eat`` handle (csrc/encoders.cpp): the library owns the weights, this class the output tensors
     and the workspace."""
@@ -42,9 +41,7 @@ class EatEncoder:
         (``pooling="cls"``, the reference wrapper's default: eat_hf.py:149,281-282) -- and ``"half"`` for token-mean outputs only
         (config C3's path).  Two library handles then, each built on first use."""
         _capi.require_gpu()
-        self.residual = str(residual or "auto").lower()
-        if self.residual != "auto":
-            K.residual_code(self.residual)      # validates
+        self._set_residual(residual)
         self.cfg = dict(cfg)
         self.dtype = operand_dtype
         self.E = int(cfg["embed_dim"]); self.H = int(cfg["num_heads"]); self.L = int(cfg["depth"]); self.P = int(cfg["patch_size"])
@@ -60,31 +57,9 @@ class EatEncoder:
         c.norm_eps, c.norm_mean, c.norm_std = self.eps, float(norm_mean), float(norm_std)
         c.operand_dtype = _capi.dtype_code(operand_dtype)
         c.max_chunk_clips = int(max_chunk_clips)
-        self._c, self._batch_invariant = c, bool(batch_invariant)
-        self._sub = {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)} if prefix else dict(state)
-        self._handles: Dict[str, int] = {}      # residual mode ("half" / "f32") -> library handle
-        self._profiling = False
-        self._h = self._handle_for(frames=self.residual in ("auto", "f32", "fp32", "float32"))      # a bad checkpoint fails here, not in the first forward
-        self._ws: Optional[torch.Tensor] = None
+        self._open("eat", c, {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)} if prefix else dict(state), batch_invariant)
         self._norm = (float(norm_mean), float(norm_std))
         self._plan = None
-
-    def _handle_for(self, frames: bool) -> int:
-        """The handle whose residual stream this call wants (``frames``: it returns un-averaged rows); ``self._h`` = the last one used."""
-        mode = ("f32" if frames else "half") if self.residual == "auto" else ("half" if K.residual_code(self.residual) & 1 else "f32")
-        h = self._handles.get(mode)
-        if h is None:
-            self._c.residual_dtype = K.residual_code(mode, self._batch_invariant)
-            arr, n, keep = K.tensor_table(self._sub)
-            h = _capi.lib().avexhip_eat_create(C.byref(self._c), arr, n)
-            del keep
-            if not h:
-                raise K.AvexHipError(f"eat_create failed: {_capi.last_error()}")
-            self._handles[mode] = h
-            if self._profiling:
-                _capi.check(_capi.lib().avexhip_eat_set_profiling(h, 1), "eat_set_profiling")
-        self._h = h
-        return h
 
     @property
     def num_tokens(self) -> int:
@@ -133,56 +108,21 @@ class EatEncoder:
         frames = bool(want_features or pooling == "cls" or (hook_layers and K.pool_code(hook_pooled) != 1))      # anything but token means
         self._handle_for(frames)
         E, Tt = self.E, self.num_tokens
-        need = int(_capi.lib().avexhip_eat_workspace_bytes(self._h, B))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        hooks: Dict[int, torch.Tensor] = {}
-        ptrs = (C.c_void_p * max(self.L, 1))()
-        mask = 0
-        for i in sorted(set(int(x) for x in hook_layers)):
+        ws = self._workspace(int(_capi.lib().avexhip_eat_workspace_bytes(self._h, B)), dev)
+        hook_layers = sorted(set(int(x) for x in hook_layers))
+        for i in hook_layers:
             if not 0 <= i < self.L:
                 raise ValueError(f"hook layer {i} out of range 0..{self.L - 1}")
-            hooks[i] = torch.empty((B, E) if K.pool_code(hook_pooled) else (B, Tt, E), dtype=torch.float32, device=dev)      # sized by the code the library gets
-            ptrs[i] = int(hooks[i].data_ptr())
-            mask |= 1 << i
+        shape = (B, E) if K.pool_code(hook_pooled) else (B, Tt, E)      # sized by the code the library gets
+        hooks, ptrs, mask = self.hook_buffers(hook_layers, self.L, lambda i: shape, dev)
         feats = torch.empty((B, Tt, E), dtype=torch.float32, device=dev) if want_features else None
         pooled = torch.empty((B, E), dtype=torch.float32, device=dev) if pooling else None
         _capi.check(_capi.lib().avexhip_eat_forward(self._h, K._ptr(wav), B, T, wav.stride(0) if wav is not None else 0, K._ptr(spec), mask, ptrs,
                                                     K.pool_code(hook_pooled), K._ptr(feats), K._ptr(pooled), {None: 0, "cls": 1, "mean": 2}[pooling],
-                                                    K._ptr(self._ws), self._ws.numel(), K._stream()), "eat_forward")
+                                                    K._ptr(ws), ws.numel(), K._stream()), "eat_forward")
         out: Dict[str, object] = {"hooks": hooks}
         if want_features:
             out["features"] = feats
         if pooling:
             out["pooled"] = pooled
         return out
-
-    def overflow_events(self, sync: bool = True) -> int:
-        total = 0
-        for h in self._handles.values():
-            n = C.c_uint32(0)
-            _capi.check(_capi.lib().avexhip_eat_overflow_count(h, C.byref(n), K._stream(), int(bool(sync))), "eat_overflow_count")
-            total += int(n.value)
-        return total
-
-    def set_profiling(self, enabled: bool) -> None:
-        self._profiling = bool(enabled)
-        for h in self._handles.values():
-            _capi.check(_capi.lib().avexhip_eat_set_profiling(h, int(enabled)), "eat_set_profiling")
-
-    def last_profile(self):
-        return K.handle_profile(_capi.lib().avexhip_eat_last_profile, self._h)
-
-    def close(self) -> None:
-        for h in getattr(self, "_handles", {}).values():
-            _capi.lib().avexhip_eat_destroy(h)
-        self._handles = {}
-        self._h = None
-        self._ws = None
-
-    def __del__(self) -> None:
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass

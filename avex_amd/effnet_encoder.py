@@ -29,7 +29,7 @@ from .synth import EFFNET_B0_STAGES
 __all__ = ["EfficientNetB0Encoder"]
 
 
-class EfficientNetB0Encoder:
+class EfficientNetB0Encoder(K.EncoderHandle):
     """``[B, n_mels, frames]`` fp32 mel images on the GPU -> ``features [B, 1280, H', W']`` (and the reference's hook taps).
     A thin wrapper over the ``avexhip_effnet`` handle (csrc/effnet_handle.cpp): the library owns the (BatchNorm-folded) weights, this
     class the output tensors and the workspace."""
@@ -37,6 +37,7 @@ class EfficientNetB0Encoder:
     def __init__(self, state: Mapping[str, np.ndarray], operand_dtype: str = "f16", prefix: str = "model.", stages: Sequence = EFFNET_B0_STAGES,
                  bn_eps: float = 1e-5, max_chunk_clips: int = 0) -> None:
         _capi.require_gpu()
+        K.EncoderHandle.__init__(self, "effnet")
         self.dtype = operand_dtype
         self.stages = [tuple(int(v) for v in s) for s in stages]
         if len(self.stages) > 8:
@@ -49,12 +50,7 @@ class EfficientNetB0Encoder:
         c.stem_channels, c.head_channels, c.bn_eps = 32, 1280, float(bn_eps)
         c.operand_dtype, c.max_chunk_clips = _capi.dtype_code(operand_dtype), int(max_chunk_clips)
         sub = {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)} if prefix else dict(state)
-        arr, n, keep = K.tensor_table(sub)
-        self._h = _capi.lib().avexhip_effnet_create(C.byref(c), arr, n)
-        del keep
-        if not self._h:
-            raise K.AvexHipError(f"effnet_create failed: {_capi.last_error()}")
-        self._ws: Optional[torch.Tensor] = None
+        self._create(c, sub)
         # hookable convolutions in the reference's order (efficientnet.py:82-114): stem, every block's projection (blocks with an expansion), head
         names = [prefix + "features.0.0"]
         for si, (er, _k, _s, _cin, _cout, n_rep) in enumerate(self.stages, start=1):
@@ -82,51 +78,21 @@ class EfficientNetB0Encoder:
         mel = mel.contiguous()
         B, H, W = mel.shape
         dev = mel.device
-        need = int(_capi.lib().avexhip_effnet_workspace_bytes(self._h, B, H, W))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        hooks: Dict[str, torch.Tensor] = {}
-        ptrs = (C.c_void_p * len(self._tap_names))()
-        mask = 0
+        ws = self._workspace(int(_capi.lib().avexhip_effnet_workspace_bytes(self._h, B, H, W)), dev)
+        slots: Dict[str, int] = {}
         for name in set(hook_layers):
             if name not in self._tap_names:
                 raise ValueError(f"{name!r} is not a hookable layer: {self._tap_names}")
-            i = self._tap_names.index(name)
-            hooks[name] = torch.empty((B,) + self._shape(i, H, W), dtype=torch.float32, device=dev)
-            ptrs[i] = int(hooks[name].data_ptr())
-            mask |= 1 << i
+            slots[name] = self._tap_names.index(name)
+        hooks, ptrs, mask = self.hook_buffers(slots, len(self._tap_names), lambda i: (B,) + self._shape(i, H, W), dev)
         ch, ho, wo = self._shape(-1, H, W)
         feats = torch.empty((B, ch, ho, wo), dtype=torch.float32, device=dev) if want_features else None
         pooled = torch.empty((B, ch), dtype=torch.float32, device=dev) if want_pooled else None
-        _capi.check(_capi.lib().avexhip_effnet_forward(self._h, K._ptr(mel), B, H, W, mask, ptrs, K._ptr(feats), K._ptr(pooled), K._ptr(self._ws),
-                                                       self._ws.numel(), K._stream()), "effnet_forward")
+        _capi.check(_capi.lib().avexhip_effnet_forward(self._h, K._ptr(mel), B, H, W, mask, ptrs, K._ptr(feats), K._ptr(pooled), K._ptr(ws),
+                                                       ws.numel(), K._stream()), "effnet_forward")
         out: Dict[str, object] = {"hooks": hooks}
         if want_features:
             out["features"] = feats                                  # (B, C, H, W) like the reference
         if want_pooled:
             out["pooled"] = pooled
         return out
-
-    def overflow_events(self, sync: bool = True) -> int:
-        n = C.c_uint32(0)
-        _capi.check(_capi.lib().avexhip_effnet_overflow_count(self._h, C.byref(n), K._stream(), int(bool(sync))), "effnet_overflow_count")
-        return int(n.value)
-
-    def set_profiling(self, enabled: bool) -> None:
-        _capi.check(_capi.lib().avexhip_effnet_set_profiling(self._h, int(enabled)), "effnet_set_profiling")
-
-    def last_profile(self):
-        return K.handle_profile(_capi.lib().avexhip_effnet_last_profile, self._h)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _capi.lib().avexhip_effnet_destroy(self._h)
-            self._h = None
-        self._ws = None
-
-    def __del__(self) -> None:
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass

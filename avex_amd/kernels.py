@@ -712,6 +712,116 @@ def pool_code(hook_pooled) -> int:
     return code
 
 
+class EncoderHandle:
+    """What every wrapper over an encoder handle of the library (``avexhip_<family>_*``) owns: the library handles it created
+    (``_handles``, ``_h`` = the one in use), the grow-only workspace tensor (``_ws``), the hook-tap buffers of a forward, and the
+    accessors over every handle it holds.  The library functions are looked up once, here, not per call."""
+
+    def __init__(self, family: str) -> None:
+        L = lib()
+        self._family = family
+        self._handles: Dict[object, int] = {}
+        self._h: Optional[int] = None
+        self._ws: Optional[torch.Tensor] = None
+        self._profiling = False
+        self._lib_create, self._lib_destroy = getattr(L, f"avexhip_{family}_create"), getattr(L, f"avexhip_{family}_destroy")
+        self._lib_overflow_count, self._what_overflow_count = getattr(L, f"avexhip_{family}_overflow_count"), f"{family}_overflow_count"
+        # (the layer stack exports neither of the two)
+        self._lib_set_profiling, self._what_set_profiling = getattr(L, f"avexhip_{family}_set_profiling", None), f"{family}_set_profiling"
+        self._lib_last_profile = getattr(L, f"avexhip_{family}_last_profile", None)
+
+    def _create(self, cfg, state: Mapping[str, object], key=None) -> int:
+        """A library handle from ``(config struct, state dict)``, kept under ``key``; it becomes the one in use."""
+        arr, n, keep = tensor_table(state)
+        h = self._lib_create(C.byref(cfg), arr, n)
+        del keep
+        if not h:
+            raise AvexHipError(f"{self._family}_create failed: {_capi.last_error()}")
+        self._handles[key] = h
+        if self._profiling:
+            check(self._lib_set_profiling(h, 1), self._what_set_profiling)
+        self._h = h
+        return h
+
+    def _workspace(self, need: int, device) -> torch.Tensor:
+        """The workspace tensor, reallocated only to grow (or to move to another device)."""
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = None
+            self._ws = torch.empty((need,), dtype=torch.uint8, device=device)
+        return self._ws
+
+    @staticmethod
+    def hook_buffers(indices, n_slots: int, shape_for, device):
+        """Tap buffers of one forward -> ``(hooks, ptrs, mask)``.  ``indices``: the selected hook slots (already validated), or a
+        ``{key: slot}`` dict when the caller names its taps; ``shape_for(slot)``: the buffer's shape -- callers decide it from
+        ``pool_code(hook_pooled)``, the code the library gets, never from the argument's truthiness ("none" is a true string)."""
+        hooks: Dict[object, torch.Tensor] = {}
+        ptrs = (C.c_void_p * max(n_slots, 1))()
+        mask = 0
+        for key, i in (indices.items() if isinstance(indices, dict) else zip(indices, indices)):
+            hooks[key] = torch.empty(shape_for(i), dtype=torch.float32, device=device)
+            ptrs[i] = int(hooks[key].data_ptr())
+            mask |= 1 << i
+        return hooks, ptrs, mask
+
+    def overflow_events(self, sync: bool = True) -> int:
+        """The sticky range-alarm count over this object's handles (0 = no f16 conversion ever clipped); ``sync`` waits for the current
+        stream first."""
+        total = 0
+        for h in self._handles.values():
+            n = C.c_uint32(0)
+            check(self._lib_overflow_count(h, C.byref(n), _stream(), int(bool(sync))), self._what_overflow_count)
+            total += int(n.value)
+        return total
+
+    def set_profiling(self, enabled: bool) -> None:
+        self._profiling = bool(enabled)
+        for h in self._handles.values():
+            check(self._lib_set_profiling(h, int(enabled)), self._what_set_profiling)
+
+    def last_profile(self) -> List[Tuple[str, float, float]]:
+        return handle_profile(self._lib_last_profile, self._h)
+
+    def close(self) -> None:
+        for h in getattr(self, "_handles", {}).values():
+            self._lib_destroy(h)
+        self._handles = {}
+        self._h = None
+        self._ws = None
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class ResidualPairHandle(EncoderHandle):
+    """EAT's and AVES' residual-stream policy (BEATs' is in beats_model.py): ``residual`` "half" / "f32" fixes one library handle; "auto"
+    keeps one per stream under ``_handles["half" | "f32"]``, each built on first use -- the fp32 stream for calls that hand back
+    un-averaged rows, the operand-type stream for token-mean outputs only."""
+
+    def _set_residual(self, residual) -> None:
+        self.residual = str(residual or "auto").lower()
+        if self.residual != "auto":
+            residual_code(self.residual)      # validates
+
+    def _open(self, family: str, cfg, state: Mapping[str, object], batch_invariant: bool) -> None:
+        EncoderHandle.__init__(self, family)
+        self._c, self._sub, self._batch_invariant = cfg, state, bool(batch_invariant)
+        self._handle_for(frames=self.residual in ("auto", "f32", "fp32", "float32"))      # a bad checkpoint fails here, not in the first forward
+
+    def _handle_for(self, frames: bool) -> int:
+        """The handle whose residual stream this call wants (``frames``: it returns un-averaged rows); ``self._h`` = the last one used."""
+        mode = ("f32" if frames else "half") if self.residual == "auto" else ("half" if residual_code(self.residual) & 1 else "f32")
+        h = self._handles.get(mode)
+        if h is None:
+            self._c.residual_dtype = residual_code(mode, self._batch_invariant)
+            return self._create(self._c, self._sub, mode)
+        self._h = h
+        return h
+
+
 class BeatsGraph:
     """A recorded forward of a ``BeatsEncoder`` at one input shape.  ``wav`` (and ``frame_pad`` when asked for) are the graph's static
     inputs: write the next batch INTO them (``g.wav.copy_(x)``), call ``replay()``, read ``features`` / ``pooled`` / ``hooks[i]`` --
@@ -727,16 +837,8 @@ class BeatsGraph:
         self.frame_pad = torch.zeros((B, Tt), dtype=torch.uint8, device=dev) if with_frame_pad else None
         need = int(lib().avexhip_beats_workspace_bytes(enc._h, B, T))
         self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)      # the graph's own: the encoder's may be reallocated
-        self.hooks: Dict[int, torch.Tensor] = {}
-        self._ptrs = (C.c_void_p * (enc.L + 1))()
-        mask = 0
-        code = pool_code(hook_pooled)      # the buffers are sized by the CODE the library gets ("none" is a true string and code 0)
-        for i in sorted(set(int(x) for x in hook_layers)):
-            if not 0 <= i <= enc.L:
-                raise ValueError(f"hook layer {i} out of range 0..{enc.L}")
-            self.hooks[i] = torch.empty((B, enc.E) if code else (B, Tt, enc.E), dtype=torch.float32, device=dev)
-            self._ptrs[i] = int(self.hooks[i].data_ptr())
-            mask |= 1 << i
+        code = pool_code(hook_pooled)
+        self.hooks, self._ptrs, mask = enc._hook_buffers(hook_layers, code, B, Tt, dev)
         self.features = torch.empty((B, Tt, enc.E), dtype=torch.float32, device=dev) if want_features else None
         self.pooled = torch.empty((B, enc.E), dtype=torch.float32, device=dev) if want_pooled else None
         # the default stream cannot be captured: record on a side stream that follows / is followed by the current one
@@ -782,7 +884,7 @@ class BeatsGraph:
             pass
 
 
-class BeatsEncoder:
+class BeatsEncoder(EncoderHandle):
     """Owns an ``avexhip_beats`` handle built from an fp32 state dict (torch tensors or numpy arrays,
     host or device).  ``forward`` runs the whole path wav -> features / taps / pooled on the current stream."""
 
@@ -816,6 +918,8 @@ class BeatsEncoder:
         the rung that served the last forward, ``None`` = the handle itself; both synchronise after every forward) or ``"ignore"``.
         Environment default: ``AVEX_AMD_ON_OVERFLOW``.  ``hidden_shift``: see ``RETRY_LADDER`` (0 = off)."""
         _capi.require_gpu()
+        EncoderHandle.__init__(self, "beats")
+        self._what_set_profiling = "set_profiling"      # (this one's text is older than the family prefixes)
         self.cfg = dict(cfg)
         self.on_overflow = (on_overflow or os.environ.get("AVEX_AMD_ON_OVERFLOW") or "warn").lower()
         if self.on_overflow not in ("warn", "raise", "retry", "ignore"):
@@ -829,10 +933,12 @@ class BeatsEncoder:
         self.ccfg = make_beats_config(cfg, operand_dtype, max_chunk_clips, residual, self.batch_invariant, hidden_shift)
         self.E = int(cfg["encoder_embed_dim"])
         self.L = int(cfg["encoder_layers"])
-        arr, n, keep = tensor_table(state)
-        self._h = lib().avexhip_beats_create(C.byref(self.ccfg), arr, n)
         self.served_by: Optional[str] = None      # set when the constructor itself had to climb the ladder (weights outside the f16 range)
-        if not self._h and self.on_overflow == "retry" and dtype_code(operand_dtype) == _capi.F16 and "do not fit the f16 range" in _capi.last_error():
+        try:
+            self._create(self.ccfg, state)
+        except AvexHipError:
+            if not (self.on_overflow == "retry" and dtype_code(operand_dtype) == _capi.F16 and "do not fit the f16 range" in _capi.last_error()):
+                raise
             # the retry contract is "a result is always returned": no f16 rung can hold these weights (the shifted ones scale fc2's up), so the
             # handle that serves every batch is the ladder's last rung
             name, mode = self.RETRY_LADDER[-1]
@@ -841,11 +947,7 @@ class BeatsEncoder:
             self._mode = (dtype_code(mode["operand_dtype"]), residual_code(mode["residual"]) & 1, mode["hidden_shift"])
             self._fallback_args = None      # nothing wider exists
             self.served_by = name
-            self._h = lib().avexhip_beats_create(C.byref(self.ccfg), arr, n)
-        del keep
-        if not self._h:
-            raise AvexHipError(f"beats_create failed: {_capi.last_error()}")
-        self._ws: Optional[torch.Tensor] = None
+            self._create(self.ccfg, state)
 
     def _retry(self, msg: str, wav, kw) -> Dict[str, object]:
         """Climb ``RETRY_LADDER``: the first rung wider than this handle whose own alarm stays quiet serves the batch."""
@@ -874,12 +976,14 @@ class BeatsEncoder:
     def num_tokens(self, T: int) -> int:
         return int(lib().avexhip_beats_num_tokens(self._h, T))
 
-    def _workspace(self, B: int, T: int, device) -> torch.Tensor:
-        need = int(lib().avexhip_beats_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = None
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=device)
-        return self._ws
+    def _hook_buffers(self, hook_layers, code: int, B: int, Tt: int, dev):
+        """Tap buffers for ``hook_layers`` (0 = post_extract_proj, i + 1 = layer i's fc2), sized by the pooling CODE the library gets."""
+        layers = sorted(set(int(x) for x in hook_layers))
+        for i in layers:
+            if not 0 <= i <= self.L:
+                raise ValueError(f"hook layer {i} out of range 0..{self.L}")
+        shape = (B, self.E) if code else (B, Tt, self.E)
+        return self.hook_buffers(layers, self.L + 1, lambda i: shape, dev)
 
     def forward(self, wav: torch.Tensor, *, hook_layers: Sequence[int] = (), hook_pooled=False,
                 want_features: bool = True, want_pooled: bool = False, frame_pad: Optional[torch.Tensor] = None
@@ -898,18 +1002,9 @@ class BeatsEncoder:
         if B == 0 or Tt <= 0:
             raise AvexHipError(f"input too short: {T} samples give {Tt} tokens")
         dev = wav.device
-        ws = self._workspace(B, T, dev)
-        hooks: Dict[int, torch.Tensor] = {}
-        ptrs = (C.c_void_p * (self.L + 1))()
-        mask = 0
+        ws = self._workspace(int(lib().avexhip_beats_workspace_bytes(self._h, B, T)), dev)
         code = pool_code(hook_pooled)      # sizes the tap buffers AND goes to the library: never the truthiness of the argument
-        for i in sorted(set(int(x) for x in hook_layers)):
-            if not 0 <= i <= self.L:
-                raise ValueError(f"hook layer {i} out of range 0..{self.L}")
-            shape = (B, self.E) if code else (B, Tt, self.E)
-            hooks[i] = torch.empty(shape, dtype=torch.float32, device=dev)
-            ptrs[i] = int(hooks[i].data_ptr())
-            mask |= 1 << i
+        hooks, ptrs, mask = self._hook_buffers(hook_layers, code, B, Tt, dev)
         feats = torch.empty((B, Tt, self.E), dtype=torch.float32, device=dev) if want_features else None
         pooled = torch.empty((B, self.E), dtype=torch.float32, device=dev) if want_pooled else None
         pad = None
@@ -944,12 +1039,6 @@ class BeatsEncoder:
         return BeatsGraph(self, batch, samples, hook_layers, hook_pooled, want_features, want_pooled, with_frame_pad,
                           device or torch.device("cuda", torch.cuda.current_device()))
 
-    def overflow_events(self, sync: bool = True) -> int:
-        """The handle's sticky range-alarm count (0 = no f16 conversion ever clipped); ``sync`` waits for the current stream first."""
-        n = C.c_uint32(0)
-        check(lib().avexhip_beats_overflow_count(self._h, C.byref(n), _stream(), int(bool(sync))), "beats_overflow_count")
-        return int(n.value)
-
     def reset_overflow(self) -> None:
         check(lib().avexhip_beats_overflow_reset(self._h, _stream()), "beats_overflow_reset")
         torch.cuda.current_stream().synchronize()
@@ -961,29 +1050,9 @@ class BeatsEncoder:
         self._overflow_seen = n
         return max(new, 0)
 
-    def set_profiling(self, enabled: bool) -> None:
-        check(lib().avexhip_beats_set_profiling(self._h, int(enabled)), "set_profiling")
-
-    def last_profile(self) -> List[Tuple[str, float, float]]:
-        names = C.POINTER(C.c_char_p)()
-        ms = C.POINTER(C.c_float)()
-        fl = C.POINTER(C.c_double)()
-        n = C.c_int(0)
-        check(lib().avexhip_beats_last_profile(self._h, C.byref(names), C.byref(ms), C.byref(fl), C.byref(n)), "last_profile")
-        return [(names[i].decode(), float(ms[i]), float(fl[i])) for i in range(n.value)]
-
     def close(self) -> None:
         for enc in list(getattr(self, "_rungs", {}).values()):
             if enc is not None:
                 enc.close()
         self._rungs = {}
-        if getattr(self, "_h", None):
-            lib().avexhip_beats_destroy(self._h)
-            self._h = None
-        self._ws = None
-
-    def __del__(self) -> None:
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        EncoderHandle.close(self)

@@ -231,37 +231,30 @@ class _DeviceProbe(nn.Module):
     def _stack_forward(self, h: torch.Tensor, padding_mask: Optional[torch.Tensor], heads: int, layers: int, ffn: int) -> torch.Tensor:
         """``layers`` post-LN blocks on f16 operands with fp32 accumulation (the transformer probe's default width, 768 / 12 heads / 4
         layers: 4.6 ms per 256 x 496 tokens instead of 46 ms on the fp32 kernels; logits within 1e-3 of them)."""
-        import ctypes as C
         from . import _capi
         names = self._stack_table()
         version = tuple(self.get_buffer(n)._version for n in names.values()) + (str(h.device),)
         if getattr(self, "_stack", None) is None or self._stack_version != version:
             self._stack_close()
+            stack = K.EncoderHandle("stack")
             cfg = _capi.StackConfig()
             cfg.embed_dim, cfg.num_heads, cfg.num_layers, cfg.ffn_dim = h.shape[-1], heads, layers, ffn
             cfg.norm_eps, cfg.activation, cfg.operand_dtype, cfg.max_chunk_clips, cfg.residual_dtype = 1e-5, 3, _capi.F16, 0, 1
             table = {k: self.get_buffer(n).detach().to(device=h.device, dtype=torch.float32).contiguous() for k, n in names.items()}
-            arr, n, keep = K.tensor_table(table)
-            self._stack = _capi.lib().avexhip_stack_create(C.byref(cfg), arr, n)
-            del keep
-            if not self._stack:
-                raise _capi.AvexHipError(f"stack_create failed: {_capi.last_error()}")
-            self._stack_version = version
+            stack._create(cfg, table)
+            self._stack, self._stack_version = stack, version
         B, T, D = h.shape
-        need = int(_capi.lib().avexhip_stack_workspace_bytes(self._stack, B, T))
-        ws = getattr(self, "_stack_ws", None)
-        if ws is None or ws.numel() < need or ws.device != h.device:
-            self._stack_ws = ws = torch.empty((need,), dtype=torch.uint8, device=h.device)
+        stack = self._stack
+        ws = stack._workspace(int(_capi.lib().avexhip_stack_workspace_bytes(stack._h, B, T)), h.device)
         pad = None if padding_mask is None else padding_mask.to(device=h.device, dtype=torch.uint8).contiguous()
         out = torch.empty_like(h)
-        _capi.check(_capi.lib().avexhip_stack_forward(self._stack, K._ptr(h), B, T, K._ptr(pad), K._ptr(out), None, K._ptr(ws), ws.numel(), K._stream()),
+        _capi.check(_capi.lib().avexhip_stack_forward(stack._h, K._ptr(h), B, T, K._ptr(pad), K._ptr(out), None, K._ptr(ws), ws.numel(), K._stream()),
                     "stack_forward")
         return out
 
     def _stack_close(self) -> None:
         if getattr(self, "_stack", None):
-            from . import _capi
-            _capi.lib().avexhip_stack_destroy(self._stack)
+            self._stack.close()
         self._stack = None
 
     def __del__(self) -> None:
