@@ -124,6 +124,18 @@ class SearchResult(C.Structure):
                 ("recording", C.c_void_p), ("start_s", C.c_void_p), ("end_s", C.c_void_p)]
 
 
+class EventsArgs(C.Structure):
+    _fields_ = [("scores", C.c_void_p), ("ld_scores", C.c_int64), ("n_rows", C.c_int64), ("n_windows", C.c_int64), ("n_classes", C.c_int32),
+                ("n_seq", C.c_int32), ("seq_offsets_host", C.c_void_p), ("seq_offsets_dev", C.c_void_p), ("row_of_window", C.c_void_p),
+                ("on", C.c_void_p), ("off", C.c_void_p), ("smooth", C.c_int32), ("smooth_mode", C.c_int32), ("merge_gap", C.c_int32),
+                ("min_windows", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("total", C.c_void_p)]
+
+
+class EventsResult(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("sequence", C.c_void_p), ("class_id", C.c_void_p), ("first", C.c_void_p), ("last", C.c_void_p),
+                ("peak", C.c_void_p), ("peak_window", C.c_void_p), ("mean", C.c_void_p)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -252,6 +264,12 @@ SYMBOLS = {
     "avexhip_search_begin": (C.c_int, [C.POINTER(SearchArgs), _P]),
     "avexhip_search_chunk": (C.c_int, [C.POINTER(SearchArgs), _P]),
     "avexhip_search_finish": (C.c_int, [C.POINTER(SearchArgs), C.POINTER(SearchResult), _P]),
+    "avexhip_events_max_smooth": (C.c_int, []),
+    "avexhip_events_max_span": (C.c_int, []),
+    "avexhip_events_chunk_windows": (C.c_int, []),
+    "avexhip_events_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "avexhip_events_scan": (C.c_int, [C.POINTER(EventsArgs), _P]),
+    "avexhip_events_emit": (C.c_int, [C.POINTER(EventsArgs), C.POINTER(EventsResult), _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

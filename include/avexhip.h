@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 15
+#define AVEXHIP_ABI_VERSION 16
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -536,6 +536,63 @@ int avexhip_search_prepare_rows(const float* rows_dev, int64_t ld_rows, int n, i
 int avexhip_search_begin(const avexhip_search_args* args, void* stream);
 int avexhip_search_chunk(const avexhip_search_args* args, void* stream);
 int avexhip_search_finish(const avexhip_search_args* args, const avexhip_search_result* result, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Event detection (ABI 16): one fp32 score per (window, class) -> events "class c is present in windows first .. last of sequence r".
+ * A sequence is one recording's windows in time order: sequence r holds the windows seq_offsets[r] .. seq_offsets[r + 1] - 1 (empty
+ * sequences are allowed).  Window i reads score row row_of_window[i] (NULL: row i; -1: no score, a NaN from here on).  Per (sequence, class):
+ *   1. smoothing over the positions i - h .. i + h (h = (smooth - 1) / 2) inside the sequence that hold a number: the lower median, or
+ *      the fp32 sum in position order over float(n); none: NaN;
+ *   2. hysteresis from inactive: s >= on[c] sets, !(s >= off[c]) clears (so NaN clears), anything else holds;
+ *   3. an inactive run of at most merge_gap windows strictly between two active runs becomes active;
+ *   4. active runs shorter than min_windows are dropped.
+ * An event is a remaining maximal run: sequence, class_id, first, last (global windows), peak (the largest smoothed score, fp32),
+ * peak_window (the lowest window attaining it), mean (fp64 sum of the smoothed scores that are numbers over their count).  Events are
+ * numbered in the order (sequence, class_id, first) by counting the events in front of each: no sort, no atomics, the same bits on
+ * every run.  *total receives the true number of events; the first `capacity` are written, rows past min(total, capacity) are filled
+ * with -1 / -inf / NaN.  Every decision is an fp32 compare; time is cut into chunks of avexhip_events_chunk_windows() windows that
+ * sequences start and end inside freely.  Nothing here allocates or synchronises.
+ *   avexhip_events_scan   everything up to the counts and *total;
+ *   avexhip_events_emit   the columns, for the workspace a scan with the same arguments left.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float* scores;            /* [n_rows, n_classes] fp32 on the device, row stride ld_scores */
+    int64_t ld_scores;
+    int64_t n_rows;                 /* M; equal to n_windows when row_of_window is NULL */
+    int64_t n_windows;              /* N, 1 .. 2^31 - 1 */
+    int32_t n_classes;              /* C */
+    int32_t n_seq;                  /* R */
+    const int64_t* seq_offsets_host; /* [R + 1], checked here: starts at 0, never decreases, ends at N */
+    const int64_t* seq_offsets_dev;  /* the same numbers on the device */
+    const int32_t* row_of_window;   /* [N] on the device, or NULL */
+    const float* on;                /* [C] on the device */
+    const float* off;               /* [C] on the device, off <= on, no NaN (the caller's promise) */
+    int32_t smooth;                 /* odd, 1 .. avexhip_events_max_smooth() */
+    int32_t smooth_mode;            /* 0 median, 1 mean */
+    int32_t merge_gap;              /* 0 .. avexhip_events_max_span() */
+    int32_t min_windows;            /* 1 .. avexhip_events_max_span() */
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t* total;                 /* out, on the device */
+} avexhip_events_args;
+
+typedef struct {
+    int64_t capacity;               /* rows of the seven columns */
+    int32_t* sequence;
+    int32_t* class_id;
+    int32_t* first;
+    int32_t* last;
+    float* peak;
+    int32_t* peak_window;
+    double* mean;
+} avexhip_events_result;
+
+int avexhip_events_max_smooth(void);        /* 31 */
+int avexhip_events_max_span(void);          /* 64: the largest merge_gap and min_windows */
+int avexhip_events_chunk_windows(void);     /* consecutive windows of one class that one unit of the time-parallel scan covers */
+size_t avexhip_events_workspace_bytes(int64_t n_windows, int n_classes, int n_seq);      /* 0 for a bad shape */
+int avexhip_events_scan(const avexhip_events_args* args, void* stream);
+int avexhip_events_emit(const avexhip_events_args* args, const avexhip_events_result* result, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Clustering metrics (ABI 11): what avex/evaluation/clustering.py computes from cached embeddings -- scikit-learn's
