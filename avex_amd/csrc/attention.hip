@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "attention_plan.h"
 
 namespace {
 
@@ -1043,87 +1044,54 @@ __global__ __launch_bounds__(256) void attention_tail_kernel(const T* __restrict
     }
 }
 
+static_assert(TMAX == avx::ATT_PLAN_TMAX && ATT_LDS == avx::ATT_PLAN_LDS1 && ATT2_LDS == avx::ATT_PLAN_LDS2 && ATT2L_LDS == avx::ATT_PLAN_LDS2L && ATT2X_LDS == avx::ATT_PLAN_LDS2X,
+              "attention_plan.h plans for these kernels");
+
+// the one place that reads the attention path's environment: every knob per launch
+static avx::AttKnobs att_knobs() {
+    avx::AttKnobs k;
+    const char* e;
+    if ((e = getenv("AVEX_AMD_ATT_VARIANT"))) k.variant = atoi(e);
+    if ((e = getenv("AVEX_AMD_ATT_GRID"))) k.grid = atoi(e);
+    if ((e = getenv("AVEX_AMD_ATT_TAIL_ROWS"))) k.tail_rows = atoi(e);
+    k.no_tail = getenv("AVEX_AMD_ATT_NO_TAIL") != nullptr;
+    k.no_xt = getenv("AVEX_AMD_ATT_NO_XT") != nullptr;
+    return k;
+}
+
 template <typename T>
 int launch(const void* qkv, int B, int Tn, int H, const float* bias_tab, const float* grep_w, const float* grep_b,
            const float* grep_a, const uint8_t* key_pad, void* out, int q_log2e, hipStream_t s) {
     static const int dbg = getenv("AVEX_AMD_ATT_DEBUG") ? atoi(getenv("AVEX_AMD_ATT_DEBUG")) : 0;
-    // 1 = stage-then-compute, 2 = persistent streamed (32x32x16 MFMAs), 3 = persistent streamed on 16x16x32 MFMAs (attention16.hip; default up to 512 tokens)
-    int variant = getenv("AVEX_AMD_ATT_VARIANT") ? atoi(getenv("AVEX_AMD_ATT_VARIANT")) : 3;
-    if (Tn > TMAX) variant = 2;          // variants 1 and 3 are built for T <= 512
-    if (variant == 3) {
-        int n_cu = 256;
-        { const int rc_ = avx::device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
-        int n_wg = n_cu;
-        if (const char* fg = getenv("AVEX_AMD_ATT_GRID")) { const int g = atoi(fg); if (g > 0) n_wg = g; }
-        return avx::attention16(qkv, B, Tn, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, __is_same(T, _Float16) ? AVEXHIP_F16 : AVEXHIP_BF16, q_log2e, n_wg, s);
-    }
-    if (variant == 2) {
-        int n_cu = 256;
-        { const int rc_ = avx::device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
-        int n_wg = n_cu;
-        if (const char* fg = getenv("AVEX_AMD_ATT_GRID")) { const int g = atoi(fg); if (g > 0) n_wg = g; }   // tests: several units per workgroup
-        // A last query block of one or two rows (EAT's class token: 513 = 512 + 1) goes to the tail kernel instead of a further query block
-        // of the streamed kernel.  Only that: in a short last block the waves without query rows skip their tiles, so the block is cheap
-        // -- measured at 3 072 (clip, head) items (scripts/att_513.py): 513 tokens 0.441 ms with the tail, 0.491 without; 520 tokens
-        // 0.532 / 0.485; 544 tokens 0.949 / 0.491 (and 1.79 ms with round 2's one-row-per-wave tail up to 32 rows).
-        const int rem = Tn % 512;
-        const int tail_max = getenv("AVEX_AMD_ATT_TAIL_ROWS") ? atoi(getenv("AVEX_AMD_ATT_TAIL_ROWS")) : 2;      // (tests raise it to 32)
-        const bool use_tail = Tn > TMAX && rem > 0 && rem <= tail_max && rem <= 32 && !getenv("AVEX_AMD_ATT_NO_TAIL");
-        const int nqb_main = Tn > TMAX ? (use_tail ? Tn / 512 : (Tn + 511) / 512) : 1;
-        AVX_REQUIRE((int64_t)B * H * nqb_main < (1ll << 31), "attention: too many (item, query block) units");
-        const int n_units = B * H * nqb_main;            // (clip, head, query block of 512) units, dealt to the workgroups in consecutive runs
-        const int per_block = (n_units + n_wg - 1) / n_wg;
-        const int grid = (n_units + per_block - 1) / per_block;
-        if (Tn > TMAX) {
-            // EAT's shape (513 .. 544 tokens, no bias table, the rows beyond 512 in the tail kernel): the main block on variant 3's nine-tile form
-            const bool v3_long = !(getenv("AVEX_AMD_ATT_VARIANT") && atoi(getenv("AVEX_AMD_ATT_VARIANT")) == 2);      // (read per launch: A/B in one process)
-            if (!bias_tab && use_tail && nqb_main == 1 && Tn <= TMAX + 32 && v3_long && !getenv("AVEX_AMD_ATT_NO_XT")) {
-                const int rc3 = avx::attention16(qkv, B, Tn, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, __is_same(T, _Float16) ? AVEXHIP_F16 : AVEXHIP_BF16, q_log2e, n_wg, s);
-                if (rc3 != AVEXHIP_OK) return rc3;
-            } else if (bias_tab) {
-                AVX_ENSURE_LDS((attention2_kernel<T, true, true>), ATT2L_LDS);
-                hipLaunchKernelGGL((attention2_kernel<T, true, true>), dim3(grid), dim3(512), ATT2L_LDS, s, (const T*)qkv, Tn, H, B, per_block, nqb_main, bias_tab,
-                                   grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
-            } else if (Tn % 256 >= 1 && Tn % 256 <= 32 && !getenv("AVEX_AMD_ATT_NO_XT")) {
-                // the 1 .. 32 keys beyond a multiple of 256 ride in the last full key block's phase as a ninth key tile (EAT: 513 keys)
-                AVX_ENSURE_LDS((attention2_kernel<T, true, false, true>), ATT2X_LDS);
-                hipLaunchKernelGGL((attention2_kernel<T, true, false, true>), dim3(grid), dim3(512), ATT2X_LDS, s, (const T*)qkv, Tn, H, B, per_block, nqb_main, bias_tab,
-                                   grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
-            } else {
-                AVX_ENSURE_LDS((attention2_kernel<T, true, false>), ATT2L_LDS);
-                hipLaunchKernelGGL((attention2_kernel<T, true, false>), dim3(grid), dim3(512), ATT2L_LDS, s, (const T*)qkv, Tn, H, B, per_block, nqb_main, bias_tab,
-                                   grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
-            }
-            AVX_LAUNCH_CHECK();
-            if (use_tail) {
-                AVX_REQUIRE((int64_t)B * H * rem < (1ll << 31), "attention: too many tail rows");
-                // rows per wave: as many as the tail has (up to 8) and as fit the LDS (RW x (Tn + 64) floats)
-                int rw = rem >= 8 ? 8 : (rem >= 4 ? 4 : (rem >= 2 ? 2 : 1));
-                while (rw > 1 && sizeof(float) * (size_t)rw * ((size_t)Tn + 65 + 256) > 150 * 1024) rw >>= 1;
-                const size_t lds = sizeof(float) * (size_t)rw * ((size_t)Tn + 65 + 256);      // scores, q, gate, four partial output rows
-                const dim3 tgrid((unsigned)(B * H * ((rem + rw - 1) / rw)));
-#define AVX_TAIL(RWV) do { AVX_ENSURE_LDS((attention_tail_kernel<T, RWV>), 160 * 1024); \
-                hipLaunchKernelGGL((attention_tail_kernel<T, RWV>), tgrid, dim3(256), lds, s, (const T*)qkv, Tn, H, Tn - rem, rem, bias_tab, grep_w, grep_b, \
-                                   grep_a, key_pad, (T*)out, q_log2e); } while (0)
-                if (rw == 8) AVX_TAIL(8); else if (rw == 4) AVX_TAIL(4); else if (rw == 2) AVX_TAIL(2); else AVX_TAIL(1);
-#undef AVX_TAIL
-            }
-        } else if (bias_tab) {
-            AVX_ENSURE_LDS((attention2_kernel<T, false, true>), ATT2_LDS);
-            hipLaunchKernelGGL((attention2_kernel<T, false, true>), dim3(grid), dim3(512), ATT2_LDS, s, (const T*)qkv, Tn, H, B, per_block, 1, bias_tab,
-                               grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
-        } else {
-            AVX_ENSURE_LDS((attention2_kernel<T, false, false>), ATT2_LDS);
-            hipLaunchKernelGGL((attention2_kernel<T, false, false>), dim3(grid), dim3(512), ATT2_LDS, s, (const T*)qkv, Tn, H, B, per_block, 1, bias_tab,
-                               grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
-        }
-        AVX_LAUNCH_CHECK();
-        return AVEXHIP_OK;
-    }
-    AVX_ENSURE_LDS(attention_kernel<T>, ATT_LDS);      // (variant 1 only: behind the dispatch)
-    hipLaunchKernelGGL(attention_kernel<T>, dim3(B * H), dim3(1024), ATT_LDS, s, (const T*)qkv, Tn, H, bias_tab, grep_w,
-                       grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
+    int n_cu = 256;
+    { const int rc_ = avx::device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
+    const avx::AttPlan p = avx::plan_attention(Tn, B, H, bias_tab != nullptr, n_cu, att_knobs());
+    if (p.rc != AVEXHIP_OK) return p.rc;
+#define AVX_ATT2(LONG, BIAS, XT) do { AVX_ENSURE_LDS((attention2_kernel<T, LONG, BIAS, XT>), p.lds); \
+        hipLaunchKernelGGL((attention2_kernel<T, LONG, BIAS, XT>), dim3(p.grid), dim3(p.block), p.lds, s, (const T*)qkv, Tn, H, B, p.per_block, p.nqb_main, bias_tab, \
+                           grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg); } while (0)
+    if (p.kernel == avx::ATT_KERNEL3) {      // attention16.hip: the whole product up to 512 tokens, or the first 512 query rows of up to 544
+        const int rc3 = avx::attention16(qkv, B, Tn, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, __is_same(T, _Float16) ? AVEXHIP_F16 : AVEXHIP_BF16, q_log2e, p, s);
+        if (rc3 != AVEXHIP_OK || !p.use_tail) return rc3;
+    } else if (p.kernel == avx::ATT_KERNEL1) {
+        AVX_ENSURE_LDS(attention_kernel<T>, p.lds);
+        hipLaunchKernelGGL(attention_kernel<T>, dim3(p.grid), dim3(p.block), p.lds, s, (const T*)qkv, Tn, H, bias_tab, grep_w,
+                           grep_b, grep_a, key_pad, (T*)out, q_log2e, dbg);
+    } else if (!p.k_long) {
+        if (p.k_bias) AVX_ATT2(false, true, false); else AVX_ATT2(false, false, false);
+    } else if (p.k_bias) AVX_ATT2(true, true, false);
+    else if (p.k_xt) AVX_ATT2(true, false, true);
+    else AVX_ATT2(true, false, false);
+#undef AVX_ATT2
     AVX_LAUNCH_CHECK();
+    if (p.use_tail) {
+#define AVX_TAIL(RWV) do { AVX_ENSURE_LDS((attention_tail_kernel<T, RWV>), 160 * 1024); \
+        hipLaunchKernelGGL((attention_tail_kernel<T, RWV>), dim3(p.tail_grid), dim3(256), p.tail_lds, s, (const T*)qkv, Tn, H, Tn - p.tail_rows, p.tail_rows, bias_tab, \
+                           grep_w, grep_b, grep_a, key_pad, (T*)out, q_log2e); } while (0)
+        if (p.tail_rw == 8) AVX_TAIL(8); else if (p.tail_rw == 4) AVX_TAIL(4); else if (p.tail_rw == 2) AVX_TAIL(2); else AVX_TAIL(1);
+#undef AVX_TAIL
+        AVX_LAUNCH_CHECK();
+    }
     return AVEXHIP_OK;
 }
 

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "attention_plan.h"
 
 namespace {
 
@@ -680,26 +681,17 @@ __global__ __launch_bounds__(512) void attention3_kernel(const T* __restrict__ q
     }
 }
 
+static_assert(A3_TMAX == avx::ATT_PLAN_TMAX && ATT3_LDS == avx::ATT_PLAN_LDS3 && ATT3X_LDS == avx::ATT_PLAN_LDS3X, "attention_plan.h plans for these kernels");
+
 template <typename T>
 int launch3(const void* qkv, int B, int Tn, int H, const float* bias_tab, const float* grep_w, const float* grep_b, const float* grep_a,
-            const uint8_t* key_pad, void* out, int q_log2e, int n_wg, hipStream_t s) {
-    const int n_units = B * H;
-    const int per_block = (n_units + n_wg - 1) / n_wg;
-    const int grid = (n_units + per_block - 1) / per_block;
+            const uint8_t* key_pad, void* out, int q_log2e, const avx::AttPlan& p, hipStream_t s) {
     const int Tq = Tn < A3_TMAX ? Tn : A3_TMAX;
-    if (Tn > A3_TMAX) {
-        AVX_ENSURE_LDS((attention3_kernel<T, false, true>), ATT3X_LDS);
-        hipLaunchKernelGGL((attention3_kernel<T, false, true>), dim3(grid), dim3(512), ATT3X_LDS, s, (const T*)qkv, Tn, Tq, H, B, per_block, bias_tab, grep_w,
-                           grep_b, grep_a, key_pad, (T*)out, q_log2e);
-    } else if (bias_tab) {
-        AVX_ENSURE_LDS((attention3_kernel<T, true>), ATT3_LDS);
-        hipLaunchKernelGGL((attention3_kernel<T, true>), dim3(grid), dim3(512), ATT3_LDS, s, (const T*)qkv, Tn, Tq, H, B, per_block, bias_tab, grep_w, grep_b,
-                           grep_a, key_pad, (T*)out, q_log2e);
-    } else {
-        AVX_ENSURE_LDS((attention3_kernel<T, false>), ATT3_LDS);
-        hipLaunchKernelGGL((attention3_kernel<T, false>), dim3(grid), dim3(512), ATT3_LDS, s, (const T*)qkv, Tn, Tq, H, B, per_block, bias_tab, grep_w, grep_b,
-                           grep_a, key_pad, (T*)out, q_log2e);
-    }
+#define AVX_ATT3(BIAS, XT) do { AVX_ENSURE_LDS((attention3_kernel<T, BIAS, XT>), p.lds); \
+        hipLaunchKernelGGL((attention3_kernel<T, BIAS, XT>), dim3(p.grid), dim3(p.block), p.lds, s, (const T*)qkv, Tn, Tq, H, B, p.per_block, bias_tab, grep_w, grep_b, \
+                           grep_a, key_pad, (T*)out, q_log2e); } while (0)
+    if (p.k_xt) AVX_ATT3(false, true); else if (p.k_bias) AVX_ATT3(true, false); else AVX_ATT3(false, false);
+#undef AVX_ATT3
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
 }
@@ -711,11 +703,11 @@ namespace avx {
 // Variant 3: called by avx::attention (attention.hip), which has validated the arguments.  T <= 512: the whole product.  512 < T <= 544 without a
 // bias table (EAT's 513 tokens): query rows 0 .. 511 against all T keys (nine-tile last phase); the caller computes the rows beyond with the tail kernel.
 int attention16(const void* qkv, int B, int T, int H, const float* bias_tab, const float* grep_w, const float* grep_b, const float* grep_a,
-                const uint8_t* key_pad, void* out, int dtype, int q_log2e, int n_wg, hipStream_t s) {
+                const uint8_t* key_pad, void* out, int dtype, int q_log2e, const AttPlan& p, hipStream_t s) {
     AVX_REQUIRE(T > 0 && (T <= A3_TMAX || (T <= A3_TMAX + 32 && !bias_tab)), "attention16: T=%d tokens (1..512, or up to 544 without a bias table)", T);
     AVX_REQUIRE((int64_t)B * H < (1ll << 31), "attention16: too many (clip, head) items");
-    if (dtype == AVEXHIP_F16) return launch3<_Float16>(qkv, B, T, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, q_log2e, n_wg, s);
-    if (dtype == AVEXHIP_BF16) return launch3<__bf16>(qkv, B, T, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, q_log2e, n_wg, s);
+    if (dtype == AVEXHIP_F16) return launch3<_Float16>(qkv, B, T, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, q_log2e, p, s);
+    if (dtype == AVEXHIP_BF16) return launch3<__bf16>(qkv, B, T, H, bias_tab, grep_w, grep_b, grep_a, key_pad, out, q_log2e, p, s);
     avexhip_set_error("attention16: unknown dtype %d", dtype);
     return AVEXHIP_ERR_INVALID;
 }

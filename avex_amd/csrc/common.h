@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/avexhip.h"
+#include "gemm_args.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -344,71 +345,6 @@ int ensure_max_dynamic_lds(const void* func, int bytes);
 int device_cu_count(int* n_cu);
 #define AVX_ENSURE_LDS(kernel, bytes) do { const int rc_ = avx::ensure_max_dynamic_lds((const void*)(kernel), (int)(bytes)); if (rc_ != AVEXHIP_OK) return rc_; } while (0)
 
-struct GemmArgs {
-    const void* A; int64_t lda;
-    const void* W; int64_t ldw;
-    int M, N, K;
-    const float* bias;
-    const float* resid; int64_t ldr; float alpha;
-    const void* resid_half; int64_t ldrh;   // residual in the operand type (used when resid == NULL)
-    int gelu;
-    float* out_f32; int64_t ldo;
-    void* out_half; int64_t ldh;
-    float* out_raw; int64_t ldraw;
-    const uint8_t* row_zero;  // optional [M] mask: rows with 1 store zeros to every output
-    float half_scale;         // 0 or 1: off.  Otherwise out_half receives value * half_scale (a power of two: the third rung of the f16 range ladder stores
-                              // fc1's hidden activations scaled down and folds the inverse into fc2's weights); generic epilogues only, fp32 outputs unscaled
-    int variant;
-    // ---- LayerNorm folded into the GEMMs around it (256-tile streaming kernel) --------------------------------------
-    // A tensor y that is only ever consumed through LayerNorm is kept RAW in the operand type.  The GEMM that produces y writes
-    // per-row partial statistics [M][N/64][2] = (sum, sum of squares) of each 64-column segment (stats_out); avx::ln_rowstats
-    // reduces them, in a fixed order, to one (rstd, -mu * rstd) pair per row; the consumers take those pairs:
-    //  * consumer of LN(y) as its A operand:  A = y, W = W * diag(gamma) (folded by the caller), ln_s[n] = sum_k W'[n][k],
-    //    bias = b + W beta;  the epilogue forms  rstd[m] * acc + ((-mu rstd)[m] * ln_s[n] + bias[n])  before GELU / rounding;
-    //  * consumer of LN(y) as its residual:  out = alpha * ((y * rstd - mu rstd) * gamma + beta) + acc + bias;
-    //  * producer: stats_out receives the partial statistics of the rows it writes (from the fp32 values before rounding).
-    const float* ln_rows;     // consumer-as-A: [M rounded up to 256][2] (rstd, -mu * rstd) of the A rows, or NULL
-    const float* ln_s;        // [N]
-    const void* lnr_y;        // consumer-as-residual: raw residual rows (half), or NULL
-    int ldy;
-    const float* lnr_rows;    // [M][2] (rstd, -mu * rstd) of the residual rows
-    const float* lnr_gamma;   // [N]
-    const float* lnr_beta;    // [N]
-    int lnr_prefolded;        // lnr_gamma holds alpha * gamma and lnr_beta holds alpha * beta + bias (what the kernel takes; avx::lnr_fold makes them).
-                              // avx::gemm folds per launch when the flag is clear; callers that launch the same fold repeatedly keep the vectors
-    float* stats_out;         // [M][N/64][2] or NULL
-    // The finished row statistics instead of (or beside) the partial ones: rows_out[m] = (rstd, -mu rstd) of output row m with rows_eps inside
-    // the root -- what avx::ln_rowstats makes of stats_out, same bits: avx::gemm writes the partials to stats_out (required, as scratch) and
-    // launches ln_rowstats itself.  Readable / writable up to M rounded up to even.
-    float* rows_out; float rows_eps;
-    // Mean-pooled hook tap without the tap: the rows are clips of pool_T (>= 64) consecutive rows; each 64-row block writes the column
-    // sums of acc + bias (what out_raw would hold) over its rows, split at the one clip boundary it can contain:
-    // pool_part[block][slot][N], slot 0 = the clip of the block's first row, slot 1 = the next clip.  avx::pool_reduce adds a clip's
-    // blocks in order and divides by pool_T.  256-tile kernel, generic epilogue.
-    float* pool_part; int pool_T;
-    int pool_mode;            // 0: column sums (mean after pool_reduce); 1: column maxima; 2: each clip's FIRST row, written straight to pool_part = [clips][N]
-    // 0, or the number of leading output columns that exist in memory (a multiple of 4, < N): the product is computed for N (a multiple of
-    // the tile width, W and bias padded by the caller) but rows of every output / residual are only n_store wide.  128-tile kernels.
-    int n_store;
-    // skinny kernel (variant 7): A[m][k] *= a_scale[(m / a_scale_rows) * a_scale_ld + k] (fp32 product rounded to the operand type) as the rows
-    // are loaded: a per-(clip, channel) rescale of the input without a pass of its own (EfficientNet's squeeze-excitation)
-    const float* a_scale; int a_scale_rows; int a_scale_ld;
-    // 128-tile LDS-DMA kernel: scratch for split-K (fp32 partial products [S][M][N]), or NULL.  With it a product of <= 64 tiles and
-    // K >= 1024 is split S <= 8 ways along K and finished by splitk_epilogue_kernel (partials added in order).
-    float* splitk_ws; size_t splitk_bytes;
-    // A LayerNorm of the output rows y (after bias / residual) in the same pass: the workspace path above with an epilogue kernel that owns
-    // whole rows (one wave per row, N <= 1024, N % 256 == 0, no activation): post_ln_out_* = LN(y) * post_ln_w + post_ln_b; y itself still
-    // goes to out_f32 / out_half when those are set.  post_ln_round: y is rounded to the operand type before the statistics -- what a
-    // LayerNorm kernel reading a half residual stream sees.  For the few-row products of one to eight clips, where a kernel less per
-    // LayerNorm is 13 us less (avx::gemm_post_ln_ok says whether a product qualifies).
-    const float* post_ln_w; const float* post_ln_b; float post_ln_eps; int post_ln_round;
-    float* post_ln_out_f32; int64_t post_ln_ldo; void* post_ln_out_half; int64_t post_ln_ldh;
-    // sticky range alarm: the number of (lane, launch) pairs that rounded at least one |value| > 65504 to an f16 output is added
-    // here (one atomic per wave at most, at the end of the kernel); NULL = not counted.  bf16 outputs cannot overflow.
-    unsigned int* ovf;
-    int tile_order;           // 256-tile kernel: 0 = grouped walk where K < 2048 (default), 1 = row-major, >= 2 = grouped walk with that many row panels per group
-    int nt;                   // set by the launcher: bit 0 non-temporal output stores (256-tile kernels)
-};
 int gemm(const GemmArgs& a, int dtype, hipStream_t s);
 // fp32 NHWC rows [B * HW, ld] -> NCHW [B, C, HW], optionally undoing a folded BatchNorm: (x - shift[c]) / scale[c] (effnet.hip)
 int nhwc_to_nchw(const float* in, int64_t ld, int B, int HW, int C, const float* scale, const float* shift, float* out, hipStream_t s);
@@ -455,18 +391,24 @@ int zero_rows(float* x32, int64_t ld32, void* x_half, int64_t ldh, int M, int C,
 // final LayerNorm + mean over tokens in one pass (half rows in, [B, C] fp32 out); C % 8 == 0, C <= 768
 int layernorm_pool(const void* in_half, int64_t ld_in, const float* w, const float* b, float eps, int B, int T, int C, float* out, int dtype,
                    hipStream_t s);
-// q_log2e != 0: the Q columns of qkv already carry log2(e) (folded into W_q / b_q in fp32 by the handles); the kernel then scales by the
-// exact 1/8 only and feeds the gate with weights divided by log2(e)
+// Questions to the GEMM planner (gemm_plan.h: the rules avx::gemm itself plans with, under the environment's knobs).
 // avx::gemm's choice for a plain product (variant 0, no folded LayerNorm, no pooled tap): the 256-tile streaming kernel (true) or the 128-tile one
 bool gemm_streams(int M, int N);
 // whether a product (M, N, K set; splitk_ws lent) can take GemmArgs::post_ln_*
 bool gemm_post_ln_ok(const GemmArgs& a);
+// whether a caller may lay a product's operands out for the skinny kernel (K, N among its widths, the kernel not switched off) and force variant 7
+bool gemm_skinny_takes(int K, int N);
+// whether the streaming kernel can take this product (what a caller that pins variant 5 must know: otherwise the 128-tile kernel runs)
+bool gemm_streaming_takes(const GemmArgs& a);
+// q_log2e != 0: the Q columns of qkv already carry log2(e) (folded into W_q / b_q in fp32 by the handles); the kernel then scales by the
+// exact 1/8 only and feeds the gate with weights divided by log2(e)
 int attention(const void* qkv, int B, int T, int H, const float* bias_tab, const float* grep_w,
               const float* grep_b, const float* grep_a, const uint8_t* key_pad, void* out, int dtype,
               hipStream_t s, int q_log2e = 0);
-// variant 3 of the same (attention16.hip: 16x16x32 MFMAs, up to 512 tokens); avx::attention dispatches to it
+// variant 3 of the same (attention16.hip: 16x16x32 MFMAs, up to 512 tokens); avx::attention dispatches to it with its plan (attention_plan.h)
+struct AttPlan;
 int attention16(const void* qkv, int B, int T, int H, const float* bias_tab, const float* grep_w, const float* grep_b, const float* grep_a,
-                const uint8_t* key_pad, void* out, int dtype, int q_log2e, int n_wg, hipStream_t s);
+                const uint8_t* key_pad, void* out, int dtype, int q_log2e, const AttPlan& plan, hipStream_t s);
 int attention_hd(const void* qkv, int B, int T, int H, int head_dim, const uint8_t* key_pad, void* out, int dtype, hipStream_t s, int q_log2e = 0);
 int posconv_pack(const float* g, const float* v, int E, int groups, int K, void* w_packed, int dtype,
                  hipStream_t s);

@@ -30,7 +30,6 @@ using avxh::Table;
 namespace {
 
 inline int pad128(int c) { return ((c + 127) / 128) * 128; }
-inline bool skinny_enabled() { const char* e = getenv("AVEX_AMD_GEMM_SKINNY"); return !(e && atoi(e) == 0) && !getenv("AVEX_AMD_GEMM_VARIANT"); }
 // channels of an activation tensor in memory: 64 for the narrow block outputs of the first stages (at the largest spatial sizes: padded
 // to 128 they were 3 - 8x their size), else a multiple of 128; block outputs of <= 32 channels are 32 wide where every consumer takes
 // K = 32 (effnet_build: narrow_ok).  GEMM outputs narrower than the 128-column tile
@@ -40,9 +39,8 @@ inline int padc(int c) { return c <= 64 ? 64 : pad128(c); }
 // (padded to 128 / 256 the 144-channel tensors were 44 % padding)
 inline int padx(int c) {
     const int p32 = ((c + 31) / 32) * 32;
-    return (skinny_enabled() && (p32 == 96 || p32 == 160)) ? p32 : padc(c);
+    return ((p32 == 96 || p32 == 160) && avx::gemm_skinny_takes(p32, p32)) ? p32 : padc(c);
 }
-inline bool skinny_dim(int d) { return d == 32 || d == 64 || d == 96 || d == 128 || d == 160 || d == 256; }
 
 struct Block {
     int k = 3, stride = 1, cin = 0, cexp = 0, cout = 0, cs = 0;     // cs: squeeze width
@@ -154,10 +152,10 @@ int effnet_build(avexhip_effnet* h, const avexhip_tensor* tensors, int n) {
             plan.push_back({c.stage[si][0] != 1, st == 1 && ci == c.stage[si][4], ci * c.stage[si][0], c.stage[si][4]});
         }
     std::function<bool(size_t, int)> narrow_ok = [&](size_t idx, int ch) -> bool {
-        if (ch > 32 || !skinny_enabled() || idx >= plan.size()) return false;
+        if (ch > 32 || !avx::gemm_skinny_takes(32, 32) || idx >= plan.size()) return false;
         const Bl& n = plan[idx];
         if (n.res && !narrow_ok(idx + 1, n.cout)) return false;
-        if (n.ex) { const int ce = padx(n.cexp); return skinny_dim(ce) && ce * 32 <= 32768; }
+        if (n.ex) return avx::gemm_skinny_takes(32, padx(n.cexp));
         return pad128(n.cout) <= 256;
     };
     h->cp0 = narrow_ok(0, h->c0) ? 32 : ((h->c0 + 63) / 64) * 64;
@@ -376,7 +374,7 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
                 avxh::gemm_init(g, h);
                 g.A = w.act[in_buf]; g.lda = b.cp_in; g.W = b.w_exp; g.ldw = b.cp_in; g.M = M_in; g.N = pad128(b.cexp); g.K = b.cp_in; g.bias = b.b_exp; g.gelu = 2;
                 g.out_half = w.act[o]; g.ldh = b.cp_exp; g.n_store = b.cp_exp < g.N ? b.cp_exp : 0;
-                if (skinny_enabled() && skinny_dim(b.cp_in) && skinny_dim(b.cp_exp) && b.cp_exp != 32 && b.cp_exp * b.cp_in <= 32768) {
+                if (b.cp_exp != 32 && avx::gemm_skinny_takes(b.cp_in, b.cp_exp)) {
                     g.N = b.cp_exp; g.n_store = 0; g.variant = 7;      // whatever the row count: the 128-tile kernels take neither K = 32 nor 96 / 160 columns
                 }
                 prof.begin("gemm.expand", 2.0 * M_in * (double)b.cexp * b.cin);
@@ -405,7 +403,7 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
             // long thin projections run in the skinny streaming kernel, which applies the squeeze-excitation scale to its A rows as it loads
             // them: the rescale pass over the expanded tensor (read + write) disappears
             static const bool no_se_fold = getenv("AVEX_AMD_SE_FOLD") && atoi(getenv("AVEX_AMD_SE_FOLD")) == 0;
-            const bool skinny_proj = skinny_enabled() && skinny_dim(b.cp_exp) && pad128(b.cout) * b.cp_exp <= 32768 && (b.cp_out == 32 || b.cp_out == 64 || b.cp_out == 128 || b.cp_out == 256);
+            const bool skinny_proj = avx::gemm_skinny_takes(b.cp_exp, b.cp_out);      // (cp_out is 32, 64 or a multiple of 128: 128 and 256 are pad128(cout))
             bool se_fold = skinny_proj && (!no_se_fold || hooked);      // (the skinny kernel's raw tap comes with the scale)
             // the wider projections (K = 512 ... 1152): the register-staged form of the 128-tile kernel scales its A rows the same way
             static const bool se_fold_wide = !(getenv("AVEX_AMD_SE_FOLD_WIDE") && atoi(getenv("AVEX_AMD_SE_FOLD_WIDE")) == 0);

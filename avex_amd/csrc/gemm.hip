@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "gemm_epi.h"
+#include "gemm_plan.h"
 
 // The kernels of this file set MODE.FP16_OVFL around their epilogues (NOT while their MFMAs run: common.h), so their f16 outputs
 // saturate in hardware instead of through a v_med3_f32 per element (profiles/r04u_fp16_ovfl.txt)
@@ -407,12 +408,6 @@ static __device__ __forceinline__ void st_out(V* ptr, const V& v, int nt) {
     else *ptr = v;
 }
 // (buf_rsrc, buf_st16, buf_ld16 -- raw-buffer access of the fast epilogues -- live in gemm_epi.h)
-// AVEX_AMD_GEMM_NT: 0 no hints, 1 (default) non-temporal output stores, 5 = only for outputs wider than 768 columns (diagnostics)
-static int gemm_nt_mode(const avx::GemmArgs& a) {
-    static const int mode = getenv("AVEX_AMD_GEMM_NT") ? atoi(getenv("AVEX_AMD_GEMM_NT")) : 1;
-    if ((mode & 4) && a.N <= 768) return 0;
-    return mode & 1;
-}
 // (KT0: the first K-tile of an output tile -- its first MFMA per accumulator takes a literal zero as C, so the 128 accumulator registers are
 // never zeroed by v_mov_b32.)  The 4 x 4 MFMA grid is walked boustrophedon so that consecutive MFMAs share one operand register (the B
 // fragment stays when the A fragment changes): operand toggling is worth a few percent of MFMA power (profiles/r01h_mfma_power.txt)
@@ -993,9 +988,9 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
 }
 
 template <typename T, int EPI, int LN, int ACT = 0>
-static int launch256(const avx::GemmArgs& a5, int grid, hipStream_t s) {
+static int launch256(const avx::GemmPlan& p, hipStream_t s) {
     AVX_ENSURE_LDS((gemm256p_kernel<T, EPI, LN, ACT>), LDS5);
-    hipLaunchKernelGGL((gemm256p_kernel<T, EPI, LN, ACT>), dim3(grid), dim3(512), LDS5, s, a5);
+    hipLaunchKernelGGL((gemm256p_kernel<T, EPI, LN, ACT>), dim3(p.grid_x), dim3(p.block), p.lds, s, p.args);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
 }
@@ -1144,169 +1139,83 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const avx::GemmArgs p)
     ovf_commit<T>(p.ovf, ovf_mx);
 }
 
+static_assert(BM == avx::PLAN_BM && BN == avx::PLAN_BN && BK == avx::PLAN_BK && T2 == avx::PLAN_T2 && 2 * 2 * TILE_BYTES == avx::PLAN_LDS128 && LDS5 == avx::PLAN_LDS256 &&
+                  AVEXHIP_OK == avx::PLAN_OK && AVEXHIP_ERR_INVALID == avx::PLAN_INVALID, "gemm_plan.h plans for these kernels");
+
 template <typename T, int NT, int KS, bool SCALE, bool RAW>
-static int launch_skinny(const avx::GemmArgs& a, hipStream_t s) {
-    int n_cu = 256;
-    { const int rc_ = avx::device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
-    const size_t lds = (size_t)NT * 16 * KS * 32 * 2;
+static int launch_skinny(const avx::GemmPlan& p, hipStream_t s) {
     AVX_ENSURE_LDS((gemm_skinny_kernel<T, NT, KS, SCALE, RAW>), 64 * 1024);
-    const int64_t nblk = ((int64_t)a.M + 127) / 128;
-    int per_cu = (int)(128 * 1024 / (lds > 16384 ? lds : 16384));      // workgroups per CU the LDS (and ~100 registers per lane) allows
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    int64_t grid = (int64_t)n_cu * per_cu;
-    grid = grid < nblk ? grid : nblk;
-    hipLaunchKernelGGL((gemm_skinny_kernel<T, NT, KS, SCALE, RAW>), dim3((unsigned)grid), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((gemm_skinny_kernel<T, NT, KS, SCALE, RAW>), dim3(p.grid_x), dim3(p.block), p.lds, s, p.args);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
 }
 
-// does the skinny kernel take this product?  (half output only, no fp32 / raw outputs, no folded LayerNorm, no row mask)
-static bool skinny_ok(const avx::GemmArgs& a) {
-    if (!(a.K == 32 || a.K == 64 || a.K == 96 || a.K == 128 || a.K == 160 || a.K == 256) ||
-        !(a.N == 32 || a.N == 64 || a.N == 96 || a.N == 128 || a.N == 160 || a.N == 256) || a.N * a.K > 32768) return false;
-    if (!a.out_half || a.out_f32 || a.resid || a.row_zero || a.ln_rows || a.lnr_y || a.stats_out || a.pool_part) return false;
-    if (a.half_scale != 0.f && a.half_scale != 1.f) return false;
-    if (a.lda % 8 || a.ldw % 8 || a.ldh % 8 || (a.resid_half && a.ldrh % 8) || (a.out_raw && a.ldraw % 4) || (a.n_store > 0 && a.n_store % 16)) return false;
-    return true;
-}
-
+// the plan's skinny instantiation (AVX_SKINNY_SHAPES: the list the planner checked the shape against)
 template <typename T>
-static int launch_skinny_any(const avx::GemmArgs& a, hipStream_t s) {
-    // the raw fp32 tap exists for the projection widths (N = 64, 128, 256) in one form: with the A-row scale (a NULL a_scale is refused)
-#define AVX_SK(NTV, KSV) if (a.N == NTV * 16 && a.K == KSV * 32) { \
-        if (a.out_raw) { \
-            if constexpr (NTV == 2 || NTV == 4 || NTV == 8 || NTV == 16) { if (a.a_scale) return launch_skinny<T, NTV, KSV, true, true>(a, s); } \
-            avexhip_set_error("gemm: the skinny kernel writes a raw tap only for N = 32 / 64 / 128 / 256 with a_scale (N=%d)", a.N); return AVEXHIP_ERR_INVALID; \
-        } \
-        return a.a_scale ? launch_skinny<T, NTV, KSV, true, false>(a, s) : launch_skinny<T, NTV, KSV, false, false>(a, s); }
-    AVX_SK(4, 1); AVX_SK(8, 1); AVX_SK(4, 2); AVX_SK(4, 4); AVX_SK(4, 8); AVX_SK(8, 2); AVX_SK(8, 4); AVX_SK(8, 8); AVX_SK(16, 2); AVX_SK(16, 4);
-    AVX_SK(6, 2); AVX_SK(4, 3); AVX_SK(8, 3); AVX_SK(10, 2); AVX_SK(4, 5); AVX_SK(8, 5);      // EfficientNet's 96- and 144 (-> 160)-channel expansions
-    AVX_SK(2, 1); AVX_SK(2, 2); AVX_SK(2, 3); AVX_SK(2, 4); AVX_SK(2, 5); AVX_SK(2, 8); AVX_SK(6, 1); AVX_SK(10, 1); AVX_SK(16, 1);      // ... and its 16- and 24-channel block outputs kept at 32 channels in memory
+static int launch_skinny_any(const avx::GemmPlan& p, hipStream_t s) {
+#define AVX_SK(NTV, KSV) if (p.sk_nt == NTV && p.sk_ks == KSV) { \
+        if constexpr (avx::gemm_skinny_has_raw(NTV)) { if (p.sk_raw) return launch_skinny<T, NTV, KSV, true, true>(p, s); } \
+        return p.sk_scale ? launch_skinny<T, NTV, KSV, true, false>(p, s) : launch_skinny<T, NTV, KSV, false, false>(p, s); }
+    AVX_SKINNY_SHAPES(AVX_SK)
 #undef AVX_SK
-    avexhip_set_error("gemm: no skinny instantiation for N=%d K=%d", a.N, a.K);
-    return AVEXHIP_ERR_INVALID;
+    return AVEXHIP_ERR_INVALID;      // (not reached: plan_gemm refuses a shape outside the list)
 }
 
+// ... and its streaming instantiation gemm256p_kernel<T, EPI, LN, ACT>
 template <typename T>
-int launch(const avx::GemmArgs& a, hipStream_t s) {
-    if (a.variant == 8) {      // the number of a removed full-row kernel that gave variant 5's bits: another name of variant 5
-        avx::GemmArgs b = a;
-        b.variant = 5;
-        return launch<T>(b, s);
+static int launch256_any(const avx::GemmPlan& p, hipStream_t s) {
+    switch (p.epi * 100 + p.ln * 10 + p.act) {
+#define AVX_256(EPI, LN, ACT) case EPI * 100 + LN * 10 + ACT: return launch256<T, EPI, LN, ACT>(p, s);
+        AVX_256(1, 0, 0) AVX_256(1, 0, 1) AVX_256(1, 0, 2) AVX_256(1, 1, 0) AVX_256(1, 1, 1) AVX_256(1, 1, 2)      // half output = act(acc + bias), LN: ln_rows
+        AVX_256(2, 0, 0) AVX_256(2, 1, 0) AVX_256(2, 2, 0) AVX_256(2, 3, 0)                                        // + half residual, LN bit 0: lnr_y, bit 1: stats_out
+        AVX_256(0, 0, 0) AVX_256(0, 1, 0) AVX_256(0, 2, 0) AVX_256(0, 3, 0)                                        // generic, LN: pooled tap mode + 1
+#undef AVX_256
     }
-    // variant 7 / auto for long thin products: the skinny streaming kernel (W resident in LDS, A rows straight into MFMA operands)
-    AVX_REQUIRE(!a.a_scale || ((a.variant == 7 || a.variant == 1) && a.a_scale_rows > 0 && a.a_scale_ld >= a.K && a.a_scale_ld % 4 == 0),
-                "gemm: a_scale is built for the skinny kernel (variant 7) and the register-staged 128-tile kernel (variant 1)");
-    if (a.variant == 7) {
-        AVX_REQUIRE(skinny_ok(a), "gemm: variant 7 (skinny) takes K in {32, 64, 96, 128, 160, 256}, N in {32, 64, 96, 128, 160, 256} with N K <= 32768, a half output (N=%d K=%d)", a.N, a.K);
-        return launch_skinny_any<T>(a, s);
-    }
-    if (a.variant == 0 && a.M >= 32768 && a.K % 64 == 0 && (a.N == 64 || a.N % 128 == 0) && !a.out_raw && skinny_ok(a) &&
-        (a.N % BN != 0 || (!(getenv("AVEX_AMD_GEMM_SKINNY") && atoi(getenv("AVEX_AMD_GEMM_SKINNY")) == 0) && !getenv("AVEX_AMD_GEMM_VARIANT"))))
-        return launch_skinny_any<T>(a, s);
-    if (a.rows_out) {
-        // no kernel below finishes the row statistics: partials to stats_out, then ln_rowstats
-        AVX_REQUIRE(a.stats_out, "gemm: rows_out needs stats_out as scratch");
-        avx::GemmArgs b = a;
-        b.rows_out = nullptr;
-        const int rc = launch<T>(b, s);
-        if (rc != AVEXHIP_OK) return rc;
-        return avx::ln_rowstats(a.stats_out, a.M, a.N / 64, a.rows_eps, a.rows_out, s);
-    }
-    // variant: 0 = auto, 1 = 128-tile register staging, 3 = 128-tile LDS-DMA, 5 (or 2, its tile-per-workgroup ancestor's number) =
-    // the 256-tile streaming kernel
-    int variant = a.variant;
-    const bool ln_fold = a.ln_rows || a.lnr_y || a.stats_out;      // (rows_out was turned into stats_out + ln_rowstats above)
-    if (ln_fold) {
-        // folded LayerNorm exists in the 256-tile kernel only
-        AVX_REQUIRE(a.N % T2 == 0 && a.K >= 2 * BK && (!a.out_half || a.ldh % 8 == 0), "gemm: folded LayerNorm needs N %% 256 == 0 and K >= 128 (N=%d K=%d)", a.N, a.K);
-        AVX_REQUIRE(!a.ln_rows || (a.ln_s && a.bias && a.M >= 2), "gemm: ln_rows needs ln_s and bias");
-        AVX_REQUIRE(!a.lnr_y || (a.lnr_rows && a.lnr_gamma && a.lnr_beta && a.bias && a.lnr_prefolded && a.ldy % 8 == 0 && !a.resid && !a.resid_half),
-                    "gemm: lnr_y needs lnr_rows / gamma / beta / bias and no other residual");
-        AVX_REQUIRE(a.variant == 0 || a.variant == 2 || a.variant == 5, "gemm: folded LayerNorm is built for the 256-tile kernel only");
-        variant = 5;
-    }
-    if (a.n_store > 0 && a.n_store < a.N) {      // narrow outputs: the 128-tile kernels only
-        AVX_REQUIRE(a.n_store % 4 == 0 && !a.ln_rows && !a.lnr_y && !a.stats_out && !a.pool_part, "gemm: n_store=%d needs a multiple of 4 and no folded LayerNorm / pooled tap", a.n_store);
-        if (variant == 0 || variant == 2 || variant == 5) variant = 3;
-    }
-    if (a.pool_part) {
-        AVX_REQUIRE(a.pool_T >= 64 && a.pool_mode >= 0 && a.pool_mode <= 2, "gemm: pool_part needs clips of at least 64 rows (got %d) and pool_mode 0..2 (got %d)", a.pool_T, a.pool_mode);
-        AVX_REQUIRE((a.variant == 0 || a.variant == 2 || a.variant == 5) && a.N % T2 == 0 && a.K >= 2 * BK, "gemm: pool_part is built for the 256-tile kernel only");
-        variant = 5;
-    }
-    if (variant == 0) { static const char* fv = getenv("AVEX_AMD_GEMM_VARIANT"); if (fv) variant = atoi(fv); }
-    if (variant == 0) {
-        // the 256-tile streaming kernel wants enough tiles to occupy the chip: from about half a tile per CU it wins (K = 768 -> N = 2304 at
-        // 3 968 rows, 144 tiles: 26 us against 41), below that the 128-tile kernel does -- four times the tiles, split-K for long contractions
-        // (K = 3072 -> N = 768 at 3 968 rows, 48 tiles: 44 us against 66; scripts/gemm_midsize.py, profiles/r03r_midsize.txt)
-        variant = avx::gemm_streams(a.M, a.N) ? 5 : 3;
-    }
-    if (a.post_ln_w) variant = 3;      // (the caller checked gemm_post_ln_ok)
-    if (variant == 2) variant = 5;
-    if (variant == 5 && (a.K < 2 * BK || a.N % T2 != 0 || (a.out_half && a.ldh % 8) || (a.resid_half && a.ldrh % 8))) variant = 3;
-    if (variant == 5) {
-        int n_cu = 256;
-        { const int rc_ = avx::device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
-        const int tiles = ((a.M + T2 - 1) / T2) * (a.N / T2);
-        avx::GemmArgs a5 = a;
-        const char* eo = getenv("AVEX_AMD_GEMM_TILE_ORDER");      // read per launch: A/B runs switch it inside one process
-        a5.tile_order = eo ? atoi(eo) : 0;
-        a5.nt = gemm_nt_mode(a);
-        int grid = tiles < n_cu ? ((tiles + 7) / 8) * 8 : (n_cu / 8) * 8;
-        if (grid < 8) grid = 8;
-        if (const char* fg = getenv("AVEX_AMD_GEMM_GRID")) { const int g = atoi(fg); if (g >= 8) grid = (g / 8) * 8; }   // tests: force many tiles per workgroup
-        const char* fgen = getenv("AVEX_AMD_GEMM_GENERIC");
-        const bool force_generic = fgen && atoi(fgen) != 0;     // tests: cross-check of the fast epilogues
-        const bool scaled = a.half_scale != 0.f && a.half_scale != 1.f;      // the fast epilogues do not know GemmArgs::half_scale
-        const bool plain_out = a.out_half && a.bias && !a.out_f32 && !a.out_raw && !a.pool_part && !a.resid && !a.row_zero && !force_generic && !scaled;
-        const bool fast_half = plain_out && !a.resid_half && !a.lnr_y && !a.stats_out && (a.gelu <= 2 || a.gelu == 6);      // the fast epilogue knows GELU and SiLU only
-        const bool fast_resid = plain_out && (a.resid_half || a.lnr_y) && !a.gelu && !a.ln_rows;
-        if (fast_half) {
-            if (a.gelu == 1 || a.gelu == 6) return a.ln_rows ? launch256<T, 1, 1, 1>(a5, grid, s) : launch256<T, 1, 0, 1>(a5, grid, s);      // (half output only: both mean the degree-4 fit here)
-            if (a.gelu == 2) return a.ln_rows ? launch256<T, 1, 1, 2>(a5, grid, s) : launch256<T, 1, 0, 2>(a5, grid, s);
-            return a.ln_rows ? launch256<T, 1, 1, 0>(a5, grid, s) : launch256<T, 1, 0, 0>(a5, grid, s);
-        }
-        if (fast_resid) {
-            if (a.lnr_y) return a.stats_out ? launch256<T, 2, 3>(a5, grid, s) : launch256<T, 2, 1>(a5, grid, s);
-            return a.stats_out ? launch256<T, 2, 2>(a5, grid, s) : launch256<T, 2, 0>(a5, grid, s);
-        }
-        if (a.pool_part) {
-            if (a.pool_mode == 0) return launch256<T, 0, 1>(a5, grid, s);
-            if (a.pool_mode == 1) return launch256<T, 0, 2>(a5, grid, s);
-            return launch256<T, 0, 3>(a5, grid, s);
-        }
-        return launch256<T, 0, 0>(a5, grid, s);
-    }
-    const int tiles = ((a.M + BM - 1) / BM) * (a.N / BN);
-    static const char* pad_env = getenv("AVEX_AMD_DEBUG_LDS_PAD");
-    const size_t lds = 2 * 2 * TILE_BYTES + (pad_env ? atoi(pad_env) : 0);
-    AVX_ENSURE_LDS((gemm_nt_kernel<T, false>), 96 * 1024);
-    AVX_ENSURE_LDS((gemm_nt_kernel<T, true>), 96 * 1024);
-    if (variant == 1) {
-        hipLaunchKernelGGL((gemm_nt_kernel<T, false>), dim3(tiles), dim3(256), lds, s, a);
-    } else {
-        // split-K when the caller lent a workspace and the product is few tiles of a long contraction (one clip's fc2: 24 tiles, K = 3072)
-        int S = 1;
-        if (a.post_ln_w) AVX_REQUIRE(avx::gemm_post_ln_ok(a), "gemm: post_ln_* needs the 128-tile kernel's workspace path (N %% 256 == 0, N <= 1024, no activation, splitk_ws >= M N floats)");
-        if (a.splitk_ws && (a.K >= 1024 || a.post_ln_w)) {
-            int n_cu = 256;
-            { const int rc_ = avx::device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
-            S = 8;      // as many splits as keep the launch within two workgroups per CU (and leave every split at least two K-steps)
-            while (S > 1 && (tiles * S > 2 * n_cu || a.K % (S * BK) != 0 || a.K / S < 2 * BK || (size_t)S * a.M * a.N * sizeof(float) > a.splitk_bytes)) S >>= 1;
-        }
-        hipLaunchKernelGGL((gemm_nt_kernel<T, true>), dim3(tiles, S), dim3(256), lds, s, a);
-        if (a.post_ln_w) {
+    return AVEXHIP_ERR_INVALID;      // (not reached)
+}
+
+// plan -> launches
+template <typename T>
+static int execute(const avx::GemmPlan& p, hipStream_t s) {
+    int rc = AVEXHIP_OK;
+    switch (p.family) {
+    case avx::GEMM_SKINNY: return launch_skinny_any<T>(p, s);
+    case avx::GEMM_STREAM: rc = launch256_any<T>(p, s); break;
+    case avx::GEMM_TILE128_REG:
+    case avx::GEMM_TILE128_DMA:
+        AVX_ENSURE_LDS((gemm_nt_kernel<T, false>), 96 * 1024);
+        AVX_ENSURE_LDS((gemm_nt_kernel<T, true>), 96 * 1024);
+        if (p.family == avx::GEMM_TILE128_REG) hipLaunchKernelGGL((gemm_nt_kernel<T, false>), dim3(p.grid_x), dim3(p.block), p.lds, s, p.args);
+        else hipLaunchKernelGGL((gemm_nt_kernel<T, true>), dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, s, p.args);
+        if (p.after != avx::GEMM_AFTER_NONE) {
             AVX_LAUNCH_CHECK();
-            hipLaunchKernelGGL((splitk_ln_epilogue_kernel<T>), dim3((unsigned)((a.M + 3) / 4)), dim3(256), 0, s, a, S);
-        } else if (S > 1) {
-            AVX_LAUNCH_CHECK();
-            const int64_t nthr = (int64_t)a.M * (a.N / 4);
-            hipLaunchKernelGGL((splitk_epilogue_kernel<T>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, a, S);
+            if (p.after == avx::GEMM_AFTER_SPLITK_LN) hipLaunchKernelGGL((splitk_ln_epilogue_kernel<T>), dim3(p.after_grid), dim3(256), 0, s, p.args, p.S);
+            else hipLaunchKernelGGL((splitk_epilogue_kernel<T>), dim3(p.after_grid), dim3(256), 0, s, p.args, p.S);
         }
+        AVX_LAUNCH_CHECK();
+        break;
+    default: return p.rc;
     }
-    AVX_LAUNCH_CHECK();
-    return AVEXHIP_OK;
+    if (rc != AVEXHIP_OK || !p.rows_out) return rc;
+    return avx::ln_rowstats(p.args.stats_out, p.args.M, p.args.N / 64, p.args.rows_eps, p.rows_out, s);
+}
+
+// The one place that reads the GEMM path's environment.  Once per process: GEMM_NT, GEMM_256_MIN_TILES, DEBUG_LDS_PAD.  The others are
+// read per call (tests and A/B runs switch them inside one process), each only by the calls it can matter to -- a clip is about a
+// hundred dependent launches, and a getenv is a walk over the whole environment.
+enum { KNOB_VARIANT = 1, KNOB_SKINNY = 2, KNOB_STREAM = 4, KNOB_POST_LN = 8 };
+static int env_int(const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; }
+static void gemm_knobs(avx::GemmKnobs& k, int which) {
+    static const int nt = env_int("AVEX_AMD_GEMM_NT", 1), min_tiles = env_int("AVEX_AMD_GEMM_256_MIN_TILES", 128), lds_pad = env_int("AVEX_AMD_DEBUG_LDS_PAD", 0);
+    k.nt = nt; k.min_tiles = min_tiles; k.lds_pad = lds_pad;
+    if (which & KNOB_VARIANT) { const char* e = getenv("AVEX_AMD_GEMM_VARIANT"); k.variant_set = e != nullptr; k.variant = e ? atoi(e) : 0; }
+    if (which & KNOB_SKINNY) k.skinny = env_int("AVEX_AMD_GEMM_SKINNY", 1) != 0;
+    if (which & KNOB_STREAM) {
+        k.tile_order = env_int("AVEX_AMD_GEMM_TILE_ORDER", 0);
+        k.grid = env_int("AVEX_AMD_GEMM_GRID", 0);
+        k.generic = env_int("AVEX_AMD_GEMM_GENERIC", 0) != 0;
+    }
+    if (which & KNOB_POST_LN) k.post_ln = env_int("AVEX_AMD_POST_LN", 1) != 0;
 }
 
 }  // namespace
@@ -1314,59 +1223,52 @@ int launch(const avx::GemmArgs& a, hipStream_t s) {
 namespace avx {
 
 bool gemm_streams(int M, int N) {
-    static const int min_tiles = getenv("AVEX_AMD_GEMM_256_MIN_TILES") ? atoi(getenv("AVEX_AMD_GEMM_256_MIN_TILES")) : 128;
-    const int t256 = ((M + T2 - 1) / T2) * (N / T2);
-    return N % T2 == 0 && M >= 1024 && t256 >= min_tiles;
+    GemmKnobs k;
+    gemm_knobs(k, 0);
+    return gemm_rule_streams(M, N, k);
 }
 
 bool gemm_post_ln_ok(const GemmArgs& a) {
-    const char* e = getenv("AVEX_AMD_POST_LN");      // read per call (24 per forward): tests switch it within a process
-    const bool off = e && atoi(e) == 0;
-    return !off && a.splitk_ws && a.N % 256 == 0 && a.N <= 1024 && a.K % BK == 0 && !a.gelu && !a.ln_rows && !a.lnr_y && !a.stats_out && !a.pool_part &&
-           !(a.n_store > 0 && a.n_store < a.N) && (size_t)a.M * a.N * sizeof(float) <= a.splitk_bytes && !gemm_streams(a.M, a.N) &&
-           (a.variant == 0 || a.variant == 3);
+    GemmKnobs k;
+    gemm_knobs(k, KNOB_POST_LN);
+    return gemm_rule_post_ln_ok(a, k);
 }
 
+bool gemm_skinny_takes(int K, int N) {
+    GemmKnobs k;
+    gemm_knobs(k, KNOB_VARIANT | KNOB_SKINNY);
+    return gemm_rule_skinny_takes(K, N, k);
+}
+
+bool gemm_streaming_takes(const GemmArgs& a) { return gemm_rule_streaming_takes(a); }
+
 int gemm(const GemmArgs& a, int dtype, hipStream_t s) {
-    AVX_REQUIRE(a.A && a.W, "gemm: A and W must be non-null");
-    AVX_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
-    AVX_REQUIRE(a.N % BN == 0 || ((a.variant == 7 || (a.variant == 0 && a.N == 64 && a.M >= 32768 && a.K % 64 == 0)) && skinny_ok(a)),
-                "gemm: N=%d must be a multiple of %d (64 columns: the skinny streaming kernel only, >= 32768 rows)", a.N, BN);
-    AVX_REQUIRE(a.K % BK == 0 || (a.K % 32 == 0 && a.variant == 7), "gemm: K=%d must be a multiple of %d (of 32 with the skinny kernel, variant 7)", a.K, BK);
-    AVX_REQUIRE(a.lda % 8 == 0 && a.ldw % 8 == 0, "gemm: lda/ldw must be multiples of 8 elements");
-    AVX_REQUIRE(a.half_scale == 0.f || a.half_scale == 1.f || (a.out_half && !a.stats_out && !a.post_ln_w && !a.pool_part && a.variant != 7 && a.half_scale > 0.f),
-                "gemm: half_scale goes with a plain half output (no row statistics, folded post-LayerNorm, pooled tap or skinny kernel)");
-    AVX_REQUIRE(a.out_f32 || a.out_half || a.out_raw || (a.post_ln_w && (a.post_ln_out_f32 || a.post_ln_out_half)), "gemm: no output buffer");
-    AVX_REQUIRE((!a.out_f32 || a.ldo % 4 == 0) && (!a.out_half || a.ldh % 4 == 0) &&
-                    (!a.out_raw || a.ldraw % 4 == 0) && (!a.resid || a.ldr % 4 == 0) &&
-                    (!a.resid_half || a.ldrh % 4 == 0),
-                "gemm: output/residual leading dims must be multiples of 4 elements");
+    { const int rc_ = gemm_validate(a); if (rc_ != AVEXHIP_OK) return rc_; }
     if (dtype != AVEXHIP_F16 && dtype != AVEXHIP_BF16) {
         avexhip_set_error("gemm: unknown dtype %d", dtype);
         return AVEXHIP_ERR_INVALID;
     }
-    if (a.gelu == 1 && a.out_half && !a.out_f32) {
-        // GELU whose only consumer reads the operand type: the degree-4 fit, in whichever kernel and epilogue form runs (activation code 6)
-        GemmArgs b = a;
-        b.gelu = 6;
-        return gemm(b, dtype, s);
+    int n_cu = 256;
+    { const int rc_ = device_cu_count(&n_cu); if (rc_ != AVEXHIP_OK) return rc_; }
+    // a forced variant asks for no routing knob; a product that ends in the streaming kernel is planned again with that kernel's knobs
+    GemmKnobs k;
+    gemm_knobs(k, (a.variant == 0 ? KNOB_VARIANT : 0) | (gemm_skinny_auto(a) ? KNOB_SKINNY : 0) | (a.post_ln_w ? KNOB_POST_LN : 0));
+    GemmPlan p = plan_gemm(a, n_cu, k);
+    if (p.family == GEMM_STREAM) {      // (the streaming kernel's knobs decide its grid, tile walk and epilogue form, never the family)
+        gemm_knobs(k, KNOB_STREAM);
+        p = plan_gemm(a, n_cu, k);
+        AVX_REQUIRE(p.family == GEMM_STREAM, "gemm: the streaming kernel's knobs changed the kernel family");
     }
-    if (a.lnr_y && !a.lnr_prefolded) {
-        // the kernel takes alpha * gamma and bias + alpha * beta: callers that launch the same fold repeatedly keep those vectors
-        // (lnr_prefolded); for the others they are made here, in stream-ordered scratch
-        AVX_REQUIRE(a.lnr_gamma && a.lnr_beta && a.bias, "gemm: lnr_y needs lnr_gamma, lnr_beta and bias");
-        float* tmp = nullptr;
+    if (p.rc != AVEXHIP_OK) return p.rc;
+    float* tmp = nullptr;
+    if (p.fold_lnr) {      // alpha * gamma and bias + alpha * beta for this launch
         AVX_HIP_CHECK(hipMallocAsync((void**)&tmp, sizeof(float) * 2 * (size_t)a.N, s));
-        GemmArgs b = a;
-        int rc = lnr_fold(a.lnr_gamma, a.lnr_beta, a.bias, a.alpha, a.N, tmp, tmp + a.N, s);
-        if (rc == AVEXHIP_OK) {
-            b.lnr_gamma = tmp; b.lnr_beta = tmp + a.N; b.lnr_prefolded = 1;
-            rc = dtype == AVEXHIP_F16 ? launch<_Float16>(b, s) : launch<__bf16>(b, s);
-        }
-        (void)hipFreeAsync(tmp, s);
-        return rc;
+        p.args.lnr_gamma = tmp; p.args.lnr_beta = tmp + a.N;
     }
-    return dtype == AVEXHIP_F16 ? launch<_Float16>(a, s) : launch<__bf16>(a, s);
+    int rc = p.fold_lnr ? lnr_fold(a.lnr_gamma, a.lnr_beta, a.bias, a.alpha, a.N, tmp, tmp + a.N, s) : AVEXHIP_OK;
+    if (rc == AVEXHIP_OK) rc = dtype == AVEXHIP_F16 ? execute<_Float16>(p, s) : execute<__bf16>(p, s);
+    if (tmp) (void)hipFreeAsync(tmp, s);
+    return rc;
 }
 
 }  // namespace avx

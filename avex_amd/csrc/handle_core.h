@@ -637,7 +637,7 @@ inline int tap_finish(const Tap& t, const CoreCfg& c, const CoreWs& w, const Cor
 // batch-invariant handles: every layer product in the 256-tile streaming kernel whatever its row count (the 128-tile kernel's residual
 // epilogue multiplies and adds where the streaming kernel's fuses, and its split-K adds in another order)
 inline void pin_kernel(const CoreCfg& c, avx::GemmArgs& g) {
-    if (c.batch_invariant && g.variant == 0 && g.N % 256 == 0 && g.K >= 128 && g.M >= 2) g.variant = 5;
+    if (c.batch_invariant && g.variant == 0 && g.M >= 2 && avx::gemm_streaming_takes(g)) g.variant = 5;
 }
 
 inline int self_attention(HandleBase* h, const CoreCfg& c, const Layer& ly, const CoreWs& w, const CoreIo& io, hipStream_t cs) {
@@ -663,221 +663,221 @@ inline int ffn_hidden(HandleBase* h, const CoreCfg& c, const CoreWs& w, avx::Gem
     return rc;
 }
 
+// The residual stream where a product reads or writes it: fp32, or the operand type (fast handles) -- one of the two pointers
+struct Stream { float* f32; void* half; };
+// what the LayerNorm fold (run_layers) changes in a layer's products
+struct Fold {
+    bool on = false;          // y1 / y2 stay raw with row statistics; fc1 and fc2 read LayerNorm 1 through them
+    bool raw_in = false;      // ... and the layer's input is the previous layer's raw y2 (QKV and out_proj read LayerNorm 2 through it)
+    bool last = false;        // the last layer's y2 goes to a LayerNorm kernel that takes its own statistics
+};
+
+// ---- the four products of a layer, each set up in one place ---------------------------------------------------------------------
+// out = alpha * residual + product: the stream in and out; with `lnr_rows` (fold) src holds raw rows whose LayerNorm is the residual, applied on the fly
+inline void residual_args(avx::GemmArgs& g, const CoreCfg& c, Stream src, Stream dst, const float* lnr_rows = nullptr, const float* ga = nullptr, const float* bb = nullptr) {
+    g.alpha = c.alpha;
+    if (dst.half) { g.out_half = dst.half; g.ldh = c.E; } else { g.out_f32 = dst.f32; g.ldo = c.E; }
+    if (lnr_rows) { g.lnr_y = src.half; g.ldy = c.E; g.lnr_rows = lnr_rows; g.lnr_gamma = ga; g.lnr_beta = bb; g.lnr_prefolded = 1; }
+    else if (src.half) { g.resid_half = src.half; g.ldrh = c.E; }
+    else { g.resid = src.f32; g.ldr = c.E; }
+}
+inline void qkv_args(avx::GemmArgs& g, const HandleBase* h, const CoreCfg& c, const Layer& ly, const CoreWs& w, int M, const void* A, const Fold& f) {
+    gemm_init(g, h);
+    g.A = A; g.lda = c.E; g.W = ly.w_qkv; g.ldw = c.E; g.M = M; g.N = 3 * c.E; g.K = c.E; g.bias = ly.b_qkv;
+    g.out_half = w.qkv; g.ldh = 3 * c.E;
+    if (f.raw_in) { g.W = ly.w_qkv_f; g.bias = ly.b_qkv_f; g.ln_rows = w.r2; g.ln_s = ly.s_qkv; }
+}
+inline void out_proj_args(avx::GemmArgs& g, const HandleBase* h, const CoreCfg& c, const Layer& ly, const CoreWs& w, int M, Stream src, Stream dst, const Fold& f) {
+    gemm_init(g, h);
+    g.A = w.ah; g.lda = c.E; g.W = ly.w_o; g.ldw = c.E; g.M = M; g.N = c.E; g.K = c.E; g.bias = ly.b_o;
+    if (f.raw_in) residual_args(g, c, src, dst, w.r2, ly.ga_o, ly.bb_o);
+    else residual_args(g, c, src, dst);
+    if (f.on) { g.stats_out = w.st1; g.rows_out = w.r1; g.rows_eps = c.eps; }      // LN1's row statistics with the product (avx::gemm runs ln_rowstats behind it)
+}
+inline void fc1_args(avx::GemmArgs& g, const HandleBase* h, const CoreCfg& c, const Layer& ly, const CoreWs& w, int M, const void* A, const Fold& f) {
+    gemm_init(g, h);
+    g.A = A; g.lda = c.E; g.W = ly.w_fc1; g.ldw = c.E; g.M = M; g.N = c.F; g.K = c.E; g.bias = ly.b_fc1; g.gelu = c.act;
+    g.out_half = w.hh; g.ldh = c.F;
+    if (f.on) { g.W = ly.w_fc1_f; g.bias = ly.b_fc1_f; g.ln_rows = w.r1; g.ln_s = ly.s_fc1; }
+}
+inline void fc2_args(avx::GemmArgs& g, const HandleBase* h, const CoreCfg& c, const Layer& ly, const CoreWs& w, int M, Stream src, Stream dst, const Fold& f) {
+    gemm_init(g, h);
+    g.A = w.hh; g.lda = c.F; g.W = ly.w_fc2; g.ldw = c.F; g.M = M; g.N = c.E; g.K = c.F; g.bias = ly.b_fc2;
+    if (M <= 8192 && !c.batch_invariant) { g.splitk_ws = w.splitk; g.splitk_bytes = w.splitk_bytes; }      // (split-K adds in another order than one pass over K)
+    if (f.on) {
+        residual_args(g, c, src, dst, w.r1, ly.ga_fc2, ly.bb_fc2);
+        g.stats_out = !f.last ? w.st2 : nullptr;
+    } else residual_args(g, c, src, dst);
+}
+// LayerNorm in the split-K epilogue of the product (one kernel less; the caller asked avx::gemm_post_ln_ok)
+inline void post_ln_args(avx::GemmArgs& g, const CoreCfg& c, const float* ln_w, const float* ln_b, float* out_f32, void* out_half) {
+    g.post_ln_w = ln_w; g.post_ln_b = ln_b; g.post_ln_eps = c.eps; g.post_ln_round = c.fast ? 1 : 0;
+    g.post_ln_out_f32 = out_f32; g.post_ln_ldo = c.E; g.post_ln_out_half = out_half; g.post_ln_ldh = c.E;
+}
+inline int layer_gemm(HandleBase* h, const CoreCfg& c, avx::GemmArgs& g, const char* stage, double flops, Prof& prof, hipStream_t cs) {
+    prof.begin(stage, flops);
+    pin_kernel(c, g);
+    AVXH_TRY(avx::gemm(g, h->dtype, cs));
+    prof.end();
+    return AVEXHIP_OK;
+}
+
+// ---- the outputs of the stack: the final LayerNorm of the stream -> fp32 features and / or their mean over tokens -----------------
+struct Tail {
+    bool fused_pool = false;      // pooled embedding only (the headline path): LayerNorm and the mean over tokens in one pass, no fp32 feature tensor
+    float* xo = nullptr;          // the fp32 features: the caller's buffer, scratch when something reads them, or nowhere
+    bool ln_stage = false;        // a "layernorm" profile stage even where no LayerNorm kernel runs (the post-LN loop without the fold records one per layer)
+};
+inline Tail tail_begin(const CoreCfg& c, const CoreWs& w, const CoreIo& io, bool may_fuse_pool, bool scratch_anyway) {
+    Tail t;
+    t.fused_pool = may_fuse_pool && io.pooled_out && !io.features_out && c.fast && c.E % 8 == 0 && c.E <= 768 && (io.Bc >= 32 || c.batch_invariant);
+    t.xo = io.features_out ? io.features_out + io.c0 * io.Tt * c.E : ((io.pooled_out || scratch_anyway) ? w.x : nullptr);
+    return t;
+}
+// y: the un-normalised stream.  ln_done: the LayerNorm rode in the epilogue of the product that wrote y
+inline int tail_finish(HandleBase* h, const CoreCfg& c, CoreIo& io, const Tail& t, Stream y, const float* ln_w, const float* ln_b, bool ln_done, Prof& prof, hipStream_t cs) {
+    const int E = c.E, M = io.Bc * io.Tt;
+    if (t.fused_pool) {
+        prof.begin("layernorm+mean_pool", 0.0);
+        AVXH_TRY(avx::layernorm_pool(y.half, E, ln_w, ln_b, c.eps, io.Bc, io.Tt, E, io.pooled_out + io.c0 * E, h->dtype, cs));
+        prof.end();
+        return AVEXHIP_OK;
+    }
+    if (t.xo || t.ln_stage) {
+        prof.begin("layernorm", 0.0);
+        if (t.xo && !ln_done) AVXH_TRY(avx::layernorm(y.f32, y.half, E, ln_w, ln_b, c.eps, M, E, t.xo, E, nullptr, E, h->dtype, cs));
+        prof.end();
+    }
+    io.final_f32 = t.xo;
+    if (io.pooled_out) {
+        prof.begin("mean_pool", 0.0);
+        AVXH_TRY(avx::mean_pool(t.xo, io.Bc, io.Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
+        prof.end();
+    }
+    return AVEXHIP_OK;
+}
+
 // Pre-LN blocks (backbone.py:328-348).  The un-normalised stream starts in w.pre (fp32 residual stream) / w.preh (fast) -- where the
 // positional convolution left x + pos_conv(x) -- and is back there after every layer; each LayerNorm writes the GEMM operand to w.ah.
 inline int run_layers_pre_ln(HandleBase* h, const CoreCfg& c, const std::vector<Layer>& layers, const CoreWs& w, CoreIo& io, Prof& prof, hipStream_t cs) {
-    const int E = c.E, F = c.F, H = c.H, L = c.L, dt = h->dtype, Bc = io.Bc, Tt = io.Tt;
-    const int M = Bc * Tt;
+    const int E = c.E, F = c.F, H = c.H, L = c.L, dt = h->dtype, Tt = io.Tt;
+    const int M = io.Bc * Tt;
     const double Md = (double)M;
-    const bool fast = c.fast;
-    float* s0_32 = fast ? nullptr : w.pre;  void* s0_h = fast ? w.preh : nullptr;      // stream at layer boundaries
-    float* s1_32 = fast ? nullptr : w.x;    void* s1_h = fast ? w.xh : nullptr;        // stream after the attention block
+    const Stream s0 = c.fast ? Stream{nullptr, w.preh} : Stream{w.pre, nullptr};      // stream at layer boundaries
+    const Stream s1 = c.fast ? Stream{nullptr, w.xh} : Stream{w.x, nullptr};          // stream after the attention block
+    const Fold no_fold;
     avx::GemmArgs g;
     io.final_f32 = nullptr;
     for (int i = 0; i < L; ++i) {
         const Layer& ly = layers[i];
         prof.begin("layernorm", 0.0);
-        AVXH_TRY(avx::layernorm(s0_32, s0_h, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
+        AVXH_TRY(avx::layernorm(s0.f32, s0.half, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
         prof.end();
-        gemm_init(g, h);
-        g.A = w.ah; g.lda = E; g.W = ly.w_qkv; g.ldw = E; g.M = M; g.N = 3 * E; g.K = E; g.bias = ly.b_qkv;
-        g.out_half = w.qkv; g.ldh = 3 * E;
-        prof.begin("gemm.qkv", 2.0 * Md * 3 * E * E);
-        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
-        prof.end();
+        qkv_args(g, h, c, ly, w, M, w.ah, no_fold);
+        AVXH_TRY(layer_gemm(h, c, g, "gemm.qkv", 2.0 * Md * 3 * E * E, prof, cs));
         prof.begin("attention", 4.0 * Md * Tt * E + (ly.grep_w ? 2.0 * Md * 8 * (E / H) * H : 0.0));
         AVXH_TRY(self_attention(h, c, ly, w, io, cs));
         prof.end();
-        gemm_init(g, h);
-        g.A = w.ah; g.lda = E; g.W = ly.w_o; g.ldw = E; g.M = M; g.N = E; g.K = E; g.bias = ly.b_o; g.alpha = c.alpha;
-        if (fast) { g.resid_half = s0_h; g.ldrh = E; g.out_half = s1_h; g.ldh = E; }
-        else { g.resid = s0_32; g.ldr = E; g.out_f32 = s1_32; g.ldo = E; }
+        out_proj_args(g, h, c, ly, w, M, s0, s1, no_fold);
         Tap tap_o;
         if (c.hook_site == 1) tap_o = tap_begin(c, w, io, i, g);
-        prof.begin("gemm.out_proj", 2.0 * Md * E * E);
-        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
-        prof.end();
+        AVXH_TRY(layer_gemm(h, c, g, "gemm.out_proj", 2.0 * Md * E * E, prof, cs));
         AVXH_TRY(tap_finish(tap_o, c, w, io, cs));
         prof.begin("layernorm", 0.0);
-        AVXH_TRY(avx::layernorm(s1_32, s1_h, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
+        AVXH_TRY(avx::layernorm(s1.f32, s1.half, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, nullptr, E, w.ah, E, dt, cs));
         prof.end();
-        gemm_init(g, h);
-        g.A = w.ah; g.lda = E; g.W = ly.w_fc1; g.ldw = E; g.M = M; g.N = F; g.K = E; g.bias = ly.b_fc1; g.gelu = c.act;
-        g.out_half = w.hh; g.ldh = F;
+        fc1_args(g, h, c, ly, w, M, w.ah, no_fold);
         AVXH_TRY(ffn_hidden(h, c, w, g, M, prof, cs));
-        gemm_init(g, h);
-        g.A = w.hh; g.lda = F; g.W = ly.w_fc2; g.ldw = F; g.M = M; g.N = E; g.K = F; g.bias = ly.b_fc2; g.alpha = c.alpha;
-        if (M <= 8192 && !c.batch_invariant) { g.splitk_ws = w.splitk; g.splitk_bytes = w.splitk_bytes; }
-        if (fast) { g.resid_half = s1_h; g.ldrh = E; g.out_half = s0_h; g.ldh = E; }
-        else { g.resid = s1_32; g.ldr = E; g.out_f32 = s0_32; g.ldo = E; }
+        fc2_args(g, h, c, ly, w, M, s1, s0, no_fold);
         Tap tap_f;
         if (c.hook_site == 0) tap_f = tap_begin(c, w, io, i, g);
-        prof.begin("gemm.fc2", 2.0 * Md * E * F);
-        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
-        prof.end();
+        AVXH_TRY(layer_gemm(h, c, g, "gemm.fc2", 2.0 * Md * E * F, prof, cs));
         AVXH_TRY(tap_finish(tap_f, c, w, io, cs));
     }
-    if (L > 0 && (io.features_out || io.pooled_out)) {      // the encoder's LayerNorm after the stack (backbone.py:146-147)
-        const bool fused_pool = io.pooled_out && !io.features_out && fast && E % 8 == 0 && E <= 768 && (Bc >= 32 || c.batch_invariant);
-        if (fused_pool) {
-            prof.begin("layernorm+mean_pool", 0.0);
-            AVXH_TRY(avx::layernorm_pool(s0_h, E, c.final_ln_w, c.final_ln_b, c.eps, Bc, Tt, E, io.pooled_out + io.c0 * E, dt, cs));
-            prof.end();
-        } else {
-            float* xo = io.features_out ? io.features_out + io.c0 * Tt * E : w.x;
-            prof.begin("layernorm", 0.0);
-            AVXH_TRY(avx::layernorm(s0_32, s0_h, E, c.final_ln_w, c.final_ln_b, c.eps, M, E, xo, E, nullptr, E, dt, cs));
-            prof.end();
-            io.final_f32 = xo;
-            if (io.pooled_out) {
-                prof.begin("mean_pool", 0.0);
-                AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
-                prof.end();
-            }
-        }
-    }
+    // the encoder's LayerNorm after the stack (backbone.py:146-147)
+    if (L > 0 && (io.features_out || io.pooled_out)) AVXH_TRY(tail_finish(h, c, io, tail_begin(c, w, io, true, false), s0, c.final_ln_w, c.final_ln_b, false, prof, cs));
     return AVEXHIP_OK;
 }
 
 // x (the encoder input after its own LayerNorm) is in w.xh (fast) / w.x + w.xh (fp32 residual stream); runs the L layers and the outputs
 inline int run_layers(HandleBase* h, const CoreCfg& c, const std::vector<Layer>& layers, const CoreWs& w, CoreIo& io, Prof& prof, hipStream_t cs) {
-    const int E = c.E, F = c.F, H = c.H, L = c.L, dt = h->dtype, Bc = io.Bc, Tt = io.Tt;
-    const int M = Bc * Tt;
+    const int E = c.E, F = c.F, H = c.H, L = c.L, dt = h->dtype, Tt = io.Tt;
+    const int M = io.Bc * Tt;
     const double Md = (double)M;
     const bool fast = c.fast;
     if (c.pre_ln) return run_layers_pre_ln(h, c, layers, w, io, prof, cs);
-    float* x32 = w.x;
-    float* pre32 = fast ? nullptr : w.pre;
-    void* preh = fast ? w.preh : nullptr;
+    float* x32 = fast ? nullptr : w.x;      // the fp32 copy of x beside w.xh (fp32 residual stream only)
+    const Stream x = fast ? Stream{nullptr, w.xh} : Stream{w.x, nullptr};          // the stream at layer boundaries and after LayerNorm 1
+    const Stream pre = fast ? Stream{nullptr, w.preh} : Stream{w.pre, nullptr};    // the sums y1 / y2 before their LayerNorms
     // "fold": the two LayerNorms of a layer never run as kernels.  y1 = x*alpha + attn (preh) and y2 = x1*alpha + ffn (xh) stay raw
     // in the operand type with per-row partial statistics from the epilogue that wrote them; fc1 / the next QKV read them
     // through LayerNorm-folded weights, out_proj / fc2 apply LayerNorm to their residual on the fly (GemmArgs, gemm.hip).
-    const bool fold = fast && c.fold && F > 0 && M >= c.fold_min_rows;      // default: any M, the same arithmetic whatever the chunking
-    const int nseg = E / 64;
+    Fold f;
+    f.on = fast && c.fold && F > 0 && M >= c.fold_min_rows;      // default: any M, the same arithmetic whatever the chunking
+    const bool few_rows = !f.on && M <= 8192 && !c.batch_invariant;      // LayerNorms may ride in split-K epilogues
     avx::GemmArgs g;
     io.final_f32 = nullptr;
     for (int i = 0; i < L; ++i) {
         const Layer& ly = layers[i];
-        const bool raw_in = fold && i > 0;      // xh holds y2 of layer i-1 (raw) instead of its LayerNorm
-        gemm_init(g, h);
-        g.A = w.xh; g.lda = E; g.W = ly.w_qkv; g.ldw = E; g.M = M; g.N = 3 * E; g.K = E; g.bias = ly.b_qkv;
-        g.out_half = w.qkv; g.ldh = 3 * E;
-        if (raw_in) { g.W = ly.w_qkv_f; g.bias = ly.b_qkv_f; g.ln_rows = w.r2; g.ln_s = ly.s_qkv; }
-        prof.begin("gemm.qkv", 2.0 * Md * 3 * E * E);
-        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
-        prof.end();
+        const bool last = i == L - 1;
+        f.raw_in = f.on && i > 0;      // xh holds y2 of layer i-1 (raw) instead of its LayerNorm
+        f.last = last;
+        qkv_args(g, h, c, ly, w, M, w.xh, f);
+        AVXH_TRY(layer_gemm(h, c, g, "gemm.qkv", 2.0 * Md * 3 * E * E, prof, cs));
         prof.begin("attention", 4.0 * Md * Tt * E + (ly.grep_w ? 2.0 * Md * 8 * (E / H) * H : 0.0));
         AVXH_TRY(self_attention(h, c, ly, w, io, cs));
         prof.end();
-        gemm_init(g, h);
-        g.A = w.ah; g.lda = E; g.W = ly.w_o; g.ldw = E; g.M = M; g.N = E; g.K = E; g.bias = ly.b_o; g.alpha = c.alpha;
-        if (fast) { g.resid_half = w.xh; g.ldrh = E; g.out_half = preh; g.ldh = E; }
-        else { g.resid = x32; g.ldr = E; g.out_f32 = pre32; g.ldo = E; }
-        if (fold) {
-            g.stats_out = w.st1;
-            g.rows_out = w.r1; g.rows_eps = c.eps;      // LN1's row statistics with the product (avx::gemm runs ln_rowstats behind it)
-            if (raw_in) {
-                g.resid_half = nullptr; g.ldrh = 0;
-                g.lnr_y = w.xh; g.ldy = E; g.lnr_rows = w.r2; g.lnr_gamma = ly.ga_o; g.lnr_beta = ly.bb_o; g.lnr_prefolded = 1;
-            }
-        }
+        out_proj_args(g, h, c, ly, w, M, x, pre, f);
         Tap tap_o;
         if (c.hook_site == 1) tap_o = tap_begin(c, w, io, i, g);
         // few rows, no fold: LayerNorm 1 rides in the split-K epilogue of the product (one kernel less per layer; x32 / xh are read as the
         // residual and rewritten row by row by the same wave)
         bool ln1_fused = false;
-        if (!fold && F > 0 && M <= 8192 && !c.batch_invariant) {
+        if (few_rows && F > 0) {
             g.splitk_ws = w.splitk; g.splitk_bytes = w.splitk_bytes;
-            if (avx::gemm_post_ln_ok(g)) {
-                g.post_ln_w = ly.ln1_w; g.post_ln_b = ly.ln1_b; g.post_ln_eps = c.eps; g.post_ln_round = fast ? 1 : 0;
-                g.post_ln_out_f32 = fast ? nullptr : x32; g.post_ln_ldo = E; g.post_ln_out_half = w.xh; g.post_ln_ldh = E;
-                ln1_fused = true;
-            } else { g.splitk_ws = nullptr; g.splitk_bytes = 0; }
+            ln1_fused = avx::gemm_post_ln_ok(g);
+            if (ln1_fused) post_ln_args(g, c, ly.ln1_w, ly.ln1_b, x32, w.xh);
+            else { g.splitk_ws = nullptr; g.splitk_bytes = 0; }
         }
-        prof.begin("gemm.out_proj", 2.0 * Md * E * E);
-        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
-        prof.end();
+        AVXH_TRY(layer_gemm(h, c, g, "gemm.out_proj", 2.0 * Md * E * E, prof, cs));
         AVXH_TRY(tap_finish(tap_o, c, w, io, cs));
         if (F == 0) {      // attention-only block: LN1 closes it
-            const bool last_a = i == L - 1;
-            float* xa = last_a ? (io.features_out ? io.features_out + io.c0 * Tt * E : x32) : (fast ? nullptr : x32);
+            if (last) { AVXH_TRY(tail_finish(h, c, io, tail_begin(c, w, io, false, true), pre, ly.ln1_w, ly.ln1_b, false, prof, cs)); continue; }
             prof.begin("layernorm", 0.0);
-            AVXH_TRY(avx::layernorm(pre32, preh, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, xa, E, last_a ? nullptr : w.xh, E, dt, cs));
+            AVXH_TRY(avx::layernorm(pre.f32, pre.half, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, x32, E, w.xh, E, dt, cs));
             prof.end();
-            if (last_a) {
-                io.final_f32 = xa;
-                if (io.pooled_out) {
-                    prof.begin("mean_pool", 0.0);
-                    AVXH_TRY(avx::mean_pool(xa, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
-                    prof.end();
-                }
-            }
             continue;
         }
-        if (fold) {
-            // (w.r1 = LN1's (rstd, -mu rstd) came out of the product: GemmArgs::rows_out)
-        } else if (!ln1_fused) {
+        if (!f.on && !ln1_fused) {      // (fold: w.r1 = LN1's (rstd, -mu rstd) came out of the product: GemmArgs::rows_out)
             prof.begin("layernorm", 0.0);
-            AVXH_TRY(avx::layernorm(pre32, preh, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, fast ? nullptr : x32, E, w.xh, E, dt, cs));
+            AVXH_TRY(avx::layernorm(pre.f32, pre.half, E, ly.ln1_w, ly.ln1_b, c.eps, M, E, x32, E, w.xh, E, dt, cs));
             prof.end();
         }
-        gemm_init(g, h);
-        g.A = w.xh; g.lda = E; g.W = ly.w_fc1; g.ldw = E; g.M = M; g.N = F; g.K = E; g.bias = ly.b_fc1; g.gelu = c.act;
-        g.out_half = w.hh; g.ldh = F;
-        if (fold) { g.A = preh; g.W = ly.w_fc1_f; g.bias = ly.b_fc1_f; g.ln_rows = w.r1; g.ln_s = ly.s_fc1; }
+        fc1_args(g, h, c, ly, w, M, f.on ? w.preh : w.xh, f);
         AVXH_TRY(ffn_hidden(h, c, w, g, M, prof, cs));
-        const bool last = i == L - 1;
-        gemm_init(g, h);
-        g.A = w.hh; g.lda = F; g.W = ly.w_fc2; g.ldw = F; g.M = M; g.N = E; g.K = F; g.bias = ly.b_fc2; g.alpha = c.alpha;
-        if (M <= 8192 && !c.batch_invariant) { g.splitk_ws = w.splitk; g.splitk_bytes = w.splitk_bytes; }      // (split-K adds in another order than one pass over K)
-        if (fast) { g.resid_half = w.xh; g.ldrh = E; g.out_half = preh; g.ldh = E; }
-        else { g.resid = x32; g.ldr = E; g.out_f32 = pre32; g.ldo = E; }
-        if (fold) {   // residual = LN1(y1) on the fly; y2 (raw) goes to xh, which nothing reads any more in this layer
-            g.resid_half = nullptr; g.ldrh = 0;
-            g.lnr_y = preh; g.ldy = E; g.lnr_rows = w.r1; g.lnr_gamma = ly.ga_fc2; g.lnr_beta = ly.bb_fc2; g.lnr_prefolded = 1;
-            g.out_half = w.xh; g.stats_out = !last ? w.st2 : nullptr;      // the last layer's y2 goes to a LayerNorm kernel that takes its own statistics
-        }
+        // fold: residual = LN1(y1) on the fly; y2 (raw) goes to xh, which nothing reads any more in this layer
+        const Stream y2 = f.on ? x : pre;
+        fc2_args(g, h, c, ly, w, M, f.on ? pre : x, y2, f);
         Tap tap_f;
         if (c.hook_site == 0) tap_f = tap_begin(c, w, io, i, g);
-        // the last LayerNorm produces the fp32 features (caller's buffer, or scratch when only pooling)
-        float* xo = nullptr;
-        if (last) xo = io.features_out ? io.features_out + io.c0 * Tt * E : ((io.pooled_out || !fast) ? x32 : nullptr);
-        else if (!fast) xo = x32;
-        // pooled embedding only (the headline path): final LayerNorm and the mean over tokens in one pass, no fp32 feature tensor
-        const bool fused_pool = last && io.pooled_out && !io.features_out && preh && !pre32 && E % 8 == 0 && E <= 768 && (Bc >= 32 || c.batch_invariant);
+        // LayerNorm 2 makes the next layer's x -- or, after the last layer, the outputs
+        Tail tail;
+        if (last) tail = tail_begin(c, w, io, true, !fast);
+        else tail.xo = x32;
+        tail.ln_stage = !f.on;
         // few rows, no fold: LayerNorm 2 in the split-K epilogue (as LayerNorm 1 above)
-        bool ln2_fused = false;
-        if (!fold && !fused_pool && (xo || !last) && avx::gemm_post_ln_ok(g)) {
-            g.post_ln_w = ly.ln2_w; g.post_ln_b = ly.ln2_b; g.post_ln_eps = c.eps; g.post_ln_round = fast ? 1 : 0;
-            g.post_ln_out_f32 = xo; g.post_ln_ldo = E; g.post_ln_out_half = last ? nullptr : w.xh; g.post_ln_ldh = E;
-            ln2_fused = true;
-        }
-        prof.begin("gemm.fc2", 2.0 * Md * E * F);
-        pin_kernel(c, g); AVXH_TRY(avx::gemm(g, dt, cs));
-        prof.end();
+        const bool ln2_fused = !f.on && !tail.fused_pool && (tail.xo || !last) && avx::gemm_post_ln_ok(g);
+        if (ln2_fused) post_ln_args(g, c, ly.ln2_w, ly.ln2_b, tail.xo, last ? nullptr : w.xh);
+        AVXH_TRY(layer_gemm(h, c, g, "gemm.fc2", 2.0 * Md * E * F, prof, cs));
         AVXH_TRY(tap_finish(tap_f, c, w, io, cs));
-        if (fold && !last) {
+        if (last) { AVXH_TRY(tail_finish(h, c, io, tail, y2, ly.ln2_w, ly.ln2_b, ln2_fused, prof, cs)); continue; }
+        if (f.on) {
             prof.begin("ln_rowstats", 0.0);
-            AVXH_TRY(avx::ln_rowstats(w.st2, M, nseg, c.eps, w.r2, cs));
+            AVXH_TRY(avx::ln_rowstats(w.st2, M, E / 64, c.eps, w.r2, cs));
             prof.end();
-        }
-        if (fused_pool) {      // the pre-LayerNorm sums y2 sit in preh, with the fold in xh
-            prof.begin("layernorm+mean_pool", 0.0);
-            AVXH_TRY(avx::layernorm_pool(fold ? w.xh : preh, E, ly.ln2_w, ly.ln2_b, c.eps, Bc, Tt, E, io.pooled_out + io.c0 * E, dt, cs));
-            prof.end();
-        } else if (!fold) {
+        } else {
             prof.begin("layernorm", 0.0);
-            if ((xo || !last) && !ln2_fused) AVXH_TRY(avx::layernorm(pre32, preh, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, xo, E, last ? nullptr : w.xh, E, dt, cs));
-            prof.end();
-        } else if (last && xo) {   // the only LayerNorm of the layer stack that still runs: fp32 features from the raw y2
-            prof.begin("layernorm", 0.0);
-            AVXH_TRY(avx::layernorm(nullptr, w.xh, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, xo, E, nullptr, E, dt, cs));
-            prof.end();
-        }
-        if (last) io.final_f32 = xo;
-        if (last && io.pooled_out && !fused_pool) {
-            prof.begin("mean_pool", 0.0);
-            AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
+            if (!ln2_fused) AVXH_TRY(avx::layernorm(pre.f32, pre.half, E, ly.ln2_w, ly.ln2_b, c.eps, M, E, x32, E, w.xh, E, dt, cs));
             prof.end();
         }
     }

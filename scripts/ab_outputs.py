@@ -1,0 +1,194 @@
+#!/usr/bin/env python3
+"""Do two builds of libavexhip.so compute the same thing?
+
+    python scripts/ab_outputs.py LIB_A LIB_B [--timeout SECONDS]
+
+Runs one fixed set of small forwards under each library -- a fresh child process per library (AVEX_AMD_LIB), one after the other, each
+under its own time limit; the first child that fails ends the run -- and compares every output array with np.array_equal, every
+last_profile() name list and every BeatsGraph.nodes.  For refactors of host code (launchers, layer loops): the second library is usually
+a build of the parent commit (AVEX_AMD_LIB_SUFFIX=parent python -m avex_amd.build in a worktree of it).
+
+The set takes the smallest shapes that reach every branch of the layer loops and the GEMM / attention dispatch: BEATs at base width with
+2 layers at 1 clip (split-K, LayerNorm in the epilogue), 3 clips (128-tile kernels, LayerNorm kernels on the wide products) and 9 clips
+(4 464 rows: over the fold threshold), both residual streams, batch-invariant, unpooled and pooled hooks with and without padding, graph
+captures, the loop-shape variants of synth.BEATS_VARIANTS, EAT (513 tokens: nine-tile attention + tail), AVES, EfficientNet-B0 behind the
+mel plan with taps, the probes on the stack handle, and tests/test_gpu_source_build.py's FORWARD set.  Exit status 0: everything equal.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def child(out_path: str) -> None:
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from avex_amd import _capi, synth, kernels as K
+
+    arrays, profiles, nodes = {}, {}, {}
+
+    def keep(tag, out):
+        for k in ("features", "pooled"):
+            if out.get(k) is not None:
+                arrays[f"{tag}.{k}"] = out[k].float().cpu().numpy()
+        for i, t in (out.get("hooks") or {}).items():
+            arrays[f"{tag}.hook{i}"] = t.float().cpu().numpy()
+
+    def run(tag, enc, fn):
+        enc.set_profiling(True)
+        keep(tag, fn())
+        torch.cuda.synchronize()
+        profiles[tag] = [name for name, _, _ in enc.last_profile()]      # stages in order of first appearance
+        enc.set_profiling(False)
+
+    # ---- BEATs, base width, 2 layers, 10 s clips ----
+    cfg = dict(synth.BEATS_BASE_CFG, encoder_layers=2)
+    sd = synth.beats_state_dict(cfg, seed=5)
+    wav9 = torch.from_numpy(synth.noise_clips(9, 160000, seed=9)).cuda()
+    for residual in ("half", "f32"):
+        enc = K.BeatsEncoder(cfg, sd, operand_dtype="f16", residual=residual)
+        for n in (1, 3, 9):
+            w = wav9[:n]
+            run(f"beats.{residual}.{n}", enc, lambda: enc.forward(w, want_features=True, want_pooled=True))
+            run(f"beats.{residual}.{n}.pooled_only", enc, lambda: enc.forward(w, want_features=False, want_pooled=True))
+        Tt = enc.num_tokens(160000)
+        pad = torch.zeros((9, Tt), dtype=torch.uint8)
+        pad[1::2, Tt // 2:] = 1      # every second clip half padding
+        run(f"beats.{residual}.9.hooks", enc, lambda: enc.forward(wav9, hook_layers=[0, 1, 2], want_features=False))
+        for mode in ("mean", "max", "cls_token"):
+            run(f"beats.{residual}.9.{mode}", enc, lambda: enc.forward(wav9, hook_layers=[0, 1, 2], hook_pooled=mode, want_features=False, want_pooled=True))
+            run(f"beats.{residual}.9.{mode}.pad", enc, lambda: enc.forward(wav9, hook_layers=[0, 1, 2], hook_pooled=mode, want_features=False, want_pooled=True, frame_pad=pad.cuda()))
+        for n in (1, 9):
+            g = enc.capture(n, 160000, want_features=True, want_pooled=True)
+            g.wav.copy_(wav9[:n])
+            g.replay()
+            torch.cuda.synchronize()
+            nodes[f"beats.{residual}.{n}"] = g.nodes
+            keep(f"beats.{residual}.{n}.graph", dict(features=g.features, pooled=g.pooled))
+            g.close()
+        enc.close()
+    inv = K.BeatsEncoder(cfg, sd, operand_dtype="f16", residual="half", batch_invariant=True)
+    run("beats.invariant.9", inv, lambda: inv.forward(wav9, want_features=True, want_pooled=True))
+    run("beats.invariant.9.pooled_only", inv, lambda: inv.forward(wav9, want_features=False, want_pooled=True))
+    for mode in ("mean", "max", "cls_token"):
+        run(f"beats.invariant.9.{mode}", inv, lambda: inv.forward(wav9, hook_layers=[0, 1, 2], hook_pooled=mode, want_features=False))
+    inv.close()
+    # ---- the loop shapes: pre-LN, no post_extract_proj, GLU, identity activation ----
+    for name in ("preln_relu_convbias", "preln_tanh_nopost", "postln_glu_nogate", "postln_linear"):
+        vcfg = synth.BEATS_VARIANTS[name]
+        for residual in ("half", "f32"):
+            v = K.BeatsEncoder(vcfg, synth.beats_state_dict(vcfg, seed=3), operand_dtype="f16", residual=residual)
+            run(f"variant.{name}.{residual}", v, lambda: v.forward(wav9[:2], hook_layers=[1, 2], want_features=True, want_pooled=True))
+            run(f"variant.{name}.{residual}.pooled_only", v, lambda: v.forward(wav9[:2], want_features=False, want_pooled=True))
+            v.close()
+    # ---- EAT: 513 tokens ----
+    from avex_amd.eat_encoder import EatEncoder
+    ecfg = dict(synth.EAT_BASE_CFG, depth=2)
+    eat = EatEncoder(ecfg, synth.eat_state_dict(ecfg), operand_dtype="f16")
+    ew = torch.from_numpy(synth.noise_clips(3, 48000, seed=10)).cuda()
+    run("eat.cls", eat, lambda: eat.forward(ew, hook_layers=[0, 1], pooling="cls"))
+    run("eat.cls.pooled_only", eat, lambda: eat.forward(ew, want_features=False, pooling="cls"))
+    run("eat.mean", eat, lambda: eat.forward(ew, want_features=False, pooling="mean", hook_layers=[1], hook_pooled=True))
+    eat.close()
+    # ---- AVES ----
+    from avex_amd.aves_encoder import AvesEncoder
+    acfg = dict(synth.AVES_BASE_CFG, encoder_num_layers=2)
+    aves = AvesEncoder(acfg, synth.aves_state_dict(acfg))
+    aw = torch.from_numpy(synth.noise_clips(3, 32000, seed=12)).cuda()
+    run("aves", aves, lambda: aves.forward(aw, hook_layers=[0, 1], want_features=True, want_pooled=True))
+    run("aves.pooled_only", aves, lambda: aves.forward(aw, want_features=False, want_pooled=True))
+    aves.close()
+    # ---- EfficientNet-B0 behind the mel plan ----
+    from avex_amd.effnet_encoder import EfficientNetB0Encoder
+    eff = EfficientNetB0Encoder(synth.effnet_b0_state_dict())
+    mel = K.MelspecPlan(n_fft=800, hop_length=160, n_mels=128, normalize=True)(torch.from_numpy(synth.noise_clips(3, 64000, seed=11)).cuda())
+    run("effnet", eff, lambda: eff.forward(mel, hook_layers=eff.tap_names(), want_features=True, want_pooled=True))
+    eff.close()
+    # ---- probes on the stack handle: attention-only blocks (F = 0) and head widths other than 64 ----
+    from avex_amd import probes as P
+    gen = torch.Generator().manual_seed(4)
+    seqs = [torch.randn(5, 24, 128, generator=gen).cuda() for _ in range(3)]
+    torch.manual_seed(7)
+    att = P.AttentionProbe(None, [], 37, device="cuda", feature_mode=True, input_dim=[(24, 128)] * 3, aggregation="none", num_heads=4, num_layers=2,
+                           dropout_rate=0.0, max_sequence_length=64, use_positional_encoding=True).eval()
+    arrays["probe.attention"] = att(seqs).float().cpu().numpy()
+    tr = P.TransformerProbe(None, [], 19, device="cuda", feature_mode=True, input_dim=[(24, 128)] * 3, aggregation="none", num_heads=4, attention_dim=192,
+                            num_layers=2, dropout_rate=0.0, max_sequence_length=64, use_positional_encoding=True).eval()
+    arrays["probe.transformer"] = tr(seqs).float().cpu().numpy()
+    # ---- tests/test_gpu_source_build.py's set ----
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_source_build as sb
+    fd, side = tempfile.mkstemp(suffix=".npz")
+    os.close(fd)
+    exec(compile(sb.FORWARD.format(root=ROOT, out=side), "FORWARD", "exec"), {"__name__": "forward_set"})
+    with np.load(side) as z:
+        for k in z.files:
+            if k != "lib":
+                arrays[f"source_build.{k}"] = z[k]
+    os.remove(side)
+    torch.cuda.synchronize()
+    np.savez(out_path, **arrays)
+    with open(out_path + ".json", "w") as f:
+        json.dump(dict(lib=_capi.LIB_PATH, profiles=profiles, nodes=nodes), f)
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("lib_a")
+    ap.add_argument("lib_b")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
+    ap.add_argument("--child", metavar="OUT", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        child(a.child)
+        return 0
+    import numpy as np
+    res = []
+    with tempfile.TemporaryDirectory() as td:
+        for tag, lib in (("a", a.lib_a), ("b", a.lib_b)):
+            lib = os.path.abspath(lib)
+            out = os.path.join(td, tag + ".npz")
+            env = dict(os.environ, AVEX_AMD_LIB=lib)
+            env.pop("AVEX_AMD_LIB_SUFFIX", None)
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--child", out], env=env, timeout=a.timeout)
+            except subprocess.TimeoutExpired:
+                print(f"ab_outputs: the run under {lib} did not finish in {a.timeout} s; stopping")
+                return 3
+            if r.returncode != 0:
+                print(f"ab_outputs: the run under {lib} failed with status {r.returncode}; stopping")
+                return 2
+            with open(out + ".json") as f:
+                meta = json.load(f)
+            assert meta["lib"] == lib, (meta["lib"], lib)
+            with np.load(out) as z:
+                res.append((dict(z), meta))
+    (xa, ma), (xb, mb) = res
+    bad = 0
+    if sorted(xa) != sorted(xb):
+        print("ab_outputs: the two runs returned different sets of arrays")
+        bad += 1
+    for k in sorted(set(xa) & set(xb)):
+        if xa[k].shape != xb[k].shape or not np.array_equal(xa[k], xb[k], equal_nan=True):
+            d = np.abs(xa[k].astype(np.float64) - xb[k].astype(np.float64)).max() if xa[k].shape == xb[k].shape else float("nan")
+            print(f"DIFF array {k}: shapes {xa[k].shape} {xb[k].shape}, max |a - b| = {d:.3g}")
+            bad += 1
+        elif not np.isfinite(xa[k]).all():
+            print(f"note: {k} holds non-finite values (equal in both)")
+    for kind in ("profiles", "nodes"):
+        for k in sorted(set(ma[kind]) | set(mb[kind])):
+            if ma[kind].get(k) != mb[kind].get(k):
+                print(f"DIFF {kind} {k}:\n  a: {ma[kind].get(k)}\n  b: {mb[kind].get(k)}")
+                bad += 1
+    print(f"ab_outputs: {len(xa)} arrays, {len(ma['profiles'])} profile name lists, {len(ma['nodes'])} graph node counts compared: "
+          + ("all equal" if not bad else f"{bad} differ"))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -40,7 +40,8 @@ int main(int argc, char** argv) {
     hipMemcpy(dgb, gb.data(), 32, hipMemcpyHostToDevice);
     hipMemcpy(dga, ga.data(), H * 4, hipMemcpyHostToDevice);
     int ncu = 256; avx::device_cu_count(&ncu);
-    auto run = [&]() { return avx::attention16(dq, B, T, H, dtab, dgw, dgb, dga, nullptr, dout, AVEXHIP_F16, 0, ncu, 0); };
+    const avx::AttPlan plan = avx::plan_attention(T, B, H, dtab != nullptr, ncu, avx::AttKnobs());
+    auto run = [&]() { return avx::attention16(dq, B, T, H, dtab, dgw, dgb, dga, nullptr, dout, AVEXHIP_F16, 0, plan, 0); };
     if (run() != 0) return 1;
     hipDeviceSynchronize();
     for (int i = 0; i < 3 * iters; ++i) run();      // to the board's steady clock
