@@ -136,6 +136,14 @@ class EventsResult(C.Structure):
                 ("peak", C.c_void_p), ("peak_window", C.c_void_p), ("mean", C.c_void_p)]
 
 
+class ExamplesArgs(C.Structure):
+    _fields_ = [("bank", C.c_void_p), ("row_id", C.c_void_p), ("m", C.c_int64), ("d", C.c_int32), ("n_classes", C.c_int32), ("n_segments", C.c_int32),
+                ("batch", C.c_int32), ("segments", C.c_void_p), ("tile_segments", C.c_void_p), ("class_segments", C.c_void_p), ("query", C.c_void_p),
+                ("ld_query", C.c_int64), ("n", C.c_int32), ("top_m", C.c_int32), ("mode", C.c_int32), ("normalise", C.c_int32), ("stages", C.c_int32),
+                ("reserved", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("scores", C.c_void_p), ("ld_scores", C.c_int64),
+                ("nearest", C.c_void_p), ("ld_nearest", C.c_int64)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -270,6 +278,10 @@ SYMBOLS = {
     "avexhip_events_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "avexhip_events_scan": (C.c_int, [C.POINTER(EventsArgs), _P]),
     "avexhip_events_emit": (C.c_int, [C.POINTER(EventsArgs), C.POINTER(EventsResult), _P]),
+    "avexhip_examples_max_top_m": (C.c_int, []),
+    "avexhip_examples_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "avexhip_examples_score": (C.c_int, [C.POINTER(ExamplesArgs), _P]),
+    "avexhip_examples_class_mean": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 16
+#define AVEXHIP_ABI_VERSION 17
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -593,6 +593,64 @@ int avexhip_events_chunk_windows(void);     /* consecutive windows of one class 
 size_t avexhip_events_workspace_bytes(int64_t n_windows, int n_classes, int n_seq);      /* 0 for a bad shape */
 int avexhip_events_scan(const avexhip_events_args* args, void* stream);
 int avexhip_events_emit(const avexhip_events_args* args, const avexhip_events_result* result, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Few-shot class scores from labelled examples (ABI 17): scores[n][c] = the mean of the top_m largest similarities of query n to the
+ * example rows of class c (nearest-example scoring; with one mean row per class, nearest-prototype scoring), for window embeddings that
+ * are already on the device.  The [queries, examples] matrix is never stored.
+ * The bank is one [m, dpad] matrix of rows prepared by avexhip_search_prepare_rows, SORTED BY CLASS with the background examples (label
+ * -1) last, stable in the order the rows were added; row_id[column] is a row's number in that order.  A class is a column range, a segment
+ * is (class, 128-column tile).  The caller builds the tables on the host (avex_amd/examples.py: segment_tables):
+ *   segments[s] = {class, first column, last column, tile}, in column order;
+ *   tile_segments[t] .. tile_segments[t + 1] - 1 = the segments of tile t;
+ *   class_segments[c] = {first, last} segment of class c (first > last: an empty class); class index n_classes is the background.
+ * avexhip_examples_score, one call per query batch: the rows are prepared like the bank's (normalise = 1: divided by max(||row||, 1e-12)),
+ * their similarities to a column tile come from the fp32 MFMA tile of the search (queries are its A operand: the bits of a similarity
+ * are those avexhip_search_chunk gives for the same two rows), and per (query, segment) the top_m largest keys
+ *   key = (mono32(sim + 0.0f) << 32) | (0xFFFFFFFF - row_id)      -0 folded onto +0; a NaN similarity is never counted
+ * go to the workspace.  Per (query, class) the lists of the class's segments are merged, the min(top_m, count) largest similarities are
+ * added in fp32 in descending order from the largest and divided by float(count kept); no number: NaN.  mode SIMILARITY writes that
+ * value, mode MARGIN that value minus the same over the background rows (one fp32 subtraction; NaN carries).  nearest[n][c] (optional) is
+ * the row_id of the class's largest key -- the highest similarity, the lower row on a tie -- or -1.
+ * No atomics; nothing here allocates or synchronises; the result does not depend on the batch, on the order the rows were added in, or
+ * on the run.  Working memory is O(batch x n_segments x top_m) and does not depend on the number of rows scored.
+ * ------------------------------------------------------------------------------------------ */
+enum { AVEXHIP_EXAMPLES_SIMILARITY = 0, AVEXHIP_EXAMPLES_MARGIN = 1 };
+
+typedef struct {
+    const float* bank;              /* [m, dpad] prepared rows sorted by class, background last */
+    const int32_t* row_id;          /* [m] insertion number of each sorted row */
+    int64_t m;                      /* 1 .. 2^31 - 1 */
+    int32_t d;                      /* width of a row; dpad = ceil(d / 32) * 32 */
+    int32_t n_classes;              /* C >= 1 */
+    int32_t n_segments;             /* ceil(m / 128) .. ceil(m / 128) + C */
+    int32_t batch;                  /* as given to avexhip_examples_workspace_bytes */
+    const int32_t* segments;        /* [n_segments][4] on the device */
+    const int32_t* tile_segments;   /* [ceil(m / 128) + 1] on the device */
+    const int32_t* class_segments;  /* [C + 1][2] on the device */
+    const float* query;             /* [n, d] fp32 rows of this batch (row stride ld_query) */
+    int64_t ld_query;
+    int32_t n;                      /* rows of this batch, 1 .. batch */
+    int32_t top_m;                  /* 1 .. avexhip_examples_max_top_m() */
+    int32_t mode;                   /* AVEXHIP_EXAMPLES_* */
+    int32_t normalise;              /* 1 = divide the query rows by their norm (cosine), 0 = copy them (dot) */
+    int32_t stages;                 /* 0 or 3: all; 1: prepare + tile kernel only; 2: reduce only (of the lists in the workspace) */
+    int32_t reserved;
+    void* workspace;
+    size_t workspace_bytes;
+    float* scores;                  /* out [n, C] (row stride ld_scores): the layout avexhip_events_scan reads */
+    int64_t ld_scores;
+    int32_t* nearest;               /* out [n, C] (row stride ld_nearest), or NULL */
+    int64_t ld_nearest;
+} avexhip_examples_args;
+
+int avexhip_examples_max_top_m(void);       /* 16 */
+size_t avexhip_examples_workspace_bytes(int batch, int n_segments, int top_m, int dpad);      /* 0 for a bad shape; no number of rows scored */
+int avexhip_examples_score(const avexhip_examples_args* args, void* stream);
+/* out_dev[k][0 .. d) = (bank rows first_dev[k] .. first_dev[k] + count_dev[k] - 1 added column by column in fp32, in order, from 0.0f)
+ * / float(count_dev[k]), k < n_out <= 65535: the class means a prototype bank is made of.  rows_dev: [n_rows, dpad] prepared rows. */
+int avexhip_examples_class_mean(const float* rows_dev, int64_t n_rows, int d, const int32_t* first_dev, const int32_t* count_dev, int n_out,
+                                float* out_dev, int64_t ld_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Clustering metrics (ABI 11): what avex/evaluation/clustering.py computes from cached embeddings -- scikit-learn's
