@@ -42,7 +42,11 @@ class GemmArgs(C.Structure):
                 ("lnr_y", C.c_void_p), ("ldy", C.c_int64), ("lnr_rows", C.c_void_p),
                 ("lnr_gamma", C.c_void_p), ("lnr_beta", C.c_void_p), ("stats_out", C.c_void_p),
                 ("overflow_count", C.c_void_p), ("pool_part", C.c_void_p), ("pool_rows", C.c_int32), ("pool_mode", C.c_int32),
-                ("splitk_ws", C.c_void_p), ("splitk_bytes", C.c_size_t), ("rows_out", C.c_void_p), ("rows_eps", C.c_float)]
+                ("splitk_ws", C.c_void_p), ("splitk_bytes", C.c_size_t), ("rows_out", C.c_void_p), ("rows_eps", C.c_float),
+                ("row_zero", C.c_void_p), ("half_scale", C.c_float), ("n_store", C.c_int32),
+                ("a_scale", C.c_void_p), ("a_scale_rows", C.c_int32), ("a_scale_ld", C.c_int32),
+                ("post_ln_w", C.c_void_p), ("post_ln_b", C.c_void_p), ("post_ln_eps", C.c_float), ("post_ln_round", C.c_int32),
+                ("post_ln_out_f32", C.c_void_p), ("post_ln_ldo", C.c_int64), ("post_ln_out_half", C.c_void_p), ("post_ln_ldh", C.c_int64)]
 
 
 class BeatsConfig(C.Structure):

@@ -57,10 +57,15 @@ extern "C" int avexhip_gemm(const avexhip_gemm_args* a, int dtype, void* stream)
     g.bias = a->bias; g.resid = a->resid; g.ldr = a->ldr; g.alpha = a->alpha; g.gelu = a->gelu;
     g.resid_half = a->resid_half; g.ldrh = a->ldrh;
     g.out_f32 = a->out_f32; g.ldo = a->ldo; g.out_half = a->out_half; g.ldh = a->ldh;
-    g.out_raw = a->out_raw; g.ldraw = a->ldraw; g.row_zero = nullptr; g.variant = a->variant;
+    g.out_raw = a->out_raw; g.ldraw = a->ldraw; g.variant = a->variant;
     g.pool_part = a->pool_part; g.pool_T = a->pool_rows; g.pool_mode = a->pool_mode;
     g.splitk_ws = a->splitk_ws; g.splitk_bytes = a->splitk_bytes;
     g.rows_out = a->rows_out; g.rows_eps = a->rows_eps;
+    // ABI 18: what only the handles could set before (gemm_validate / plan_gemm refuse what no kernel is built for)
+    g.row_zero = a->row_zero; g.half_scale = a->half_scale; g.n_store = a->n_store;
+    g.a_scale = a->a_scale; g.a_scale_rows = a->a_scale_rows; g.a_scale_ld = a->a_scale_ld;
+    g.post_ln_w = a->post_ln_w; g.post_ln_b = a->post_ln_b; g.post_ln_eps = a->post_ln_eps; g.post_ln_round = a->post_ln_round;
+    g.post_ln_out_f32 = a->post_ln_out_f32; g.post_ln_ldo = a->post_ln_ldo; g.post_ln_out_half = a->post_ln_out_half; g.post_ln_ldh = a->post_ln_ldh;
     return avx::gemm(g, dtype, (hipStream_t)stream);
 }
 extern "C" int avexhip_pool_reduce(const float* part, int B, int T, int N, float* out, int64_t ldo, void* stream) {

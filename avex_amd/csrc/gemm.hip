@@ -256,7 +256,8 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(avx::GemmArgs p, i
 }
 
 // ... and with a LayerNorm of the finished rows (GemmArgs::post_ln_*): one wave per row, lane l holds columns 256 c + 4 l .. + 3 of chunk c.
-// Same per-row arithmetic as layernorm_half_kernel (two-pass statistics in registers, (v - mean) * rstd * w + b).
+// The formula of the LayerNorm kernels (two-pass statistics in registers, (v - mean) * rstd * w + b) with this kernel's own summation order
+// (four columns per lane and chunk, a 64-lane butterfly): within rounding of avexhip_layernorm, not its bits (tests/test_gpu_gemm_args.py).
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_ln_epilogue_kernel(avx::GemmArgs p, int S) {
     AVX_F16_SATURATE_ON();

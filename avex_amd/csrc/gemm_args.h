@@ -19,7 +19,9 @@ struct GemmArgs {
     float* out_f32; int64_t ldo;
     void* out_half; int64_t ldh;
     float* out_raw; int64_t ldraw;
-    const uint8_t* row_zero;  // optional [M] mask: rows with 1 store zeros to every output
+    const uint8_t* row_zero;  // optional [M] mask: a row with a non-zero byte takes 0 in place of acc + bias -- its raw tap is 0.0 and its other outputs are what the
+                              // rest of the epilogue makes of 0: resid * alpha through the activation, i.e. zeros when there is no residual (the one caller, the
+                              // projection behind the patch embedding, has none); every kernel form that knows the mask does the same
     float half_scale;         // 0 or 1: off.  Otherwise out_half receives value * half_scale (a power of two: the third rung of the f16 range ladder stores
                               // fc1's hidden activations scaled down and folds the inverse into fc2's weights); generic epilogues only, fp32 outputs unscaled
     int variant;

@@ -413,7 +413,13 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = Non
          lnr_gamma: Optional[torch.Tensor] = None, lnr_beta: Optional[torch.Tensor] = None, stats_out: bool = False,
          lda: Optional[int] = None, rows: Optional[int] = None, kdim: Optional[int] = None, slack_rows: int = 0,
          overflow: Optional[torch.Tensor] = None, pool_rows: int = 0, pool_mode: str = "mean", splitk: bool = False,
-         rows_eps: Optional[float] = None) -> Dict[str, torch.Tensor]:
+         rows_eps: Optional[float] = None,
+         act: Optional[int] = None, row_zero: Optional[torch.Tensor] = None, half_scale: float = 0.0, n_store: int = 0,
+         a_scale: Optional[torch.Tensor] = None, a_scale_rows: int = 0,
+         post_ln_w: Optional[torch.Tensor] = None, post_ln_b: Optional[torch.Tensor] = None, post_ln_eps: float = 1e-5,
+         post_ln_round: int = 0, post_ln_out_f32: bool = True, post_ln_out_half: bool = False,
+         ld_out: Optional[int] = None, ldw: Optional[int] = None, guard_rows: int = 0,
+         sentinel: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """``epi(a @ w.T)`` with ``a [M,K]`` and ``w [N,K]`` half tensors (see avexhip_gemm).  ``ln_rows``/``ln_s`` fold a
     LayerNorm of the A rows into the epilogue, ``lnr_*`` apply LayerNorm(lnr_y) as the residual (the ``*_rows`` tensors come from
     :func:`ln_rowstats`), ``stats_out`` returns the per-row partial statistics ``[M, N/64, 2]`` of the output under ``"stats"``;
@@ -421,7 +427,16 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = Non
     treats the rows as clips of T rows and returns under ``"pooled"`` the per-clip mean of the raw output (bias added, before residual /
     activation) without materialising it (``pool_part`` + ``avexhip_pool_reduce``); ``pool_mode`` "max" / "cls_token" return the per-clip
     maximum / first row instead; ``rows_eps`` returns under ``"rows"`` the finished row statistics ``[M (+1 if odd), 2]`` = (rstd, -mean rstd)
-    of the output (what :func:`ln_rowstats` makes of ``"stats"``, same bits).  ``variant=8`` runs variant 5."""
+    of the output (what :func:`ln_rowstats` makes of ``"stats"``, same bits).  ``variant=8`` runs variant 5.
+
+    The ABI 18 fields: ``act`` is the integer activation code (0-5; ``gelu=`` / ``silu=`` are codes 1 and 2), ``row_zero`` a ``[M]``
+    mask, ``half_scale`` / ``n_store`` the fields of that name, ``a_scale [clips, a_scale_ld]`` fp32 with ``a_scale_rows`` rows per clip,
+    ``post_ln_w`` / ``post_ln_b`` the LayerNorm behind the split-K path (needs ``splitk=True``), returned under ``"ln_f32"`` / ``"ln_half"``.
+    ``ld_out`` is one leading dimension for every output and residual (>= the stored width): the buffers are allocated that wide and the
+    result holds the ``[:M, :N]`` view under the usual key and the whole buffer under ``key + "_buf"``; residuals are copied into buffers
+    of that width, NaN beside their own columns.  ``ldw`` pads the rows of ``w`` with NaN to that width.  ``guard_rows`` adds rows behind
+    the last one to every output buffer; ``sentinel`` is the value the output buffers are filled with before the launch (kept where the
+    kernel does not write)."""
     _need_cuda(a, w)
     if a.dtype != w.dtype or a.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError("a and w must both be float16 or bfloat16")
@@ -437,27 +452,77 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = Non
         M, K = a.shape
         lda = K
     N = w.shape[0]
+    if ldw is not None:
+        if ldw < K:
+            raise ValueError("gemm: ldw must be at least K")
+        wide = torch.full((N, int(ldw)), float("nan"), dtype=w.dtype, device=w.device)
+        wide[:, :K] = w.reshape(N, -1)[:, :K]
+        w = wide
+    else:
+        ldw = K
+    ld = N if ld_out is None else int(ld_out)
+    width = min(N, ld)      # (n_store < N with ld_out = n_store: the rows hold n_store columns)
+    if ld_out is not None and ld < (n_store if 0 < n_store < N else N):
+        raise ValueError("gemm: ld_out is narrower than the stored columns")
     res: Dict[str, torch.Tensor] = {}
+
+    def _out(key, dtype, extra_rows=0):
+        shape = (M + extra_rows + guard_rows, ld)
+        buf = torch.empty(shape, dtype=dtype, device=a.device) if sentinel is None else torch.full(shape, sentinel, dtype=dtype, device=a.device)
+        if ld_out is None and not guard_rows:
+            res[key] = buf
+        else:
+            res[key] = buf[:M + extra_rows, :width]
+            res[key + "_buf"] = buf
+        return _ptr(buf)
+
+    def _resid(r):
+        r = r.contiguous()
+        if ld_out is None:
+            return r, r.shape[-1]
+        wide = torch.full((M, ld), float("nan"), dtype=r.dtype, device=r.device)
+        wide[:, :r.shape[-1]] = r
+        return wide, ld
+
     args = GemmArgs()
-    args.A, args.lda, args.W, args.ldw = _ptr(a), lda, _ptr(w), K
+    args.A, args.lda, args.W, args.ldw = _ptr(a), lda, _ptr(w), int(ldw)
     args.M, args.N, args.K = M, N, K
     args.bias = _ptr(bias)
     if resid is not None:
-        resid = resid.contiguous()
-        args.resid, args.ldr = _ptr(resid), N
+        resid, args.ldr = _resid(resid)
+        args.resid = _ptr(resid)
     elif resid_half is not None:
-        resid_half = resid_half.contiguous()
-        args.resid_half, args.ldrh = _ptr(resid_half), N
-    args.alpha, args.gelu, args.variant = alpha, (2 if silu else int(gelu)), variant
+        resid_half, args.ldrh = _resid(resid_half)
+        args.resid_half = _ptr(resid_half)
+    if act is not None and (gelu or silu):
+        raise ValueError("gemm: act= and gelu= / silu= are two spellings of one field")
+    args.alpha, args.gelu, args.variant = alpha, (int(act) if act is not None else 2 if silu else int(gelu)), variant
     if out_f32:
-        res["f32"] = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        args.out_f32, args.ldo = _ptr(res["f32"]), N
+        args.out_f32, args.ldo = _out("f32", torch.float32), ld
     if out_half:
-        res["half"] = torch.empty((M + slack_rows, N), dtype=a.dtype, device=a.device)   # slack rows (uninitialised) for strided readers
-        args.out_half, args.ldh = _ptr(res["half"]), N
+        args.out_half, args.ldh = _out("half", a.dtype, slack_rows), ld   # slack rows (uninitialised) for strided readers
     if out_raw:
-        res["raw"] = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        args.out_raw, args.ldraw = _ptr(res["raw"]), N
+        args.out_raw, args.ldraw = _out("raw", torch.float32), ld
+    if row_zero is not None:
+        row_zero = row_zero.to(device=a.device, dtype=torch.uint8).contiguous()
+        if row_zero.numel() != M:
+            raise ValueError("gemm: row_zero must hold M entries")
+        args.row_zero = _ptr(row_zero)
+    args.half_scale, args.n_store = float(half_scale), int(n_store)
+    if a_scale is not None:
+        _need_cuda(a_scale)
+        a_scale = a_scale.contiguous()
+        if a_scale.dtype != torch.float32 or a_scale.dim() != 2 or a_scale_rows <= 0 or a_scale.shape[0] * a_scale_rows < M:
+            raise ValueError("gemm: a_scale must be fp32 [clips, a_scale_ld] with clips * a_scale_rows >= M")
+        args.a_scale, args.a_scale_rows, args.a_scale_ld = _ptr(a_scale), int(a_scale_rows), a_scale.shape[1]
+    if post_ln_w is not None:
+        post_ln_w, post_ln_b = post_ln_w.contiguous(), post_ln_b.contiguous()
+        args.post_ln_w, args.post_ln_b = _ptr(post_ln_w), _ptr(post_ln_b)
+        args.post_ln_eps, args.post_ln_round = float(post_ln_eps), int(post_ln_round)
+        if post_ln_out_f32:
+            args.post_ln_out_f32, args.post_ln_ldo = _out("ln_f32", torch.float32), ld
+        if post_ln_out_half:
+            args.post_ln_out_half, args.post_ln_ldh = _out("ln_half", a.dtype), ld
     if ln_rows is not None:
         ln_rows = _padded_rows(ln_rows, M)
         args.ln_rows, args.ln_s = _ptr(ln_rows), _ptr(ln_s)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 17
+#define AVEXHIP_ABI_VERSION 18
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -287,10 +287,11 @@ int avexhip_cast_half_to_f32(const void* in_dev, float* out_dev, int64_t n, int 
 
 /* out[m, n] = epilogue( sum_k A[m,k] * W[n,k] )      (torch.nn.Linear layout: W is [N, K])
  *   acc' = acc + bias[n]                               (bias may be NULL)
+ *   if row_zero && row_zero[m]:  acc' = 0              (ABI 18; before the raw tap and the residual)
  *   if out_raw:  out_raw[m,n] = acc'                   (fp32 "hook tap", e.g. fc2 raw output)
  *   if resid / resid_half:  acc' = resid[m,n] * alpha + acc'   (DeepNorm residual, backbone.py:360,372)
  *   if gelu:     acc' = gelu_erf(acc')                 (backbone.py:368)
- *   out_f32 / out_half (either may be NULL) receive acc'.
+ *   out_f32 / out_half (either may be NULL) receive acc' (out_half: acc' * half_scale when that is set, ABI 18).
  * Requirements: N % 128 == 0 (64 with the skinny kernel), K % 64 == 0, all leading dims in elements, 16-byte aligned rows. */
 typedef struct {
     const void*  A;  int64_t lda;      /* [M, K] half */
@@ -345,6 +346,30 @@ typedef struct {
      * avexhip_ln_rowstats makes of stats_out, bit for bit: stats_out is needed as scratch and avexhip_gemm runs avexhip_ln_rowstats
      * behind the product.  `rows_out` must be writable up to M rounded up to even.  NULL = off. */
     float* rows_out; float rows_eps;
+    /* ABI 18.  The options the encoder handles use, so that every epilogue can be tested through this entry point (all NULL / 0 = off;
+     * avexhip_gemm refuses the combinations no kernel is built for).
+     * row_zero: [M] bytes; a row with a non-zero byte takes 0 in place of acc + bias: its raw tap is 0.0, and its other outputs are what
+     * the rest of the epilogue makes of 0 -- resid * alpha through the activation, so exactly 0.0 without a residual (AVES' padded frames).
+     * Not with variant 7. */
+    const uint8_t* row_zero;
+    /* 0 or 1: off.  Otherwise (> 0, a power of two in practice) out_half receives value * half_scale; out_f32 and out_raw stay unscaled.
+     * Generic epilogues only: not with stats_out, pool_part, post_ln_* or variant 7. */
+    float half_scale;
+    /* 0, or the number of leading output columns that exist in memory (< N; a multiple of 4, of 16 with variant 7): the product is
+     * computed for N columns (W and bias padded by the caller), every output and residual row is only n_store wide and columns
+     * >= n_store are neither read nor written.  128-tile kernels (variants 1, 3, split-K) and variant 7. */
+    int32_t n_store;
+    /* A[m][k] is multiplied by a_scale[(m / a_scale_rows) * a_scale_ld + k] on its way into the product (the fp32 product rounded to the
+     * operand type): one scale row per clip of a_scale_rows consecutive rows.  a_scale_ld >= K, a multiple of 4.  Variants 7 and 1;
+     * variant 7 writes out_raw only together with a_scale, for N = 32 / 64 / 128 / 256. */
+    const float* a_scale; int32_t a_scale_rows; int32_t a_scale_ld;
+    /* LayerNorm of the finished rows y (after bias / row_zero / residual) behind the 128-tile kernel's workspace path:
+     * post_ln_out_* = LN(y) * post_ln_w + post_ln_b, and y itself still goes to out_f32 / out_half / out_raw when those are set.
+     * post_ln_round != 0: the statistics and the normalisation read y rounded to the operand type (what a LayerNorm kernel reading
+     * out_half would see); 0: the fp32 y.  Needs splitk_ws of at least M N floats, N % 256 == 0, N <= 1024, no activation, no n_store,
+     * variant 0 or 3. */
+    const float* post_ln_w; const float* post_ln_b; float post_ln_eps; int32_t post_ln_round;
+    float* post_ln_out_f32; int64_t post_ln_ldo; void* post_ln_out_half; int64_t post_ln_ldh;
 } avexhip_gemm_args;
 int avexhip_gemm(const avexhip_gemm_args* args, int dtype, void* stream);
 /* pool_part as written through avexhip_gemm_args.pool_part -> out[b, n] = mean over clip b's T rows of the raw GEMM output (bit-reproducible). */
