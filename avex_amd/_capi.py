@@ -218,6 +218,13 @@ SYMBOLS = {
     "avexhip_posconv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "avexhip_mean_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "avexhip_rel_bucket": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "avexhip_layernorm_pool": (C.c_int, [_P, C.c_int64, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "avexhip_glu_swish": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int, _P]),
+    "avexhip_agg_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "avexhip_zero_rows": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    "avexhip_row_sum_half": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "avexhip_lnr_fold": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, _P, _P, _P]),
+    "avexhip_bias_toeplitz": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "avexhip_beats_create": (_P, [C.POINTER(BeatsConfig), C.POINTER(Tensor), C.c_int]),
     "avexhip_beats_destroy": (None, [_P]),
     "avexhip_beats_num_tokens": (C.c_int, [_P, C.c_int64]),

@@ -140,7 +140,32 @@ extern "C" int avexhip_token_embed_ln(const void* patches_half, const float* pos
 }
 
 extern "C" int avexhip_mean_pool(const float* in, int B, int T, int C, float* out, void* stream) {
-    return avx::mean_pool(in, B, T, C, nullptr, out, (hipStream_t)stream);
+    return avx::mean_pool(in, B, T, C, out, (hipStream_t)stream);
+}
+
+// ABI 19: the remaining row kernels of elementwise.hip, each a pass-through to the launcher the encoder handles call (tests/test_gpu_rows.py)
+extern "C" int avexhip_layernorm_pool(const void* in_half, int64_t ld_in, const float* w, const float* b, float eps, int B, int T, int C,
+                                      float* out, int dtype, void* stream) {
+    return avx::layernorm_pool(in_half, ld_in, w, b, eps, B, T, C, out, dtype, (hipStream_t)stream);
+}
+extern "C" int avexhip_glu_swish(const void* in_half, int64_t M, int F, void* out_half, uint32_t* overflow_count, int dtype, void* stream) {
+    return avx::glu_swish(in_half, M, F, out_half, overflow_count, dtype, (hipStream_t)stream);
+}
+extern "C" int avexhip_agg_pool(const float* in, int B, int T, int C, int mode, float* out, void* stream) {
+    return avx::agg_pool(in, B, T, C, mode, out, (hipStream_t)stream);
+}
+extern "C" int avexhip_zero_rows(float* x_f32, int64_t ld32, void* x_half, int64_t ldh, int M, int C, const uint8_t* pad, void* stream) {
+    return avx::zero_rows(x_f32, ld32, x_half, ldh, M, C, pad, (hipStream_t)stream);
+}
+extern "C" int avexhip_row_sum_half(const void* w_half, int N, int K, float* out, int dtype, void* stream) {
+    return avx::row_sum_half(w_half, N, K, out, dtype, (hipStream_t)stream);
+}
+extern "C" int avexhip_lnr_fold(const float* gamma, const float* beta, const float* bias, float alpha, int N, float* ga, float* bb, void* stream) {
+    return avx::lnr_fold(gamma, beta, bias, alpha, N, ga, bb, (hipStream_t)stream);
+}
+extern "C" int avexhip_bias_toeplitz(const float* rel_table, const int32_t* lut, int maxd, int T, int H, float* out, void* stream) {
+    AVX_REQUIRE(rel_table && lut && out && maxd > 0 && T > 0 && H > 0, "bias_toeplitz: bad arguments (maxd=%d T=%d H=%d)", maxd, T, H);
+    return avx::bias_toeplitz(rel_table, lut, maxd, T, H, out, (hipStream_t)stream);
 }
 
 // T5 bidirectional bucket, fp32 arithmetic exactly as the reference writes it (backbone.py:438-473):
@@ -544,7 +569,7 @@ int forward_impl(avexhip_beats* h, const float* wav, const float* fbank_in, int 
             if (features_out || pooled_out) {
                 float* xo = features_out ? features_out + (size_t)c0 * Tt * E : x32;
                 AVXH_TRY(avx::layernorm(pre32, preh, E, h->lnE_w, h->lnE_b, 1e-5f, M, E, xo, E, nullptr, E, dt, cs));
-                if (pooled_out) AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, nullptr, pooled_out + (size_t)c0 * E, cs));
+                if (pooled_out) AVXH_TRY(avx::mean_pool(xo, Bc, Tt, E, pooled_out + (size_t)c0 * E, cs));
             }
         }
     }

@@ -286,6 +286,11 @@ static __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// max(a, x) that keeps a NaN from either side, like torch.max over a dimension (fmaxf returns its non-NaN operand): the pooled maxima
+static __device__ __forceinline__ float nan_max(float a, float x) { return (x > a || x != x) ? x : a; }
+static __device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 x) {
+    return (f32x4){nan_max(a[0], x[0]), nan_max(a[1], x[1]), nan_max(a[2], x[2]), nan_max(a[3], x[3])};
+}
 static __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -379,7 +384,7 @@ int layernorm(const float* in, const void* in_half, int64_t ld_in, const float* 
 int cast_to_half(const float* in, void* out, int64_t n, int dtype, hipStream_t s, unsigned int* ovf = nullptr);
 int row_sum_half(const void* w, int N, int K, float* out, int dtype, hipStream_t s);
 int cast_to_f32(const void* in, float* out, int64_t n, int dtype, hipStream_t s);
-int mean_pool(const float* in, int B, int T, int C, const uint8_t* frame_pad, float* out, hipStream_t s);
+int mean_pool(const float* in, int B, int T, int C, float* out, hipStream_t s);
 // [B * Tp, C] patch rows (half) -> [B * (Tp + 1), C]: class token row + (patch + position) rows, LayerNorm'ed
 int token_embed_ln(const void* patches, const float* pos, const float* cls, const float* w, const float* b, float eps, int B, int Tp, int C,
                    void* out_half, float* out_f32, int dtype, hipStream_t s);

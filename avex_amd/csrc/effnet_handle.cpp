@@ -449,7 +449,7 @@ extern "C" int avexhip_effnet_forward(avexhip_effnet* h, const float* mel, int B
         if (features_out) AVXH_TRY(avx::nhwc_to_nchw(w.headf, Np, Bc, hh * ww, h->head, nullptr, nullptr, features_out + (size_t)c0 * h->head * hh * ww, s));
         if (pooled_out) {
             AVX_REQUIRE(Np == h->head, "effnet_forward: pooled output needs a head width that is a multiple of 128 (%d)", h->head);
-            AVXH_TRY(avx::mean_pool(w.headf, Bc, hh * ww, h->head, nullptr, pooled_out + (size_t)c0 * h->head, s));
+            AVXH_TRY(avx::mean_pool(w.headf, Bc, hh * ww, h->head, pooled_out + (size_t)c0 * h->head, s));
         }
     }
     return avxh::finish_forward(h, prof, s);

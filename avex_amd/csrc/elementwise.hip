@@ -253,35 +253,23 @@ __global__ __launch_bounds__(1024) void layernorm_pool_kernel(const T* __restric
     }
 }
 
-// in [B,T,C] -> out [B,C]; block (64 columns x 4 token phases), grid (C/64, B).
-// With frame_pad: masked mean over non-padded tokens (beats_model.py:269-273).
-__global__ __launch_bounds__(256) void mean_pool_kernel(const float* __restrict__ in, int T, int C,
-                                                        const uint8_t* __restrict__ frame_pad,
-                                                        float* __restrict__ out) {
+// in [B,T,C] -> out [B,C]; block (64 columns x 4 token phases), grid (C/64, B).  Each phase adds its tokens t = ph, ph + 4, ... in
+// increasing order, the phases are combined as (p0 + p1) + (p2 + p3): tests/_rows_ref.py restates this order and the test holds the
+// kernel to its bits.  (The masked mean of beats_model.py:269-273 is taken on the host from the feature tensor, avex_amd/beats_model.py.)
+__global__ __launch_bounds__(256) void mean_pool_kernel(const float* __restrict__ in, int T, int C, float* __restrict__ out) {
     __shared__ float part[4][64];
-    __shared__ int cnt[4];
     const int b = blockIdx.y;
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const int ph = threadIdx.x >> 6;
     float s = 0.f;
-    int n = 0;
     if (c < C) {
-        for (int t = ph; t < T; t += 4) {
-            const bool pad = frame_pad && frame_pad[(int64_t)b * T + t];
-            if (!pad) {
-                s += in[((int64_t)b * T + t) * C + c];
-                ++n;
-            }
-        }
+        for (int t = ph; t < T; t += 4) s += in[((int64_t)b * T + t) * C + c];
     }
     part[ph][threadIdx.x & 63] = s;
-    if ((threadIdx.x & 63) == 0) cnt[ph] = n;
     __syncthreads();
     if (ph == 0 && c < C) {
         const float tot = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-        int nn = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-        if (nn < 1) nn = 1;
-        out[(int64_t)b * C + c] = tot / (float)nn;
+        out[(int64_t)b * C + c] = tot / (float)T;
     }
 }
 
@@ -451,19 +439,19 @@ __global__ __launch_bounds__(256) void pool_reduce_kernel(const float* __restric
     for (int64_t rb = r0 >> 6; rb <= (r1 >> 6); ++rb) {
         const int64_t first_clip = (rb * 64) / T;       // the clip of the block's first row owns slot 0
         const float v = part[(rb * 2 + (first_clip == b ? 0 : 1)) * N + n];
-        acc = mode == 1 ? fmaxf(acc, v) : acc + v;
+        acc = mode == 1 ? nan_max(acc, v) : acc + v;
     }
     out[(int64_t)b * ldo + n] = mode == 1 ? acc : acc * (1.0f / (float)T);
 }
 
-// fp32 [B, T, C] -> [B, C]: the maximum over a clip's rows (mode 2) or its first row (mode 3)
+// fp32 [B, T, C] -> [B, C]: the maximum over a clip's rows (mode 2; a NaN in a column stays, as in torch.max) or its first row (mode 3)
 __global__ __launch_bounds__(256) void agg_pool_kernel(const float* __restrict__ in, int T, int C, int mode, float* __restrict__ out) {
     const int c = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (c >= C) return;
     const float* p = in + (int64_t)b * T * C + c;
     float v = p[0];
     if (mode == 2)
-        for (int t = 1; t < T; ++t) v = fmaxf(v, p[(int64_t)t * C]);
+        for (int t = 1; t < T; ++t) v = nan_max(v, p[(int64_t)t * C]);
     out[(int64_t)b * C + c] = v;
 }
 
@@ -596,9 +584,9 @@ int layernorm(const float* in, const void* in_half, int64_t ld_in, const float* 
     return AVEXHIP_OK;
 }
 
-int mean_pool(const float* in, int B, int T, int C, const uint8_t* frame_pad, float* out, hipStream_t s) {
+int mean_pool(const float* in, int B, int T, int C, float* out, hipStream_t s) {
     AVX_REQUIRE(in && out && B > 0 && T > 0 && C > 0, "mean_pool: bad arguments");
-    hipLaunchKernelGGL(mean_pool_kernel, dim3((C + 63) / 64, B), dim3(256), 0, s, in, T, C, frame_pad, out);
+    hipLaunchKernelGGL(mean_pool_kernel, dim3((C + 63) / 64, B), dim3(256), 0, s, in, T, C, out);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
 }
@@ -646,7 +634,7 @@ int pool_reduce(const float* part, int B, int T, int N, float* out, int64_t ldo,
 }
 
 int agg_pool(const float* in, int B, int T, int C, int mode, float* out, hipStream_t s) {
-    if (mode == 1) return mean_pool(in, B, T, C, nullptr, out, s);
+    if (mode == 1) return mean_pool(in, B, T, C, out, s);
     AVX_REQUIRE(in && out && B > 0 && T > 0 && C > 0 && (mode == 2 || mode == 3), "agg_pool: bad arguments (mode %d)", mode);
     hipLaunchKernelGGL(agg_pool_kernel, dim3((C + 255) / 256, B), dim3(256), 0, s, in, T, C, mode, out);
     AVX_LAUNCH_CHECK();

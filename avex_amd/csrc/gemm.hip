@@ -901,8 +901,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
                                     *(f32x4*)dst = v0; *(f32x4*)(dst + 4) = v1;
                                 }
                             } else if constexpr (POOL == 2) {
-                                if (m < pool_bnd) { pa0 = __builtin_elementwise_max(pa0, v0); pa1 = __builtin_elementwise_max(pa1, v1); }
-                                else { pb0 = __builtin_elementwise_max(pb0, v0); pb1 = __builtin_elementwise_max(pb1, v1); }
+                                if (m < pool_bnd) { pa0 = nan_max4(pa0, v0); pa1 = nan_max4(pa1, v1); }
+                                else { pb0 = nan_max4(pb0, v0); pb1 = nan_max4(pb1, v1); }
                             } else if constexpr (POOL == 1) {
                                 if (m < pool_bnd) { pa0 += v0; pa1 += v1; } else { pb0 += v0; pb1 += v1; }
                             }
@@ -956,8 +956,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(avx::GemmArgs p) {
 #pragma unroll
                         for (int sh = 8; sh <= 32; sh <<= 1) {
                             if constexpr (POOL == 2) {
-                                pa0[e] = __builtin_fmaxf(pa0[e], __shfl_xor(pa0[e], sh, 64)); pa1[e] = __builtin_fmaxf(pa1[e], __shfl_xor(pa1[e], sh, 64));
-                                pb0[e] = __builtin_fmaxf(pb0[e], __shfl_xor(pb0[e], sh, 64)); pb1[e] = __builtin_fmaxf(pb1[e], __shfl_xor(pb1[e], sh, 64));
+                                pa0[e] = nan_max(pa0[e], __shfl_xor(pa0[e], sh, 64)); pa1[e] = nan_max(pa1[e], __shfl_xor(pa1[e], sh, 64));
+                                pb0[e] = nan_max(pb0[e], __shfl_xor(pb0[e], sh, 64)); pb1[e] = nan_max(pb1[e], __shfl_xor(pb1[e], sh, 64));
                             } else {
                                 pa0[e] += __shfl_xor(pa0[e], sh, 64); pa1[e] += __shfl_xor(pa1[e], sh, 64);
                                 pb0[e] += __shfl_xor(pb0[e], sh, 64); pb1[e] += __shfl_xor(pb1[e], sh, 64);

@@ -751,7 +751,7 @@ inline int tail_finish(HandleBase* h, const CoreCfg& c, CoreIo& io, const Tail& 
     io.final_f32 = t.xo;
     if (io.pooled_out) {
         prof.begin("mean_pool", 0.0);
-        AVXH_TRY(avx::mean_pool(t.xo, io.Bc, io.Tt, E, nullptr, io.pooled_out + io.c0 * E, cs));
+        AVXH_TRY(avx::mean_pool(t.xo, io.Bc, io.Tt, E, io.pooled_out + io.c0 * E, cs));
         prof.end();
     }
     return AVEXHIP_OK;

@@ -587,22 +587,145 @@ def ln_rowstats(stats: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
 
 
 def layernorm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5, half_dtype="f16",
-              want_f32: bool = True, want_half: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """LayerNorm of an fp32 or half ``[M, C]`` tensor -> (fp32 copy, half copy); either may be skipped."""
-    _need_cuda(x, weight, bias)
+              want_f32: bool = True, want_half: bool = True, *, ld_in: Optional[int] = None, ldo: Optional[int] = None,
+              ldh: Optional[int] = None, out_f32: Optional[torch.Tensor] = None,
+              out_half: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """LayerNorm of an fp32 or half ``[M, C]`` tensor -> (fp32 copy, half copy); either may be skipped.
+
+    ``ld_in`` / ``ldo`` / ``ldh`` are leading dimensions wider than the rows: with ``ld_in`` the input is a ``[M, ld_in]`` buffer whose
+    first ``C = weight.numel()`` columns are the rows; with ``ldo`` / ``ldh`` the outputs are ``[M, ld]`` buffers.  ``out_f32`` /
+    ``out_half`` are preallocated 2-D output buffers (at least M rows, the leading dimension their row length unless given): they are
+    written in place and returned as they are, so that a caller can fill them with a sentinel first."""
+    _need_cuda(x, weight, bias, out_f32, out_half)
     x = x.contiguous()
-    M, Cc = x.shape
+    M = x.shape[0]
+    Cc = x.shape[1] if ld_in is None else int(weight.numel())
+    ld_in = x.shape[1] if ld_in is None else int(ld_in)
+    if ld_in != x.shape[1]:
+        raise ValueError("layernorm: ld_in must be the row length of the input buffer")
     if x.dtype == torch.float32:
         code = dtype_code(half_dtype)
         pin, pinh = _ptr(x), None
     else:
         code = _capi.F16 if x.dtype == torch.float16 else _capi.BF16
         pin, pinh = None, _ptr(x)
-    o32 = torch.empty((M, Cc), dtype=torch.float32, device=x.device) if want_f32 else None
-    oh = torch.empty((M, Cc), dtype=half_torch_dtype(code), device=x.device) if want_half else None
-    check(lib().avexhip_layernorm(pin, pinh, Cc, _ptr(weight), _ptr(bias), eps, M, Cc, _ptr(o32), Cc, _ptr(oh), Cc,
+
+    def _out(buf, want, ld, dtype):
+        if buf is not None:
+            if buf.dim() != 2 or buf.dtype != dtype or not buf.is_contiguous() or buf.shape[0] < M:
+                raise ValueError("layernorm: a preallocated output must be a contiguous 2-D buffer of the output type with at least M rows")
+            ld = buf.shape[1] if ld is None else int(ld)
+            if ld != buf.shape[1] or ld < Cc:
+                raise ValueError("layernorm: an output's leading dimension must be its buffer's row length, at least C")
+            return buf, ld
+        if not want:
+            return None, Cc if ld is None else int(ld)
+        ld = Cc if ld is None else int(ld)
+        return torch.empty((M, ld), dtype=dtype, device=x.device), ld
+
+    o32, ldo = _out(out_f32, want_f32, ldo, torch.float32)
+    oh, ldh = _out(out_half, want_half, ldh, half_torch_dtype(code))
+    check(lib().avexhip_layernorm(pin, pinh, ld_in, _ptr(weight), _ptr(bias), eps, M, Cc, _ptr(o32), ldo, _ptr(oh), ldh,
                                   code, _stream()), "layernorm")
     return o32, oh
+
+
+def layernorm_pool(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, B: int, T: int) -> torch.Tensor:
+    """Mean over each clip's T rows of LayerNorm(x) for half ``[B * T, ld_in]`` rows (``C = weight.numel()`` leading columns) -> ``[B, C]`` fp32."""
+    _need_cuda(x, weight, bias)
+    code = _capi.F16 if x.dtype == torch.float16 else _capi.BF16
+    x = x.contiguous()
+    if x.dim() != 2 or x.shape[0] != B * T:
+        raise ValueError("layernorm_pool: x must be [B * T, ld_in]")
+    Cc = int(weight.numel())
+    out = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+    check(lib().avexhip_layernorm_pool(_ptr(x), x.shape[1], _ptr(weight), _ptr(bias), eps, B, T, Cc, _ptr(out), code, _stream()), "layernorm_pool")
+    return out
+
+
+def _overflow_ptr(overflow: Optional[torch.Tensor]) -> Optional[int]:
+    if overflow is not None and (overflow.numel() != 1 or overflow.element_size() != 4 or not overflow.is_cuda):
+        raise ValueError("overflow must be a 4-byte device scalar")
+    return _ptr(overflow)
+
+
+def glu_swish(x: torch.Tensor, overflow: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x[:, :F] * silu(x[:, F:])`` of a half ``[M, 2F]`` tensor; ``overflow`` is the optional device counter of the f16 range alarm."""
+    _need_cuda(x)
+    code = _capi.F16 if x.dtype == torch.float16 else _capi.BF16
+    x = x.contiguous()
+    M, F2 = x.shape
+    out = torch.empty((M, F2 // 2), dtype=x.dtype, device=x.device)
+    check(lib().avexhip_glu_swish(_ptr(x), M, F2 // 2, _ptr(out), _overflow_ptr(overflow), code, _stream()), "glu_swish")
+    return out
+
+
+def agg_pool(x: torch.Tensor, mode: int) -> torch.Tensor:
+    """fp32 ``[B, T, C]`` -> ``[B, C]``: mode 1 mean, 2 maximum, 3 first row."""
+    _need_cuda(x)
+    B, T, Cc = x.shape
+    out = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+    check(lib().avexhip_agg_pool(_ptr(x.contiguous()), B, T, Cc, int(mode), _ptr(out), _stream()), "agg_pool")
+    return out
+
+
+def pool_reduce(part: torch.Tensor, B: int, T: int, mode: int = 0) -> torch.Tensor:
+    """``pool_part`` blocks ``[ceil(B * T / 64), 2, N]`` of a pooled-tap GEMM -> ``[B, N]``: mode 0 mean, 1 maximum."""
+    _need_cuda(part)
+    part = part.contiguous()
+    N = part.shape[-1]
+    out = torch.empty((B, N), dtype=torch.float32, device=part.device)
+    check(lib().avexhip_pool_reduce_mode(_ptr(part), B, T, N, _ptr(out), N, int(mode), _stream()), "pool_reduce")
+    return out
+
+
+def zero_rows(x_f32: Optional[torch.Tensor], x_half: Optional[torch.Tensor], pad: Optional[torch.Tensor], C_: int) -> None:
+    """In place: rows m with ``pad[m] != 0`` become +0 in the first ``C_`` columns of the 2-D buffers given (row length = leading dimension)."""
+    _need_cuda(x_f32, x_half, pad)
+    ref = x_f32 if x_f32 is not None else x_half
+    M = ref.shape[0] if pad is None else int(pad.numel())
+    for t in (x_f32, x_half):
+        if t is not None and (t.dim() != 2 or not t.is_contiguous() or t.shape[0] < M or t.shape[1] < C_):
+            raise ValueError("zero_rows: buffers must be contiguous [>= M, >= C]")
+    check(lib().avexhip_zero_rows(_ptr(x_f32), 0 if x_f32 is None else x_f32.shape[1], _ptr(x_half), 0 if x_half is None else x_half.shape[1],
+                                  M, int(C_), _ptr(pad), _stream()), "zero_rows")
+
+
+def row_sum_half(w: torch.Tensor) -> torch.Tensor:
+    """Row sums (fp32 accumulation) of a half ``[N, K]`` matrix."""
+    _need_cuda(w)
+    code = _capi.F16 if w.dtype == torch.float16 else _capi.BF16
+    w = w.contiguous()
+    N, Kd = w.shape
+    out = torch.empty((N,), dtype=torch.float32, device=w.device)
+    check(lib().avexhip_row_sum_half(_ptr(w), N, Kd, _ptr(out), code, _stream()), "row_sum_half")
+    return out
+
+
+def lnr_fold(gamma: torch.Tensor, beta: torch.Tensor, bias: torch.Tensor, alpha: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(gamma * alpha, fma(alpha, beta, bias))``: the column vectors of a residual-side LayerNorm fold."""
+    _need_cuda(gamma, beta, bias)
+    N = int(gamma.numel())
+    ga, bb = torch.empty_like(gamma), torch.empty_like(gamma)
+    check(lib().avexhip_lnr_fold(_ptr(gamma.contiguous()), _ptr(beta.contiguous()), _ptr(bias.contiguous()), float(alpha), N, _ptr(ga), _ptr(bb),
+                                 _stream()), "lnr_fold")
+    return ga, bb
+
+
+def bucket_lut(num_buckets: int, max_distance: int, maxd: int) -> np.ndarray:
+    """``rel_bucket(d)`` for d = -maxd .. maxd (int32, host): the table :func:`bias_toeplitz` gathers through."""
+    return np.array([rel_bucket(d, num_buckets, max_distance) for d in range(-maxd, maxd + 1)], dtype=np.int32)
+
+
+def bias_toeplitz(rel_table: torch.Tensor, lut: torch.Tensor, maxd: int, T: int) -> torch.Tensor:
+    """``[H, 2T - 1]`` Toeplitz rows of the relative position bias from ``rel_table [num_buckets, H]`` fp32 and ``lut [2 maxd + 1]`` int32."""
+    _need_cuda(rel_table, lut)
+    if lut.dtype != torch.int32 or lut.numel() != 2 * maxd + 1 or rel_table.dtype != torch.float32:
+        raise ValueError("bias_toeplitz: lut must be int32 [2 * maxd + 1], rel_table fp32")
+    H = rel_table.shape[1]
+    out = torch.empty((H, 2 * T - 1), dtype=torch.float32, device=rel_table.device)
+    check(lib().avexhip_bias_toeplitz(_ptr(rel_table.contiguous()), _ptr(lut.contiguous()), int(maxd), int(T), H, _ptr(out), _stream()), "bias_toeplitz")
+    return out
 
 
 def attention(qkv: torch.Tensor, B: int, T: int, H: int, bias_tab: Optional[torch.Tensor],

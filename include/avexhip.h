@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 18
+#define AVEXHIP_ABI_VERSION 19
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -424,6 +424,32 @@ int avexhip_token_embed_ln(const void* patches_half, const float* pos, const flo
 
 /* mean over T: in [B, T, C] fp32 -> out [B, C] fp32 (features.mean(dim=1), README:80). */
 int avexhip_mean_pool(const float* in_dev, int B, int T, int C, float* out_dev, void* stream);
+
+/* ABI 19.  The other row kernels an encoder forward runs, exported so that each can be tested off the model shapes
+ * (tests/test_gpu_rows.py); every one is the launcher the handles call, unchanged. */
+/* LayerNorm over C of half rows followed by the mean over each clip's T rows (features.mean(dim=1) of the last LayerNorm,
+ * beats_model.py:275) without the [B, T, C] tensor: in_half [B * T rows, ld_in] -> out [B, C] fp32.  C % 8 == 0, C <= 768, ld_in % 8 == 0.
+ * Bit-reproducible; a clip's result does not depend on the batch it is in. */
+int avexhip_layernorm_pool(const void* in_half_dev, int64_t ld_in, const float* weight, const float* bias, float eps, int B, int T, int C,
+                           float* out_dev, int dtype, void* stream);
+/* GLU_Linear's gate (modules.py:155-171, "swish"): out[m][f] = in[m][f] * silu(in[m][F + f]) for in [M, 2F] half, out [M, F] half; F % 8 == 0.
+ * overflow_count (may be NULL): the f16 range alarm, + 1 per 8-element group holding a value beyond +-65504 (never with bf16). */
+int avexhip_glu_swish(const void* in_half_dev, int64_t M, int F, void* out_half_dev, uint32_t* overflow_count, int dtype, void* stream);
+/* in [B, T, C] fp32 -> out [B, C]: mode 1 mean (= avexhip_mean_pool), 2 maximum over the T rows (a NaN stays, as in torch.max), 3 the
+ * first row (the aggregations of extract_embeddings, beats_model.py:403-417). */
+int avexhip_agg_pool(const float* in_dev, int B, int T, int C, int mode, float* out_dev, void* stream);
+/* rows m with pad[m] != 0 become +0 in x_f32 [M, ld32] and / or x_half [M, ldh] (either may be NULL; 16-bit elements of either operand
+ * type): `x[padding_mask] = 0`, backbone.py:169-170.  pad == NULL is a no-op. */
+int avexhip_zero_rows(float* x_f32_dev, int64_t ld32, void* x_half_dev, int64_t ldh, int M, int C, const uint8_t* pad_dev, void* stream);
+/* out[n] = sum_k w[n][k] of a half [N, K] matrix, fp32 accumulation (the column-sum vector of a LayerNorm-folded weight). */
+int avexhip_row_sum_half(const void* w_half_dev, int N, int K, float* out_dev, int dtype, void* stream);
+/* ga[n] = gamma[n] * alpha, bb[n] = fma(alpha, beta[n], bias[n]): the column vectors of a residual-side LayerNorm fold. */
+int avexhip_lnr_fold(const float* gamma_dev, const float* beta_dev, const float* bias_dev, float alpha, int N, float* ga_dev, float* bb_dev,
+                     void* stream);
+/* out[h][r] = rel_table[lut[clamp(r - (T - 1), -maxd, maxd) + maxd]][h]: the [H, 2T - 1] Toeplitz rows avexhip_attention takes
+ * (compute_bias, backbone.py:475-492) from rel_table [num_buckets, H] and lut [2 maxd + 1] = avexhip_rel_bucket(d) for d = -maxd .. maxd,
+ * where maxd is a distance at which the buckets have saturated. */
+int avexhip_bias_toeplitz(const float* rel_table_dev, const int32_t* lut_dev, int maxd, int T, int H, float* out_dev, void* stream);
 
 #ifdef AVEX_DIAG   /* diagnostic build only (AVEX_AMD_DIAG=1 python -m avex_amd.build -> libavexhip_diag.so); the product library exports none of these */
 /* Debug aid: `blocks` workgroups hold a 26 880-byte LDS pattern for `iters` re-check rounds;
