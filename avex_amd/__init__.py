@@ -13,6 +13,7 @@ from .base_model import ModelBase
 from .search import EmbeddingIndex, query_by_example
 from .detection import decode_events, detect_events
 from .examples import ExampleBank, detect_events_by_example
+from .density import dbscan, k_distance
 
 __version__ = "0.1.0"
 
@@ -20,5 +21,5 @@ __all__ = [
     "load_model", "register_model", "get_model_spec", "list_models", "describe_model", "list_model_layers",
     "register_model_class", "get_model_class", "list_model_classes", "build_model", "build_model_from_spec",
     "get_checkpoint_path", "load_label_mapping", "ModelBase", "ModelSpec", "AudioConfig", "EmbeddingIndex", "query_by_example",
-    "decode_events", "detect_events", "ExampleBank", "detect_events_by_example",
+    "decode_events", "detect_events", "ExampleBank", "detect_events_by_example", "dbscan", "k_distance",
 ]

@@ -148,6 +148,12 @@ class ExamplesArgs(C.Structure):
                 ("nearest", C.c_void_p), ("ld_nearest", C.c_int64)]
 
 
+class DensityArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("dpad", C.c_int32), ("metric", C.c_int32), ("eps", C.c_float), ("min_samples", C.c_int32), ("rows", C.c_void_p),
+                ("row0", C.c_int64), ("n_rows", C.c_int32), ("n_cols", C.c_int32), ("cols", C.c_void_p), ("col0", C.c_int64), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -293,6 +299,17 @@ SYMBOLS = {
     "avexhip_examples_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "avexhip_examples_score": (C.c_int, [C.POINTER(ExamplesArgs), _P]),
     "avexhip_examples_class_mean": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P]),
+    "avexhip_density_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "avexhip_density_max_block": (C.c_int, []),
+    "avexhip_density_begin": (C.c_int, [C.POINTER(DensityArgs), _P]),
+    "avexhip_density_norms": (C.c_int, [C.POINTER(DensityArgs), _P]),
+    "avexhip_density_count": (C.c_int, [C.POINTER(DensityArgs), _P]),
+    "avexhip_density_core": (C.c_int, [C.POINTER(DensityArgs), _P]),
+    "avexhip_density_round_begin": (C.c_int, [C.POINTER(DensityArgs), _P]),
+    "avexhip_density_hook": (C.c_int, [C.POINTER(DensityArgs), _P]),
+    "avexhip_density_round_end": (C.c_int, [C.POINTER(DensityArgs), _P, _P]),
+    "avexhip_density_labels": (C.c_int, [C.POINTER(DensityArgs), _P, _P, _P, _P, _P]),
+    "avexhip_density_summary": (C.c_int, [C.POINTER(DensityArgs), _P, C.c_int, _P, _P, _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

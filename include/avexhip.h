@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 19
+#define AVEXHIP_ABI_VERSION 20
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -806,6 +806,68 @@ int avexhip_silhouette_max_n(void);        /* 524288 */
 int avexhip_silhouette_prepare(const avexhip_silhouette_args* args, void* stream);
 int avexhip_silhouette_batch(const avexhip_silhouette_args* args, void* stream);
 int avexhip_silhouette_finalize(const avexhip_silhouette_args* args, double* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Density clustering (ABI 20): DBSCAN over embeddings that are already on the device -- what sklearn.cluster.DBSCAN(eps, min_samples,
+ * metric) returns, wherever no pair of rows sits at the threshold -- with O(n) integers of working memory; the n x n matrix is never
+ * stored.  Rows are PREPARED rows of dpad floats (dpad % 32 == 0, zero beyond the real width): for "cosine" the rows of
+ * avexhip_search_prepare_rows (divided by max(||row||, 1e-12)), for "euclidean" centred rows (avexhip_clustering_centred_rows).  They
+ * come in blocks of at most avexhip_density_max_block() rows -- the chunks of an index, or pieces of them -- and the caller walks the
+ * (row block, column block) pairs; per-row state lives in the workspace under global row numbers 0 .. n - 1.
+ *   distance   cosine: min(max(1 - s, 0), 2); euclidean: sqrt(max((nx + ny) - 2 s, 0)); s the fp32 MFMA tile product of the two rows (the
+ *              bits a search returns), nx the diagonal of the same product: bit-identical rows are at distance exactly 0.  s(i, j) and
+ *              s(j, i) are the same bits, so the relation below is exactly symmetric.
+ *   neighbour  j is a neighbour of i iff distance <= eps (fp32, inclusive); a row is always its own neighbour.  A row whose squared norm
+ *              is not a finite number (it holds a NaN or an Inf) is outside the graph: neighbour of nobody, count 0, label -1.
+ *   core       n_neighbors[i] (itself included) >= min_samples.
+ *   clusters   the connected components of the core rows, numbered 0, 1, .. in the order of their lowest core row; a row that is not
+ *              core takes the smallest number among its core neighbours, or -1.
+ *   1. avexhip_density_begin        clears the counts and the flags;
+ *   2. avexhip_density_norms        every row block once: the squared norms;
+ *   3. avexhip_density_count        every (row block, column block) pair: n_neighbors, one integer atomicAdd per (row, workgroup);
+ *   4. avexhip_density_core         core rows; a core row's label is its own number;
+ *   5. rounds, until one changes nothing: avexhip_density_round_begin; avexhip_density_hook for every pair -- per row the smallest label
+ *      among its core neighbours, sent by integer atomicMin to the row and, from a core row, to the row its label names (the root's
+ *      hook); avexhip_density_round_end -- labels take the minima, pointer jumping to the fixed point, *changed_out_dev = 1 when a label
+ *      changed.  The caller reads that word: the one synchronisation of a round.
+ *   6. avexhip_density_labels       cluster numbers by counting roots (no sort), labels, core flags, counts;
+ *      summary_out_dev[0] = clusters, [1] = rows outside the graph;
+ *   7. avexhip_density_summary      per cluster its size and its exemplar: the core row with the most neighbours, the lower row on a tie.
+ * All atomics are integer add / min / max: the result is the same bit for bit for every blocking and from run to run.  Nothing here
+ * allocates or synchronises.  Limits: n <= 2^31 - 1.
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_DENSITY_EUCLIDEAN 0
+#define AVEXHIP_DENSITY_COSINE 1
+typedef struct {
+    int64_t n;                   /* rows of the whole set */
+    int32_t dpad;                /* floats per prepared row, a multiple of 32 */
+    int32_t metric;              /* AVEXHIP_DENSITY_* */
+    float eps;                   /* finite, >= 0 */
+    int32_t min_samples;         /* >= 1 (read by avexhip_density_core) */
+    const float* rows;           /* row block: [n_rows, dpad] prepared rows on the device (_norms, _count, _hook) */
+    int64_t row0;                /* global number of its first row */
+    int32_t n_rows;              /* 1 .. avexhip_density_max_block() */
+    int32_t n_cols;
+    const float* cols;           /* column block: [n_cols, dpad] (_count, _hook) */
+    int64_t col0;
+    void* workspace;
+    size_t workspace_bytes;
+} avexhip_density_args;
+
+size_t avexhip_density_workspace_bytes(int64_t n);      /* 0 for a bad n; O(n) integers, independent of the width and of n^2 */
+int avexhip_density_max_block(void);                    /* 4194304 */
+int avexhip_density_begin(const avexhip_density_args* args, void* stream);
+int avexhip_density_norms(const avexhip_density_args* args, void* stream);
+int avexhip_density_count(const avexhip_density_args* args, void* stream);
+int avexhip_density_core(const avexhip_density_args* args, void* stream);
+int avexhip_density_round_begin(const avexhip_density_args* args, void* stream);
+int avexhip_density_hook(const avexhip_density_args* args, void* stream);
+int avexhip_density_round_end(const avexhip_density_args* args, int32_t* changed_out_dev, void* stream);
+int avexhip_density_labels(const avexhip_density_args* args, int32_t* labels_out_dev, uint8_t* core_out_dev, int32_t* n_neighbors_out_dev,
+                           int32_t* summary_out_dev, void* stream);
+/* labels_dev: what avexhip_density_labels wrote; n_clusters: summary_out_dev[0] >= 1; sizes_out_dev / exemplar_out_dev: [n_clusters] */
+int avexhip_density_summary(const avexhip_density_args* args, const int32_t* labels_dev, int n_clusters, int32_t* sizes_out_dev,
+                            int32_t* exemplar_out_dev, void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
