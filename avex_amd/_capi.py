@@ -114,6 +114,10 @@ class Window(C.Structure):
     _fields_ = [("base", C.c_int64), ("n_samples", C.c_int64), ("start", C.c_int64), ("valid", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ActivityRecording(C.Structure):
+    _fields_ = [("base", C.c_int64), ("n_samples", C.c_int64), ("first_frame", C.c_int64), ("first_block", C.c_int32), ("floor_rank", C.c_int32)]
+
+
 class SearchArgs(C.Structure):
     _fields_ = [("query", C.c_void_p), ("ld_query", C.c_int64), ("nb", C.c_int32), ("d", C.c_int32), ("batch", C.c_int32), ("k", C.c_int32),
                 ("chunk_rows", C.c_int32), ("normalise", C.c_int32), ("stages", C.c_int32), ("exclude", C.c_int32), ("chunk", C.c_void_p),
@@ -310,6 +314,10 @@ SYMBOLS = {
     "avexhip_density_round_end": (C.c_int, [C.POINTER(DensityArgs), _P, _P]),
     "avexhip_density_labels": (C.c_int, [C.POINTER(DensityArgs), _P, _P, _P, _P, _P]),
     "avexhip_density_summary": (C.c_int, [C.POINTER(DensityArgs), _P, C.c_int, _P, _P, _P]),
+    "avexhip_activity_frames": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, _P, _P]),
+    "avexhip_activity_floor": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "avexhip_activity_count": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "avexhip_activity_select": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_float, _P, _P, _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

@@ -2,7 +2,8 @@
 // device: decoded, mono, resampled once -- instead of one ingest per window.
 //
 // The reference crops a long clip to a single window (pad_or_window, avex/data/audio_utils.py:16-73) and reserves a name for the step
-// that would say which windows are worth embedding (avex/preprocessing/activity_detector.py, an empty file).  A window row here is
+// that would say which windows are worth embedding (avex/preprocessing/activity_detector.py, an empty file; activity.hip builds it on the
+// table and the statistics of this file).  A window row here is
 // pad_or_window(wav[start:], window_len, "start"): the samples, then zeros, padding_mask True on the zeros.
 //   window_stats_kernel    per window: max |x| (fp32) and sum x^2 (fp64) over its valid samples
 //   window_select_kernel   flags from two thresholds -> the kept window numbers in increasing order and their count (prefix sum, no atomics)

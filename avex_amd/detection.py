@@ -233,7 +233,8 @@ def detect_events(model: Any, probe: Callable[[torch.Tensor], torch.Tensor], sou
                   min_windows: int = 1, max_events: Optional[int] = None, probe_batch_size: int = 4096, return_scores: bool = False,
                   layers: Optional[Sequence[Any]] = None, aggregation: str = "mean", batch_size: int = 256, min_rms_db: Optional[float] = None,
                   min_peak_db: Optional[float] = None, tail: str = "pad", batch_invariant: Optional[bool] = None, sr: int = 16000,
-                  res_type: Optional[str] = None, device: Any = None, max_resident_samples: Optional[int] = None) -> Dict[str, Any]:
+                  res_type: Optional[str] = None, device: Any = None, max_resident_samples: Optional[int] = None,
+                  activity: Optional[Any] = None) -> Dict[str, Any]:
     """Files to events: the windows of ``sources`` are embedded (:func:`avex_amd.recordings.embed_recordings`, whose gate and model
     arguments this takes), ``probe(emb[lo:hi])`` scores them ``probe_batch_size`` at a time -- any callable from ``[n, D]`` to ``[n, C]``:
     an :mod:`avex_amd.probes` head in ``feature_mode``, or a torch module -- and :func:`decode_events` (whose rule arguments this takes)
@@ -255,7 +256,7 @@ def detect_events(model: Any, probe: Callable[[torch.Tensor], torch.Tensor], sou
         device = p.device if p is not None and p.is_cuda else None
     limit = recordings.MAX_RESIDENT_SAMPLES if max_resident_samples is None else max_resident_samples
     ws = recordings._windows_of(sources, window_s, hop_s, sr, tail, res_type, device, limit)
-    results = recordings._embed(model, ws, layers, aggregation, batch_size, min_rms_db, min_peak_db, batch_invariant)
+    results = recordings._embed(model, ws, layers, aggregation, batch_size, min_rms_db, min_peak_db, batch_invariant, activity)
     names = [os.fspath(s) if isinstance(s, (str, os.PathLike)) else str(i) for i, s in enumerate(sources)]
     dev = ws.wav.device
     with torch.cuda.device(dev):

@@ -3,8 +3,9 @@
 The rest of the package inherits the reference's evaluation view of audio -- one clip, one window: ``pad_or_window`` crops a long clip to a
 single ``start`` / ``center`` / ``random`` window (avex/data/audio_utils.py:16-73) and drops the rest, and the step that would say which
 windows are worth embedding is a name without a body (avex/preprocessing/activity_detector.py is empty; its long-audio wrappers chunk by
-hand).  Here a recording is decoded, averaged to mono and resampled ONCE (:func:`avex_amd.ingest.load_audio`'s pieces) and stays on the
-device; three kernels of ``csrc/windows.hip`` read that resident waveform through a table of ``(recording, start, valid)``:
+hand; :mod:`avex_amd.activity` is that step here, the ``activity=`` gate of the functions below).  Here a recording is decoded, averaged
+to mono and resampled ONCE (:func:`avex_amd.ingest.load_audio`'s pieces) and stays on the device; three kernels of ``csrc/windows.hip``
+read that resident waveform through a table of ``(recording, start, valid)``:
 
 * ``avexhip_window_stats``   per window the peak ``max |x|`` and the energy ``sum x^2`` (fp64), in an order that depends on the window alone;
 * ``avexhip_window_select``  windows over two thresholds -> their numbers in increasing order and the count (prefix sum, no atomics);
@@ -237,7 +238,7 @@ def windows(source: Any, window_s: float, hop_s: Optional[float] = None, *, sr: 
 
 
 def _embed(model: Any, ws: RecordingWindows, layers: Optional[Sequence[Any]], aggregation: str, batch_size: int, min_rms_db: Optional[float],
-           min_peak_db: Optional[float], batch_invariant: Optional[bool]) -> List[Dict[str, Any]]:
+           min_peak_db: Optional[float], batch_invariant: Optional[bool], activity: Optional[Any] = None) -> List[Dict[str, Any]]:
     if int(batch_size) <= 0:
         raise ValueError(f"batch_size={batch_size}: a positive number of windows expected")
     batch_size = min(int(batch_size), _MAX_ROWS)
@@ -251,10 +252,13 @@ def _embed(model: Any, ws: RecordingWindows, layers: Optional[Sequence[Any]], ag
     else:
         model.ensure_hooks_registered()
     n = ws.n_windows
-    gated = min_rms_db is not None or min_peak_db is not None
-    kept_dev, kept = None, np.arange(n, dtype=np.int64)
+    gated = min_rms_db is not None or min_peak_db is not None or activity is not None
+    kept_dev, kept, act = None, np.arange(n, dtype=np.int64), None
+    if activity is not None:
+        from .activity import band_activity
+        act = band_activity(ws, activity)
     if gated:
-        kept_dev = ws.select(min_rms_db, min_peak_db)
+        kept_dev = ws.select(min_rms_db, min_peak_db) if act is None else act.select(min_rms_db, min_peak_db)
         host = kept_dev.cpu().numpy()                             # the call's one host synchronisation: the count, and the list with it
         kept = host[:int(host[n])].astype(np.int64)
     chunks: List[Any] = []
@@ -271,7 +275,7 @@ def _embed(model: Any, ws: RecordingWindows, layers: Optional[Sequence[Any]], ag
         emb = torch.cat(chunks)
     rms_db, peak_db = ws._device_db()
     out = []
-    for w0, w1 in ws.ranges:
+    for r, (w0, w1) in enumerate(ws.ranges):
         a, b = (int(v) for v in np.searchsorted(kept, [w0, w1]))
         idx = kept[a:b]
         flags = np.zeros(w1 - w0, dtype=bool)
@@ -279,13 +283,15 @@ def _embed(model: Any, ws: RecordingWindows, layers: Optional[Sequence[Any]], ag
         out.append({"embeddings": [e[a:b] for e in emb] if isinstance(emb, list) else emb[a:b],
                     "window_index": torch.from_numpy(idx - w0), "start_s": ws.start_s[idx], "end_s": ws.end_s[idx],
                     "kept": torch.from_numpy(flags), "rms_db": rms_db[w0:w1], "peak_db": peak_db[w0:w1]})
+        if act is not None:
+            out[-1].update(active_frames=act.active_frames[w0:w1], floor=act.floor[r])
     return out
 
 
 def embed_recordings(model: Any, sources: Sequence[Any], window_s: float, hop_s: Optional[float] = None, *, layers: Optional[Sequence[Any]] = None,
                      aggregation: str = "mean", batch_size: int = 256, min_rms_db: Optional[float] = None, min_peak_db: Optional[float] = None,
                      tail: str = "pad", batch_invariant: Optional[bool] = None, sr: int = 16000, res_type: Optional[str] = None, device: Any = None,
-                     max_resident_samples: int = MAX_RESIDENT_SAMPLES) -> List[Dict[str, Any]]:
+                     max_resident_samples: int = MAX_RESIDENT_SAMPLES, activity: Optional[Any] = None) -> List[Dict[str, Any]]:
     """:func:`embed_recording` over several recordings whose windows share the batches, so short files still fill them; one dict per
     source, in order, each with the bits the single-source call gives when the model is batch invariant."""
     if len(sources) == 0:
@@ -294,18 +300,20 @@ def embed_recordings(model: Any, sources: Sequence[Any], window_s: float, hop_s:
         p = next(model.parameters(), None)
         device = p.device if p is not None and p.is_cuda else None
     ws = _windows_of(list(sources), window_s, hop_s, sr, tail, res_type, device, max_resident_samples)
-    return _embed(model, ws, layers, aggregation, batch_size, min_rms_db, min_peak_db, batch_invariant)
+    return _embed(model, ws, layers, aggregation, batch_size, min_rms_db, min_peak_db, batch_invariant, activity)
 
 
 def embed_recording(model: Any, source: Any, window_s: float, hop_s: Optional[float] = None, *, layers: Optional[Sequence[Any]] = None,
                     aggregation: str = "mean", batch_size: int = 256, min_rms_db: Optional[float] = None, min_peak_db: Optional[float] = None,
                     tail: str = "pad", batch_invariant: Optional[bool] = None, sr: int = 16000, res_type: Optional[str] = None, device: Any = None,
-                    max_resident_samples: int = MAX_RESIDENT_SAMPLES) -> Dict[str, Any]:
+                    max_resident_samples: int = MAX_RESIDENT_SAMPLES, activity: Optional[Any] = None) -> Dict[str, Any]:
     """One embedding per window of a recording, for any ``ModelBase`` of the package (only ``register_hooks_for_layers`` and
     ``extract_embeddings({"raw_wav", "padding_mask"}, aggregation=...)`` are used).
 
     ``layers``: registered when given; ``None`` keeps what is registered, or takes the model's last layer.  ``min_rms_db`` /
-    ``min_peak_db`` (dB re full scale; ``None``: off) gate the windows by their statistics before any of them reaches the model.
+    ``min_peak_db`` (dB re full scale; ``None``: off) gate the windows by their statistics before any of them reaches the model;
+    ``activity`` (an :class:`avex_amd.activity.ActivityGate`; ``None``: off) adds its band condition to that gate and the keys
+    ``active_frames`` (``[n_windows, n_bands]`` int32) and ``floor`` (``[n_bands]`` float32), on the device.
     ``batch_invariant`` as :func:`avex_amd.extraction.extract_embeddings_in_memory` takes it: with ``True`` a window's embedding does not
     depend on ``batch_size`` or on the windows beside it.  Returns
 
@@ -317,4 +325,4 @@ def embed_recording(model: Any, source: Any, window_s: float, hop_s: Optional[fl
     With a gate the only host synchronisation is the copy of the kept list, once per call; without one there is none."""
     return embed_recordings(model, [source], window_s, hop_s, layers=layers, aggregation=aggregation, batch_size=batch_size, min_rms_db=min_rms_db,
                             min_peak_db=min_peak_db, tail=tail, batch_invariant=batch_invariant, sr=sr, res_type=res_type, device=device,
-                            max_resident_samples=max_resident_samples)[0]
+                            max_resident_samples=max_resident_samples, activity=activity)[0]

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 20
+#define AVEXHIP_ABI_VERSION 21
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -868,6 +868,54 @@ int avexhip_density_labels(const avexhip_density_args* args, int32_t* labels_out
 /* labels_dev: what avexhip_density_labels wrote; n_clusters: summary_out_dev[0] >= 1; sizes_out_dev / exemplar_out_dev: [n_clusters] */
 int avexhip_density_summary(const avexhip_density_args* args, const int32_t* labels_dev, int n_clusters, int32_t* sizes_out_dev,
                             int32_t* exemplar_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Band-limited activity gate (ABI 21): per sliding window of the resident waveforms above, the frames whose energy in a frequency band
+ * stands over the recording's own noise floor -- the body of the name the reference leaves empty (avex/preprocessing/activity_detector.py).
+ *   frames     n_fft = 512; recording r of n_r samples has F_r = (n_r - 512) / hop + 1 frames (0 when n_r < 512), frame f the samples
+ *              [f hop, f hop + 512) of its recording, no padding; the frames of all recordings lie back to back (first_frame).
+ *   energy     y = x * w in fp32, w the periodic Hann table tables_dev[0 .. 512); X = DFT(y); E[b, f] = the fp32 sum of |X[k]|^2 over the
+ *              bins bands[b][0] <= k < bands[b][1] (0 <= lo < hi <= 257).  A frame of zeros gives +0 in every band, a frame holding a NaN
+ *              or an Inf gives NaN in every band, and E[b, f] depends on its recording's samples and hop alone: the same bits in any
+ *              company, from run to run.  energy_dev is [n_bands, total_frames].
+ *   floor      floor_dev[r, b] = the energy whose bit pattern (uint32: energies are >= +0, NaN sorts above +Inf) has rank floor_rank
+ *              (0 = lowest) among the F_r frames of the recording in band b -- an exact radix select, integer LDS atomics only; NaN when
+ *              F_r = 0.  nonfinite_dev[r] = the recording's NaN frames.
+ *   count      per window (start, valid) of recording win_rec[w], over its frames ceil(start / hop) .. floor((start + valid - 512) / hop):
+ *              n_frames_dev[w]; active_dev[w, b] = those with E > fl32(max(floor, floor_min) * ratio) (strict; false when either side is
+ *              NaN); max_energy_dev[w, b] = the largest E (NaN if any is NaN, -inf without a frame).
+ *   select     avexhip_window_select with one more condition: active_dev[w, b] >= min_active_frames in any band (AVEXHIP_ACTIVITY_ANY)
+ *              or in every band (AVEXHIP_ACTIVITY_ALL).  With min_active_frames = 0 the list is avexhip_window_select's.
+ * tables_dev: [512] fp32 w[n] = 0.5 - 0.5 cos(2 pi n / 512), then [512] pairs (cos, -sin)(2 pi k / 512), both computed in fp64 and
+ * rounded.  rec_host / rec_dev: the same table on the host (read for the argument checks) and on the device.  Every entry point refuses
+ * with AVEXHIP_ERR_INVALID before anything is launched: null or misaligned pointers, hop outside 32 .. 512, n_bands outside 1 .. 8, a
+ * band outside the bins, NaN thresholds, a recording that leaves wav_dev, first_frame / first_block / floor_rank / total_frames that do
+ * not follow from the samples and the hop, a window that is not inside its recording.  Nothing here allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_ACTIVITY_MAX_BANDS 8
+#define AVEXHIP_ACTIVITY_MIN_HOP 32
+#define AVEXHIP_ACTIVITY_ANY 0
+#define AVEXHIP_ACTIVITY_ALL 1
+typedef struct {
+    int64_t base;            /* first sample of the recording in wav_dev, counted in floats */
+    int64_t n_samples;       /* samples of the recording */
+    int64_t first_frame;     /* frames of the recordings in front of it */
+    int32_t first_block;     /* the same count in workgroups of eight frames: the sum of ceil(F / 8) */
+    int32_t floor_rank;      /* rank of the floor among its F frames, 0 .. F - 1 (0 when F = 0) */
+} avexhip_activity_recording;
+int avexhip_activity_frames(const float* wav_dev, int64_t wav_samples, const avexhip_activity_recording* rec_host,
+                            const avexhip_activity_recording* rec_dev, int n_rec, int hop, const int32_t* bands_host, int n_bands,
+                            const float* tables_dev, int64_t total_frames, float* energy_dev, void* stream);
+int avexhip_activity_floor(const float* energy_dev, int64_t total_frames, const avexhip_activity_recording* rec_host,
+                           const avexhip_activity_recording* rec_dev, int n_rec, int hop, int n_bands, float* floor_dev, int32_t* nonfinite_dev,
+                           void* stream);
+int avexhip_activity_count(const avexhip_window* win_host, const avexhip_window* win_dev, const int32_t* win_rec_host, const int32_t* win_rec_dev,
+                           int n_win, const avexhip_activity_recording* rec_host, const avexhip_activity_recording* rec_dev, int n_rec, int hop,
+                           const float* energy_dev, int64_t total_frames, const float* floor_dev, int n_bands, float floor_min, float ratio,
+                           int32_t* n_frames_dev, int32_t* active_dev, float* max_energy_dev, void* stream);
+int avexhip_activity_select(const avexhip_window* win_dev, const double* energy_dev, const float* peak_dev, const int32_t* active_dev, int n_win,
+                            int n_bands, int min_active_frames, int mode, double thr_energy, float thr_peak, int32_t* kept_dev, int32_t* count_dev,
+                            void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
