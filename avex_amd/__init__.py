@@ -15,6 +15,7 @@ from .detection import decode_events, detect_events
 from .examples import ExampleBank, detect_events_by_example
 from .density import dbscan, k_distance
 from .activity import ActivityGate, band_activity
+from .annotations import Annotations, score_events, sweep_thresholds
 
 __version__ = "0.1.0"
 
@@ -23,5 +24,5 @@ __all__ = [
     "register_model_class", "get_model_class", "list_model_classes", "build_model", "build_model_from_spec",
     "get_checkpoint_path", "load_label_mapping", "ModelBase", "ModelSpec", "AudioConfig", "EmbeddingIndex", "query_by_example",
     "decode_events", "detect_events", "ExampleBank", "detect_events_by_example", "dbscan", "k_distance",
-    "ActivityGate", "band_activity",
+    "ActivityGate", "band_activity", "Annotations", "score_events", "sweep_thresholds",
 ]

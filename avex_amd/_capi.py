@@ -144,6 +144,14 @@ class EventsResult(C.Structure):
                 ("peak", C.c_void_p), ("peak_window", C.c_void_p), ("mean", C.c_void_p)]
 
 
+class AnnotMatchArgs(C.Structure):
+    _fields_ = [("sequence", C.c_void_p), ("class_id", C.c_void_p), ("first", C.c_void_p), ("last", C.c_void_p), ("n_pred", C.c_int64),
+                ("cell_lo", C.c_void_p), ("cell_hi", C.c_void_p), ("n_windows", C.c_int64), ("seg_offsets_host", C.c_void_p),
+                ("seg_offsets_dev", C.c_void_p), ("ref_lo", C.c_void_p), ("ref_hi", C.c_void_p), ("n_ref", C.c_int64), ("iou", C.c_double),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("counts", C.c_void_p), ("errors", C.c_void_p), ("n_rec", C.c_int32),
+                ("n_classes", C.c_int32)]
+
+
 class ExamplesArgs(C.Structure):
     _fields_ = [("bank", C.c_void_p), ("row_id", C.c_void_p), ("m", C.c_int64), ("d", C.c_int32), ("n_classes", C.c_int32), ("n_segments", C.c_int32),
                 ("batch", C.c_int32), ("segments", C.c_void_p), ("tile_segments", C.c_void_p), ("class_segments", C.c_void_p), ("query", C.c_void_p),
@@ -318,6 +326,11 @@ SYMBOLS = {
     "avexhip_activity_floor": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "avexhip_activity_count": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P]),
     "avexhip_activity_select": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_float, _P, _P, _P]),
+    "avexhip_annot_chunk_pairs": (C.c_int, []),
+    "avexhip_annot_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "avexhip_annot_overlap": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "avexhip_annot_count": (C.c_int, [C.POINTER(AnnotMatchArgs), _P]),
+    "avexhip_annot_match": (C.c_int, [C.POINTER(AnnotMatchArgs), _P, _P, _P, _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

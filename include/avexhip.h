@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 21
+#define AVEXHIP_ABI_VERSION 22
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -916,6 +916,75 @@ int avexhip_activity_count(const avexhip_window* win_host, const avexhip_window*
 int avexhip_activity_select(const avexhip_window* win_dev, const double* energy_dev, const float* peak_dev, const int32_t* active_dev, int n_win,
                             int n_bands, int min_active_frames, int mode, double thr_energy, float thr_peak, int32_t* kept_dev, int32_t* count_dev,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Scoring detections against annotations (ABI 22): how many samples of each window the marked calls of each class cover, and which
+ * predicted event (avexhip_events_emit's columns, where they lie) is matched with which marked one.  Every decision is integer
+ * arithmetic on sample counts, or one fp64 multiply and compare; no atomics; the same bits on every run.
+ *   reference events   per (recording, class) the annotations merged where they overlap or touch, disjoint and ordered: ref_lo / ref_hi
+ *              [n_ref] int64 samples, sorted by (recording, class, lo); seg_offsets[r * n_classes + c] .. [.. + 1] are the events of
+ *              segment (r, c) (n_rec * n_classes + 1 entries, the last n_ref); ref_prefix[j] = the summed lengths of the events below j
+ *              (n_ref + 1 entries).
+ *   overlap    out_dev[w, c] (int32, [n_win, n_classes]) = the samples of [span_lo[w], span_hi[w]) that the class-c events of recording
+ *              win_rec[w] cover: one thread per entry, classes fastest; two binary searches in the segment, a difference of the prefix, a
+ *              clip of the two edge events.  An empty span gives 0.  Spans and events are at most 2^31 - 1 samples long (the caller's
+ *              check: longer ones saturate).
+ *   cells      cell_lo / cell_hi [n_windows] int64: the stretch of its recording that window w owns; the cells of a recording partition
+ *              it in window order, so the events of one class and recording span disjoint, ordered stretches
+ *              [cell_lo[first], cell_hi[last]).
+ *   compatible a predicted span P and a reference event R: inter > 0 and (double)inter >= iou * (double)union, AVEXHIP_ANNOT_MIN_IOU <= iou <= 1.
+ *   matching   per segment the walk over predictions i and reference events j in time order: compatible -> match both, advance both;
+ *              else advance the one that ends first (the prediction on a tie).  Both sides are disjoint, so compatible pairs never
+ *              cross and the walk is a maximum matching.
+ *                count   one thread per prediction: its segment, the events its span overlaps (two binary searches), the compatible
+ *                        ones among them -> counts_dev[i]; errors_dev[i] = 1 for a row that is malformed (first >= 0 with last < first,
+ *                        a window, sequence or class outside the tables), that follows a filler row (first < 0), or that does not come
+ *                        after the row before it in (sequence, class, span) order -- else 0.  Filler rows count 0 pairs.
+ *                (the caller makes pair_offsets_dev [n_pred + 1], the exclusive prefix of counts_dev with the total at the end)
+ *                match   fills both outputs with -1; writes the pairs (i, j) in (i, j) order, those past n_pred + n_ref dropped; the
+ *                        walk as a scan of functions on two bits of state (prediction matched, event matched) over chunks of
+ *                        AVEXHIP_ANNOT_CHUNK_PAIRS pairs: chunk functions, their carries (one workgroup), the chunks applied;
+ *                        match_of_pred_dev[i] = j and match_of_ref_dev[j] = i for every pair taken.
+ *              With a nonzero errors_dev entry the matches are unspecified; every access stays inside the arrays all the same.
+ * Host copies (win_rec_host, seg_offsets_host) are read for the argument checks.  Every entry point refuses with AVEXHIP_ERR_INVALID
+ * before anything is launched: null or misaligned pointers, counts below 1 or past 2^31 - 1, offsets that do not start at 0, decrease
+ * or end elsewhere than n_ref, a window of a recording outside 0 .. n_rec - 1, an iou outside its range or NaN; a workspace smaller
+ * than avexhip_annot_workspace_bytes(n_pred, n_ref, n_segments) gives AVEXHIP_ERR_WORKSPACE (0 from that function: sizes it refuses).
+ * Nothing here allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_ANNOT_MIN_IOU 0.0625
+#define AVEXHIP_ANNOT_CHUNK_PAIRS 256
+typedef struct {
+    const int32_t* sequence;           /* [n_pred] device: the columns of avexhip_events_result, filler rows (first < 0) behind */
+    const int32_t* class_id;
+    const int32_t* first;
+    const int32_t* last;
+    int64_t n_pred;                    /* rows of the four columns (their capacity), >= 1 */
+    const int64_t* cell_lo;            /* [n_windows] device */
+    const int64_t* cell_hi;
+    int64_t n_windows;
+    const int64_t* seg_offsets_host;   /* [n_rec * n_classes + 1] */
+    const int64_t* seg_offsets_dev;
+    const int64_t* ref_lo;             /* [n_ref] device */
+    const int64_t* ref_hi;
+    int64_t n_ref;                     /* >= 1 */
+    double iou;
+    void* workspace;                   /* device, 16-byte aligned */
+    size_t workspace_bytes;
+    int64_t* counts;                   /* [n_pred] device, written by count */
+    int32_t* errors;                   /* [n_pred] device, written by count */
+    int32_t n_rec;
+    int32_t n_classes;
+} avexhip_annot_match_args;
+int avexhip_annot_chunk_pairs(void);
+size_t avexhip_annot_workspace_bytes(int64_t n_pred, int64_t n_ref, int64_t n_segments);
+int avexhip_annot_overlap(const int64_t* span_lo_dev, const int64_t* span_hi_dev, const int32_t* win_rec_host, const int32_t* win_rec_dev,
+                          int64_t n_win, int n_rec, int n_classes, const int64_t* seg_offsets_host, const int64_t* seg_offsets_dev,
+                          const int64_t* ref_lo_dev, const int64_t* ref_hi_dev, const int64_t* ref_prefix_dev, int64_t n_ref,
+                          int32_t* out_dev, void* stream);
+int avexhip_annot_count(const avexhip_annot_match_args* args, void* stream);
+int avexhip_annot_match(const avexhip_annot_match_args* args, const int64_t* pair_offsets_dev, int32_t* match_of_pred_dev,
+                        int32_t* match_of_ref_dev, void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
