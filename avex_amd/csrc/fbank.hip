@@ -214,6 +214,9 @@ __global__ __launch_bounds__(256) void fbank_kernel(avx::FbankDev fb, const floa
     for (int m = lane; m < nm; m += 64) {
         const int st = fb.mel_start[m], len = fb.mel_len[m], off = fb.mel_off[m];
         float e0 = 0.f, e1 = 0.f;
+        // a filter without taps (the narrowest low bins of a 128-mel bank fall between two FFT bins) still sees its frame in the reference's
+        // dense power @ mel_fb: 0 * NaN = NaN there, so a poisoned frame is NaN in every bin.  Power is >= 0: +0 for a clean frame, the same bits.
+        if (len == 0) { e0 = 0.f * pw[wave][0][0]; e1 = 0.f * pw[wave][1][0]; }
 #pragma unroll 4
         for (int t = 0; t < len; ++t) {
             const float wt = fb.mel_w[off + t];

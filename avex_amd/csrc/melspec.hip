@@ -37,6 +37,12 @@ __device__ __forceinline__ int ord_key(float v) {            // monotonic float 
     return b >= 0 ? b : b ^ 0x7fffffff;
 }
 __device__ __forceinline__ float ord_val(int k) { return __builtin_bit_cast(float, k >= 0 ? k : k ^ 0x7fffffff); }
+// A NaN among a clip's values makes its min and max NaN (x.amin / x.amax of the reference, audio_utils.py:168-172, propagate it): the two
+// keys no finite or infinite value can beat, which ord_val turns back into NaNs, so the normalisation pass makes the whole clip NaN.
+__device__ __forceinline__ void minmax_poison(int* minmax, int b) {
+    atomicMin(minmax + 2 * b, (int)0x80000000);
+    atomicMax(minmax + 2 * b + 1, 0x7fffffff);
+}
 
 template <int FB>
 __device__ __forceinline__ void melspec_epilogue(const MelDev& md, const float* pw, int pw_ld, int b, int f0, int frames, float* __restrict__ out,
@@ -123,6 +129,7 @@ __device__ __forceinline__ void melspec_epilogue(const MelDev& md, const float* 
                                                  int* __restrict__ minmax, int take_log, int tid, int nthreads) {
     const int f = tid % FB, grp = tid / FB, G = nthreads / FB;
     float mn = __builtin_inff(), mx = -__builtin_inff();
+    bool bad = false;                                    // a NaN among the stored values: fminf / fmaxf return their non-NaN operand
     const bool fvalid = f0 + f < frames;
     for (int m = grp; m < md.n_out; m += G) {
         float e;
@@ -137,11 +144,16 @@ __device__ __forceinline__ void melspec_epilogue(const MelDev& md, const float* 
         if (fvalid) {
             out[((int64_t)b * md.n_out + m) * frames + f0 + f] = y;
             mn = fminf(mn, y); mx = fmaxf(mx, y);
+            bad = bad || y != y;
         }
     }
     if (minmax) {
         mn = -wave_max(-mn); mx = wave_max(mx);
-        if ((tid & 63) == 0 && mx >= mn) { atomicMin(minmax + 2 * b, ord_key(mn)); atomicMax(minmax + 2 * b + 1, ord_key(mx)); }
+        const bool poison = __any(bad);
+        if ((tid & 63) == 0) {
+            if (poison) minmax_poison(minmax, b);
+            else if (mx >= mn) { atomicMin(minmax + 2 * b, ord_key(mn)); atomicMax(minmax + 2 * b + 1, ord_key(mx)); }
+        }
     }
 }
 
@@ -437,6 +449,7 @@ __global__ __launch_bounds__(FB * 8) void stft_fft_kernel(MelDev md, const float
     __syncthreads();
     // coalesced store [clip][bin][frame] (FB consecutive frames per row) + per-clip min / max
     float mn = __builtin_inff(), mx = -__builtin_inff();
+    bool bad = false;                                    // a NaN among the stored values (fminf / fmaxf skip it): poisons the clip's min / max
     const int f = tid % FB, fr_ok = f0 + f < frames;
 #pragma unroll 4
     for (int m = tid / FB; m < ((STFT_KNOCK & 32) ? 0 : md.n_out); m += (FB * 8) / FB) {
@@ -444,18 +457,22 @@ __global__ __launch_bounds__(FB * 8) void stft_fft_kernel(MelDev md, const float
         if (fr_ok) {
             out[((int64_t)b * md.n_out + m) * frames + f0 + f] = y;
             mn = fminf(mn, y); mx = fmaxf(mx, y);
+            bad = bad || y != y;
         }
     }
     if (minmax && !(STFT_KNOCK & 64)) {
         // one pair of atomics per workgroup (through the staging tile, which every wave has finished reading), not per wave: 65 k atomics
         // on 512 addresses were 44 us of the kernel
         mn = -wave_max(-mn); mx = wave_max(mx);
+        const bool poison_w = __any(bad);
         __syncthreads();
-        if (lane == 0) { stage[2 * wave] = mn; stage[2 * wave + 1] = mx; }
+        if (lane == 0) { stage[3 * wave] = mn; stage[3 * wave + 1] = mx; stage[3 * wave + 2] = poison_w ? 1.f : 0.f; }
         __syncthreads();
         if (tid == 0) {
-            for (int w = 1; w < NW; ++w) { mn = fminf(mn, stage[2 * w]); mx = fmaxf(mx, stage[2 * w + 1]); }
-            if (mx >= mn) { atomicMin(minmax + 2 * b, ord_key(mn)); atomicMax(minmax + 2 * b + 1, ord_key(mx)); }
+            bool poison = poison_w;
+            for (int w = 1; w < NW; ++w) { mn = fminf(mn, stage[3 * w]); mx = fmaxf(mx, stage[3 * w + 1]); poison = poison || stage[3 * w + 2] != 0.f; }
+            if (poison) minmax_poison(minmax, b);
+            else if (mx >= mn) { atomicMin(minmax + 2 * b, ord_key(mn)); atomicMax(minmax + 2 * b + 1, ord_key(mx)); }
         }
     }
 }
@@ -509,7 +526,7 @@ extern "C" avexhip_melspec_plan* avexhip_melspec_plan_create(const avexhip_melsp
     const int half = ((nf + 63) / 64) * 64, nc = 2 * half, ntw = half / 64;
     if (!use_fft && (N > 1024 || (ntw != 3 && ntw != 4 && ntw != 5 && ntw != 7 && ntw != 9))) {
         avexhip_set_error("melspec_plan_create: n_fft=%d has a prime factor above 5 and its dense column tiling %d is not instantiated "
-                          "(dense path: n_fft 256..384, 400..512, 514..640, 770..896, 1026..1024)", N, ntw);
+                          "(dense path: n_fft 256..382, 384..510, 512..638, 768..894, 1024)", N, ntw);
         return nullptr;
     }
     std::vector<float> hwin(win), hmel;

@@ -192,6 +192,8 @@ int posconv_pack(const float* g, const float* v, int E, int groups, int K, void*
     AVX_REQUIRE(g && v && w_packed, "posconv_pack: null argument");
     AVX_REQUIRE(groups > 0 && E % groups == 0 && K > 0, "posconv_pack: bad shape E=%d groups=%d K=%d", E, groups, K);
     const int cg = E / groups;
+    // the packed layout is whole 96-wide tap pairs per group (nu = cg * K / 96 of them): any other shape would make the blocks overlap
+    AVX_REQUIRE(((int64_t)cg * K) % 96 == 0, "posconv_pack: E / groups * K = %d * %d is not a multiple of 96 (the packed layout holds whole tap pairs)", cg, K);
     float* norm = nullptr;
     AVX_HIP_CHECK(hipMalloc((void**)&norm, sizeof(float) * K));
     hipLaunchKernelGGL(posconv_norm_kernel, dim3(K), dim3(256), 0, s, v, E * cg, K, norm);

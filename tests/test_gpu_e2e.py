@@ -398,6 +398,13 @@ def test_config_c5_nan_stays_in_its_clip(built_lib):
     assert np.isnan(p[2]).all()
     for i in (0, 1, 3):
         assert np.array_equal(p[i], clean[i])
+    # the reference's per-clip amin / amax propagate the NaN (audio_utils.py:168-172): the whole mel image of the clip is NaN (the 800-point
+    # in-place kernel's min / max used to skip it), and with it every position of its feature map
+    img = plan(torch.from_numpy(bad).cuda())
+    assert bool(torch.isnan(img[2]).all()) and bool(torch.isfinite(img[[0, 1, 3]]).all())
+    feats = enc.forward(img, want_features=True)["features"]
+    assert bool(torch.isnan(feats[2]).all())
+    assert bool(torch.isfinite(feats[[0, 1, 3]]).all())
 
 
 def test_bias_table_cache_is_bounded_and_eviction_is_invisible(built_lib, base_sd):
