@@ -4,15 +4,17 @@
 //   activity_floor_kernel    per (recording, band) the energy of a given rank among the recording's frames: an exact 8-bit radix select
 //                            on the bit patterns (energies are >= +0, so the patterns order like the numbers; NaN sorts above +Inf)
 //   activity_count_kernel    per (window, band) the frames with E > max(floor, floor_min) * ratio, and the largest energy
-//   activity_select_kernel   window_select_kernel's ballot / prefix scheme with the extra condition on those counts
-// The transform is fbank.hip's: one wave64 per PAIR of frames packed as z = a + i b, three register-resident radix-8 passes exchanged
-// through a per-wave LDS buffer at row stride 72.  A workgroup takes eight consecutive frames of ONE recording and stages their span
+//   activity_select_kernel   window_select_kernel's condition and one more on those counts, through the same block_compact (block_prims.h)
+// The transform is shared with fbank.hip (fft512.h): one wave64 per PAIR of frames packed as z = a + i b, three register-resident radix-8
+// passes exchanged through a per-wave LDS buffer at row stride 72.  A workgroup takes eight consecutive frames of ONE recording and stages their span
 // ((8 - 1) hop + 512 samples) in LDS once, so overlapping frames cost one HBM read per sample; pairs are (2 i, 2 i + 1) of the recording,
 // so a frame's energies depend on its recording and the hop alone.  Every read is at base + j with j < n_samples of a recording the
 // entry point has checked against the buffer.
 #include <math.h>
 
+#include "block_prims.h"
 #include "common.h"
+#include "fft512.h"
 
 namespace {
 
@@ -28,33 +30,6 @@ struct ActBands {
     int lo[AVEXHIP_ACTIVITY_MAX_BANDS], hi[AVEXHIP_ACTIVITY_MAX_BANDS];      // bins lo .. hi - 1
 };
 
-__device__ __forceinline__ float2 operator+(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 operator-(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // a * (-i)
-
-// in-place 8-point DFT, natural order in and out (fbank.hip's, restated: that file's outputs are pinned bit for bit)
-__device__ __forceinline__ void dft8(float2 (&x)[8]) {
-    const float c = 0.70710678118654752440f;
-    const float2 a0 = x[0] + x[4], a1 = x[0] - x[4], a2 = x[2] + x[6], a3 = mul_mi(x[2] - x[6]);
-    const float2 b0 = x[1] + x[5], b1 = x[1] - x[5], b2 = x[3] + x[7], b3 = mul_mi(x[3] - x[7]);
-    const float2 e0 = a0 + a2, e2 = a0 - a2, e1 = a1 + a3, e3 = a1 - a3;
-    const float2 o0 = b0 + b2, o2 = b0 - b2, o1 = b1 + b3, o3 = b1 - b3;
-    const float2 t1 = make_float2(c * (o1.x + o1.y), c * (o1.y - o1.x));   // o1 * W8^1
-    const float2 t2 = mul_mi(o2);                                          // o2 * W8^2
-    const float2 t3 = make_float2(c * (o3.y - o3.x), -c * (o3.x + o3.y));  // o3 * W8^3
-    x[0] = e0 + o0; x[4] = e0 - o0;
-    x[1] = e1 + t1; x[5] = e1 - t1;
-    x[2] = e2 + t2; x[6] = e2 - t2;
-    x[3] = e3 + t3; x[7] = e3 - t3;
-}
-
-constexpr int ZROW = 72;  // complex elements per LDS row (64 + 8 pad)
-// The exchange buffers are private to one wave, whose LDS operations execute in order: no workgroup barrier between the passes, only
-// the compiler kept from moving LDS accesses across the exchange points (fbank.hip's idiom).
-#define AVX_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-
-__device__ __forceinline__ bool act_non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }      // exponent all ones
 __host__ __device__ __forceinline__ int64_t act_frames_of(int64_t n_samples, int hop) { return n_samples < kActFrame ? 0 : (n_samples - kActFrame) / hop + 1; }
 
 // grid: one workgroup per eight frames of a recording (avexhip_activity_recording::first_block numbers them), 256 threads.
@@ -116,7 +91,7 @@ __global__ __launch_bounds__(256) void activity_frames_kernel(const float* __res
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             v[q] = src[lane + 64 * q];
-            nonfin |= act_non_finite(v[q]);
+            nonfin |= non_finite(v[q]);
         }
         bad[fr] = has[fr] && __any(nonfin);
         const bool use = has[fr] && !bad[fr];
@@ -132,35 +107,7 @@ __global__ __launch_bounds__(256) void activity_frames_kernel(const float* __res
         live[fr] = __any(nz);
     }
 
-    // ---- 512-point complex FFT: three radix-8 passes (fbank.hip's layout) ------------------------------------------------------------
-    dft8(x);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; ++k1) x[k1] = cmul(x[k1], tw[lane * k1]);
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1) z[k1 * ZROW + lane] = x[k1];
-    AVX_WAVE_SYNC();
-    {
-        const int k1 = lane >> 3, m2 = lane & 7;
-#pragma unroll
-        for (int m1 = 0; m1 < 8; ++m1) x[m1] = z[k1 * ZROW + 8 * m1 + m2];
-        dft8(x);
-#pragma unroll
-        for (int j1 = 1; j1 < 8; ++j1) x[j1] = cmul(x[j1], tw[8 * m2 * j1]);
-        AVX_WAVE_SYNC();
-#pragma unroll
-        for (int j1 = 0; j1 < 8; ++j1) z[k1 * ZROW + j1 * 8 + m2] = x[j1];
-    }
-    AVX_WAVE_SYNC();
-    {
-        const int k1 = lane & 7, j1 = lane >> 3;
-#pragma unroll
-        for (int m2 = 0; m2 < 8; ++m2) x[m2] = z[k1 * ZROW + j1 * 8 + m2];
-        dft8(x);
-        AVX_WAVE_SYNC();
-#pragma unroll
-        for (int j2 = 0; j2 < 8; ++j2) z[lane + 64 * j2] = x[j2];  // natural order Z[k]
-    }
-    AVX_WAVE_SYNC();
+    fft512_wave(x, z, tw, lane);                                 // Z[k] at z[k]
 
     // ---- the two real spectra by conjugate symmetry (k = 0 and k = 256 pair with themselves), power, band sums -----------------------
     // A lane adds its bins of a band in increasing order, the wave its lanes by a butterfly: a fixed order, the same for every launch.
@@ -306,39 +253,18 @@ __global__ __launch_bounds__(64) void activity_count_kernel(const avexhip_window
     }
 }
 
-// window_select_kernel (windows.hip) with one more condition: active_frames >= min_active in any band (mode 0) or in every band (mode 1).
+// window_select_kernel's predicate (windows.hip) with one more condition: active_frames >= min_active in any band (mode 0) or in every band (mode 1).
 __global__ __launch_bounds__(kActSelectThreads) void activity_select_kernel(const avexhip_window* __restrict__ win, const double* __restrict__ energy,
                                                                             const float* __restrict__ peak, const int* __restrict__ active, int n_win,
                                                                             int n_bands, int min_active, int mode, double thr_energy, float thr_peak,
                                                                             int* __restrict__ kept, int* __restrict__ count) {
-    __shared__ int wave_total[kActSelectThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < n_win; base += kActSelectThreads) {
-        const int i = base + threadIdx.x;
-        bool keep = false;
-        if (i < n_win) {
-            const int valid = win[i].valid;
-            keep = valid > 0 && energy[i] >= thr_energy * (double)valid && peak[i] >= thr_peak;      // a NaN fails both compares
-            int bands_ok = 0;
-            for (int b = 0; b < n_bands; ++b) bands_ok += active[(int64_t)i * n_bands + b] >= min_active ? 1 : 0;
-            keep = keep && (mode == 0 ? bands_ok > 0 : bands_ok == n_bands);
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_total[wave] = __popcll(m);
-        __syncthreads();
-        int before = __popcll(m & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-        for (int q = 0; q < kActSelectThreads / 64; ++q) {
-            const int t = wave_total[q];
-            before += q < wave ? t : 0;
-            total += t;
-        }
-        if (keep) kept[carry + before] = i;
-        carry += total;
-        __syncthreads();                                         // wave_total is rewritten by the next pass
-    }
-    if (threadIdx.x == 0) *count = carry;
+    block_compact<kActSelectThreads>(n_win, [&](int i) {
+        const int valid = win[i].valid;
+        const bool keep = valid > 0 && energy[i] >= thr_energy * (double)valid && peak[i] >= thr_peak;      // a NaN fails both compares
+        int bands_ok = 0;
+        for (int b = 0; b < n_bands; ++b) bands_ok += active[(int64_t)i * n_bands + b] >= min_active ? 1 : 0;
+        return keep && (mode == 0 ? bands_ok > 0 : bands_ok == n_bands);
+    }, kept, count);
 }
 
 // What every entry point refuses in the recording table; *blocks_out = the workgroups of the frames kernel.  wav_samples < 0: no buffer to check.
@@ -382,8 +308,7 @@ extern "C" int avexhip_activity_frames(const float* wav_dev, int64_t wav_samples
     AVX_REQUIRE(((uintptr_t)wav_dev & 15) == 0 && ((uintptr_t)tables_dev & 15) == 0 && ((uintptr_t)energy_dev & 3) == 0,
                 "activity_frames: wav_dev and tables_dev must be 16-byte aligned, energy_dev 4-byte aligned");
     AVX_REQUIRE(wav_samples >= 1, "activity_frames: wav_samples=%lld", (long long)wav_samples);
-    int rc = activity_bands_check("activity_frames", n_bands);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(activity_bands_check("activity_frames", n_bands));
     ActBands bands;
     memset(&bands, 0, sizeof(bands));
     bands.n = n_bands;
@@ -394,8 +319,7 @@ extern "C" int avexhip_activity_frames(const float* wav_dev, int64_t wav_samples
                     bands.lo[b], bands.hi[b], kActBins);
     }
     int64_t blocks = 0;
-    rc = activity_recordings_check("activity_frames", rec_host, rec_dev, n_rec, hop, wav_samples, total_frames, &blocks);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(activity_recordings_check("activity_frames", rec_host, rec_dev, n_rec, hop, wav_samples, total_frames, &blocks));
     if (blocks == 0) return AVEXHIP_OK;                          // no recording holds a frame
     AVX_REQUIRE(energy_dev, "activity_frames: null argument");
     hipLaunchKernelGGL(activity_frames_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, wav_dev, rec_dev, n_rec, hop, bands, tables_dev,
@@ -410,10 +334,8 @@ extern "C" int avexhip_activity_floor(const float* energy_dev, int64_t total_fra
     AVX_REQUIRE(floor_dev && nonfinite_dev, "activity_floor: null argument");
     AVX_REQUIRE(((uintptr_t)energy_dev & 3) == 0 && ((uintptr_t)floor_dev & 3) == 0 && ((uintptr_t)nonfinite_dev & 3) == 0,
                 "activity_floor: energy_dev, floor_dev and nonfinite_dev must be 4-byte aligned");
-    int rc = activity_bands_check("activity_floor", n_bands);
-    if (rc != AVEXHIP_OK) return rc;
-    rc = activity_recordings_check("activity_floor", rec_host, rec_dev, n_rec, hop, -1, total_frames, nullptr);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(activity_bands_check("activity_floor", n_bands));
+    AVXH_TRY(activity_recordings_check("activity_floor", rec_host, rec_dev, n_rec, hop, -1, total_frames, nullptr));
     AVX_REQUIRE(energy_dev || total_frames == 0, "activity_floor: null argument");
     hipLaunchKernelGGL(activity_floor_kernel, dim3((unsigned)n_rec, (unsigned)n_bands), dim3(kFloorThreads), 0, (hipStream_t)stream, energy_dev, rec_dev, hop,
                        total_frames, n_bands, floor_dev, nonfinite_dev);
@@ -432,10 +354,8 @@ extern "C" int avexhip_activity_count(const avexhip_window* win_host, const avex
     AVX_REQUIRE(n_win >= 1, "activity_count: n_win=%d", n_win);
     AVX_REQUIRE(!(floor_min != floor_min) && !(ratio != ratio) && floor_min >= 0.f && ratio >= 0.f, "activity_count: floor_min=%g ratio=%g: numbers >= 0 expected (not NaN)",
                 (double)floor_min, (double)ratio);
-    int rc = activity_bands_check("activity_count", n_bands);
-    if (rc != AVEXHIP_OK) return rc;
-    rc = activity_recordings_check("activity_count", rec_host, rec_dev, n_rec, hop, -1, total_frames, nullptr);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(activity_bands_check("activity_count", n_bands));
+    AVXH_TRY(activity_recordings_check("activity_count", rec_host, rec_dev, n_rec, hop, -1, total_frames, nullptr));
     AVX_REQUIRE(energy_dev || total_frames == 0, "activity_count: null argument");
     for (int w = 0; w < n_win; ++w) {
         const avexhip_window& it = win_host[w];
@@ -459,8 +379,7 @@ extern "C" int avexhip_activity_select(const avexhip_window* win_dev, const doub
                     ((uintptr_t)kept_dev & 3) == 0 && ((uintptr_t)count_dev & 3) == 0,
                 "activity_select: win_dev and energy_dev must be 8-byte aligned, the other device arrays 4-byte aligned");
     AVX_REQUIRE(n_win >= 1, "activity_select: n_win=%d", n_win);
-    const int rc = activity_bands_check("activity_select", n_bands);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(activity_bands_check("activity_select", n_bands));
     AVX_REQUIRE(min_active_frames >= 0, "activity_select: min_active_frames=%d", min_active_frames);
     AVX_REQUIRE(mode == AVEXHIP_ACTIVITY_ANY || mode == AVEXHIP_ACTIVITY_ALL, "activity_select: unknown mode %d", mode);
     AVX_REQUIRE(!(thr_energy != thr_energy) && !(thr_peak != thr_peak), "activity_select: a threshold is NaN (-inf turns one off)");

@@ -21,6 +21,7 @@
 // A thread's sequential work is bounded by the reference events its own prediction overlaps (in all at most n_pred + n_ref pairs for
 // ordered input), never by the size of a segment.  Unordered or overlapping predictions cannot leave an array: searches are clamped to
 // [0, n_ref), pairs past the buffer are dropped, and such rows are flagged in errors[].
+#include "block_prims.h"
 #include "common.h"
 
 namespace {
@@ -40,24 +41,19 @@ struct AnWs {
     size_t bytes;
 };
 
-template <typename T> static inline T* an_take(char*& p, size_t n) {
-    T* r = (T*)p;
-    p += (n * sizeof(T) + 15) / 16 * 16;
-    return r;
-}
-
 static inline int64_t an_chunks(int64_t n_pred, int64_t n_ref) { return (n_pred + n_ref + AN_K - 1) / AN_K; }
 
 static AnWs an_carve(void* ws, int64_t n_pred, int64_t n_ref) {
     const size_t P = (size_t)n_pred, cap = (size_t)(n_pred + n_ref), nch = (size_t)an_chunks(n_pred, n_ref);
+    const size_t step = 16;      // bytes: every array starts 16-byte aligned
     AnWs w;
     char* p = (char*)ws;
-    w.j0 = an_take<int32_t>(p, P);
-    w.j1 = an_take<int32_t>(p, P);
-    w.pi = an_take<int32_t>(p, cap);
-    w.pj = an_take<int32_t>(p, cap);
-    w.summ = an_take<unsigned char>(p, nch);
-    w.carry = an_take<unsigned char>(p, nch);
+    w.j0 = take<int32_t>(p, P, step);
+    w.j1 = take<int32_t>(p, P, step);
+    w.pi = take<int32_t>(p, cap, step);
+    w.pj = take<int32_t>(p, cap, step);
+    w.summ = take<unsigned char>(p, nch, step);
+    w.carry = take<unsigned char>(p, nch, step);
     w.bytes = (size_t)(p - (char*)ws);
     return w;
 }
@@ -205,13 +201,15 @@ __global__ __launch_bounds__(AN_K) void an_emit_kernel(AnParams p) {
     }
 }
 
-// f then g
-static __device__ __forceinline__ unsigned an_compose(unsigned f, unsigned g) {
-    unsigned h = 0u;
+// f then g: the operator of the block scans below (associative, not commutative; AN_ID its identity)
+struct AnCompose {
+    __device__ __forceinline__ unsigned operator()(unsigned f, unsigned g) const {
+        unsigned h = 0u;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) h |= ((g >> (2u * ((f >> (2 * s)) & 3u))) & 3u) << (2 * s);
-    return h;
-}
+        for (int s = 0; s < 4; ++s) h |= ((g >> (2u * ((f >> (2 * s)) & 3u))) & 3u) << (2 * s);
+        return h;
+    }
+};
 static __device__ __forceinline__ int an_apply(unsigned f, int s) { return (int)((f >> (2 * s)) & 3u); }
 
 // the function of pair k (identity past the last pair): bit 0 of the state = the prediction is matched, bit 1 = the event is
@@ -234,37 +232,15 @@ static __device__ __forceinline__ int64_t an_total(const AnParams& p) {
     return t < 0 ? 0 : (t > cap ? cap : t);
 }
 
-// the scan of the workgroup's 256 functions in thread order: returns the composition of the threads BELOW this one, *all = of all of them
-static __device__ __forceinline__ unsigned an_block_scan(unsigned f, unsigned* wt, unsigned* all) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned incl = f;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl = an_compose(t, incl);
-    }
-    unsigned excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = AN_ID;
-    if (lane == 63) wt[wave] = incl;
-    __syncthreads();
-    unsigned before = AN_ID, total = AN_ID;
-#pragma unroll
-    for (int w = 0; w < AN_WAVES; ++w) {
-        if (w < wave) before = an_compose(before, wt[w]);
-        total = an_compose(total, wt[w]);
-    }
-    __syncthreads();                                  // wt may be rewritten by the caller's next pass
-    *all = total;
-    return an_compose(before, excl);
-}
-
+// The scans below run the workgroup's 256 functions in thread order (block_scan, block_prims.h): `before` is the composition of the
+// threads BELOW this one, `all` of all of them.
 __global__ __launch_bounds__(AN_K) void an_reduce_kernel(AnParams p) {
     __shared__ unsigned wt[AN_WAVES];
     const int64_t k = (int64_t)blockIdx.x * AN_K + threadIdx.x;
     bool np, nr;
     const unsigned f = an_pair_fn(p, k, an_total(p), np, nr);
-    unsigned all;
-    an_block_scan(f, wt, &all);
+    unsigned before, all;
+    block_scan<AN_WAVES>(f, AN_ID, AnCompose(), wt, &before, &all);
     if (threadIdx.x == 0) p.w.summ[blockIdx.x] = (unsigned char)all;
 }
 
@@ -275,8 +251,8 @@ __global__ __launch_bounds__(AN_K) void an_carry_kernel(AnParams p) {
     for (int base = 0; base < p.nch; base += AN_K) {
         const int k = base + threadIdx.x;
         const unsigned f = k < p.nch ? (unsigned)p.w.summ[k] : AN_ID;
-        unsigned all;
-        const unsigned before = an_block_scan(f, wt, &all);
+        unsigned before, all;
+        block_scan<AN_WAVES>(f, AN_ID, AnCompose(), wt, &before, &all);
         if (k < p.nch) p.w.carry[k] = (unsigned char)an_apply(before, state);
         state = an_apply(all, state);
     }
@@ -288,8 +264,8 @@ __global__ __launch_bounds__(AN_K) void an_apply_kernel(AnParams p) {
     const int64_t total = an_total(p);
     bool np, nr;
     const unsigned f = an_pair_fn(p, k, total, np, nr);
-    unsigned all;
-    const unsigned before = an_block_scan(f, wt, &all);
+    unsigned before, all;
+    block_scan<AN_WAVES>(f, AN_ID, AnCompose(), wt, &before, &all);
     if (k >= total) return;
     const int s = an_apply(before, (int)p.w.carry[blockIdx.x]) & ~((np ? 1 : 0) | (nr ? 2 : 0));
     if (s != 0) return;                               // one of the two is matched already
@@ -323,8 +299,7 @@ static int an_check(const char* what, const avexhip_annot_match_args* a, AnParam
     AVX_REQUIRE(an_shape_ok(a->n_pred, a->n_ref, n_seg), "%s: bad shape (n_pred %lld, n_ref %lld: each >= 1, together below 2^31 - 256)", what, (long long)a->n_pred,
                 (long long)a->n_ref);
     AVX_REQUIRE(a->iou >= AVEXHIP_ANNOT_MIN_IOU && a->iou <= 1.0, "%s: iou=%g outside %g .. 1", what, a->iou, (double)AVEXHIP_ANNOT_MIN_IOU);      // (a NaN fails both)
-    const int rc = an_offsets_check(what, a->seg_offsets_host, n_seg, a->n_ref);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(an_offsets_check(what, a->seg_offsets_host, n_seg, a->n_ref));
     const AnWs w = an_carve(a->workspace, a->n_pred, a->n_ref);
     if (a->workspace_bytes < w.bytes) {
         avexhip_set_error("%s: workspace %zu B < %zu B", what, a->workspace_bytes, w.bytes);
@@ -375,8 +350,7 @@ extern "C" int avexhip_annot_overlap(const int64_t* span_lo_dev, const int64_t* 
     AVX_REQUIRE(n_win >= 1 && n_win <= AN_MAX && n_win <= AN_MAX * 256 / n_classes, "annot_overlap: n_win=%lld with %d classes: more entries than one launch takes",
                 (long long)n_win, n_classes);
     AVX_REQUIRE(n_ref >= 1 && n_ref <= AN_MAX, "annot_overlap: n_ref=%lld outside 1 .. 2^31 - 1", (long long)n_ref);
-    const int rc = an_offsets_check("annot_overlap", seg_offsets_host, (int64_t)n_rec * n_classes, n_ref);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(an_offsets_check("annot_overlap", seg_offsets_host, (int64_t)n_rec * n_classes, n_ref));
     for (int64_t w = 0; w < n_win; ++w)
         AVX_REQUIRE(win_rec_host[w] >= 0 && win_rec_host[w] < n_rec, "annot_overlap: window %lld: recording %d outside the %d", (long long)w, win_rec_host[w], n_rec);
     const int64_t blocks = (n_win * n_classes + 255) / 256;
@@ -388,8 +362,7 @@ extern "C" int avexhip_annot_overlap(const int64_t* span_lo_dev, const int64_t* 
 
 extern "C" int avexhip_annot_count(const avexhip_annot_match_args* args, void* stream) {
     AnParams p;
-    const int rc = an_check("annot_count", args, &p);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(an_check("annot_count", args, &p));
     an_count_kernel<<<dim3((unsigned)((p.P + AN_K - 1) / AN_K)), dim3(AN_K), 0, (hipStream_t)stream>>>(p);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
@@ -401,8 +374,7 @@ extern "C" int avexhip_annot_match(const avexhip_annot_match_args* args, const i
     AVX_REQUIRE(((uintptr_t)pair_offsets_dev & 7) == 0 && (((uintptr_t)match_of_pred_dev | (uintptr_t)match_of_ref_dev) & 3) == 0,
                 "annot_match: pair_offsets_dev must be 8-byte aligned, the match arrays 4-byte aligned");
     AnParams p;
-    const int rc = an_check("annot_match", args, &p);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(an_check("annot_match", args, &p));
     p.pair_off = pair_offsets_dev;
     p.mop = match_of_pred_dev;
     p.mor = match_of_ref_dev;

@@ -395,8 +395,7 @@ int bias_tab_for(avexhip_beats* h, int T, hipStream_t s, float* fallback, float*
         return AVEXHIP_OK;
     }
     AVX_REQUIRE(fallback, "beats_forward: no room for the relative position bias table (T=%d)", T);
-    const int rc = avx::bias_toeplitz(h->d_rel_table, h->d_bucket_lut, h->lut_maxd, T, h->core.H, fallback, s);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(avx::bias_toeplitz(h->d_rel_table, h->d_bucket_lut, h->lut_maxd, T, h->core.H, fallback, s));
     *out = fallback;
     return AVEXHIP_OK;
 }

@@ -815,8 +815,7 @@ extern "C" int avexhip_clustering_trials(int k) { return k >= 1 ? trials_of(k) :
 
 extern "C" int avexhip_clustering_prepare(const avexhip_clustering_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "clustering_prepare", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "clustering_prepare", &w));
     AVX_REQUIRE(a->x && a->ld_x >= a->d, "clustering_prepare: embeddings missing");
     hipStream_t s = (hipStream_t)stream;
     const int dp = (int)dpad_of(a->d);
@@ -838,12 +837,10 @@ extern "C" int avexhip_clustering_prepare(const avexhip_clustering_args* a, void
 
 extern "C" int avexhip_clustering_seed(const avexhip_clustering_args* a, const int32_t* first_dev, const double* u_dev, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "clustering_seed", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "clustering_seed", &w));
     AVX_REQUIRE(first_dev && (u_dev || a->k == 1), "clustering_seed: draws missing");
     hipStream_t s = (hipStream_t)stream;
-    const int rs = reset_state(a, w, s);
-    if (rs != AVEXHIP_OK) return rs;
+    AVXH_TRY(reset_state(a, w, s));
     const int dp = (int)dpad_of(a->d), kp = kpad_of(a->k), R = a->n_init, T = trials_of(a->k), n = a->n;
     const int nblk = (n + 255) / 256;
     int32_t *cand = w.cand, *next = w.cand2;
@@ -866,12 +863,10 @@ extern "C" int avexhip_clustering_seed(const avexhip_clustering_args* a, const i
 
 extern "C" int avexhip_clustering_set_init(const avexhip_clustering_args* a, const float* init_dev, int64_t ld_init, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "clustering_set_init", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "clustering_set_init", &w));
     AVX_REQUIRE(init_dev && ld_init >= a->d && a->n_init == 1, "clustering_set_init: one run from [k, d] centres (n_init %d)", a->n_init);
     hipStream_t s = (hipStream_t)stream;
-    const int rs = reset_state(a, w, s);
-    if (rs != AVEXHIP_OK) return rs;
+    AVXH_TRY(reset_state(a, w, s));
     const int dp = (int)dpad_of(a->d);
     const int64_t total = (int64_t)a->k * dp;
     clus_set_init_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(init_dev, ld_init, a->k, a->d, dp, w.mean, w.centres);
@@ -881,8 +876,7 @@ extern "C" int avexhip_clustering_set_init(const avexhip_clustering_args* a, con
 
 extern "C" int avexhip_clustering_iterate(const avexhip_clustering_args* a, int n_iters, int stages, int32_t* unfinished_out_dev, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "clustering_iterate", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "clustering_iterate", &w));
     AVX_REQUIRE(n_iters >= 1 && a->max_iter >= 1, "clustering_iterate: n_iters %d, max_iter %d", n_iters, a->max_iter);
     hipStream_t s = (hipStream_t)stream;
     const int dp = (int)dpad_of(a->d), kp = kpad_of(a->k), R = a->n_init, n = a->n, k = a->k;
@@ -915,8 +909,7 @@ extern "C" int avexhip_clustering_iterate(const avexhip_clustering_args* a, int 
 
 extern "C" int avexhip_clustering_finish(const avexhip_clustering_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "clustering_finish", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "clustering_finish", &w));
     AVX_REQUIRE(a->labels_out && a->centers_out && a->inertias_out && a->n_iters_out && a->seeds_out && a->summary_out, "clustering_finish: null output");
     hipStream_t s = (hipStream_t)stream;
     const int dp = (int)dpad_of(a->d), kp = kpad_of(a->k), R = a->n_init, n = a->n, k = a->k;

@@ -288,6 +288,7 @@ static __device__ __forceinline__ float wave_sum(float v) {
 }
 // max(a, x) that keeps a NaN from either side, like torch.max over a dimension (fmaxf returns its non-NaN operand): the pooled maxima
 static __device__ __forceinline__ float nan_max(float a, float x) { return (x > a || x != x) ? x : a; }
+static __device__ __forceinline__ bool non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }      // NaN or Inf: exponent all ones
 static __device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 x) {
     return (f32x4){nan_max(a[0], x[0]), nan_max(a[1], x[1]), nan_max(a[2], x[2]), nan_max(a[3], x[3])};
 }
@@ -329,7 +330,17 @@ void avexhip_set_error(const char* fmt, ...);
         }                                      \
     } while (0)
 
-#define AVX_LAUNCH_CHECK()                                                                   \
+// return the callee's AVEXHIP_* code if it is not OK (its message is already set)
+#define AVXH_TRY(x) do { const int rc_ = (x); if (rc_ != AVEXHIP_OK) return rc_; } while (0)
+
+// the next `count` elements of a workspace carved in steps of `step` bytes (a power of two)
+template <typename T> static inline T* take(char*& p, size_t count, size_t step = 256) {
+    T* r = (T*)p;
+    p += (count * sizeof(T) + step - 1) & ~(step - 1);
+    return r;
+}
+
+#define AVX_LAUNCH_CHECK()                                                             \
     do {                                                                                     \
         hipError_t _e = hipGetLastError();                                                   \
         if (_e != hipSuccess) {                                                              \
@@ -348,7 +359,7 @@ namespace avx {
 //   avx::device_cu_count(&n)       multiProcessorCount of the current device, cached per device
 int ensure_max_dynamic_lds(const void* func, int bytes);
 int device_cu_count(int* n_cu);
-#define AVX_ENSURE_LDS(kernel, bytes) do { const int rc_ = avx::ensure_max_dynamic_lds((const void*)(kernel), (int)(bytes)); if (rc_ != AVEXHIP_OK) return rc_; } while (0)
+#define AVX_ENSURE_LDS(kernel, bytes) AVXH_TRY(avx::ensure_max_dynamic_lds((const void*)(kernel), (int)(bytes)))
 
 int gemm(const GemmArgs& a, int dtype, hipStream_t s);
 // fp32 NHWC rows [B * HW, ld] -> NCHW [B, C, HW], optionally undoing a folded BatchNorm: (x - shift[c]) / scale[c] (effnet.hip)

@@ -36,6 +36,7 @@
 // Determinism.  Every atomic is an integer add, min or max on global memory: order-free.  Counts, labels and keys are integers, so the
 // result does not depend on the segments, the blocks, or the run.  No float atomics.
 // Limits: n <= 2^31 - 1 rows, dpad % 32 == 0, a block of at most 2^22 rows.
+#include "block_prims.h"
 #include "f32_tile.h"
 
 namespace {
@@ -253,14 +254,10 @@ __global__ __launch_bounds__(256) void dens_root_count_kernel(int64_t n, const i
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (b0 + e < n && label[b0 + e] == b0 + e) ++c;
-    __shared__ int red[256];
-    red[threadIdx.x] = c;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block[blockIdx.x] = red[0];
+    __shared__ int wt[4];
+    int before, all;
+    block_scan<4>(c, 0, BlockSum(), wt, &before, &all);
+    if (threadIdx.x == 0) block[blockIdx.x] = all;
 }
 
 // one workgroup: block[b] -> the number of roots in the blocks before b; flags[1] = all of them
@@ -293,7 +290,7 @@ __global__ __launch_bounds__(256) void dens_block_scan_kernel(int64_t n_blocks, 
 
 __global__ __launch_bounds__(256) void dens_number_kernel(int64_t n, const int32_t* __restrict__ label, const int32_t* __restrict__ block,
                                                           int32_t* __restrict__ cid) {
-    __shared__ int sc[256];
+    __shared__ int wt[4];
     const int tid = threadIdx.x;
     const int64_t b0 = (int64_t)blockIdx.x * DN_SCAN_ROWS + 4 * tid;
     bool root[4];
@@ -303,15 +300,9 @@ __global__ __launch_bounds__(256) void dens_number_kernel(int64_t n, const int32
         root[e] = b0 + e < n && label[b0 + e] == b0 + e;
         c += root[e] ? 1 : 0;
     }
-    sc[tid] = c;
-    __syncthreads();
-    for (int st = 1; st < 256; st <<= 1) {      // inclusive scan over the 256 threads
-        const int v = tid >= st ? sc[tid - st] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    int run = block[blockIdx.x] + sc[tid] - c;
+    int before, all;
+    block_scan<4>(c, 0, BlockSum(), wt, &before, &all);      // the roots of the threads below this one
+    int run = block[blockIdx.x] + before;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (b0 + e < n) {
@@ -446,8 +437,7 @@ extern "C" int avexhip_density_max_block(void) { return DN_MAX_BLOCK; }
 
 extern "C" int avexhip_density_begin(const avexhip_density_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "density_begin", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_begin", &w));
     hipStream_t s = (hipStream_t)stream;
     AVX_HIP_CHECK(hipMemsetAsync(w.count, 0, (size_t)a->n * 4, s));
     AVX_HIP_CHECK(hipMemsetAsync(w.flags, 0, 16, s));
@@ -456,9 +446,8 @@ extern "C" int avexhip_density_begin(const avexhip_density_args* a, void* stream
 
 extern "C" int avexhip_density_norms(const avexhip_density_args* a, void* stream) {
     Workspace w;
-    int rc = check_args(a, "density_norms", &w);
-    if (rc != AVEXHIP_OK) return rc;
-    if ((rc = check_rows(a, "density_norms")) != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_norms", &w));
+    AVXH_TRY(check_rows(a, "density_norms"));
     AVX_ENSURE_LDS(dens_diag_kernel, FT_LDS_BYTES);
     dens_diag_kernel<<<dim3((a->n_rows + FT_BM - 1) / FT_BM), dim3(256), FT_LDS_BYTES, (hipStream_t)stream>>>(a->rows, a->n_rows, a->dpad, w.nrm + a->row0);
     AVX_LAUNCH_CHECK();
@@ -467,17 +456,15 @@ extern "C" int avexhip_density_norms(const avexhip_density_args* a, void* stream
 
 extern "C" int avexhip_density_count(const avexhip_density_args* a, void* stream) {
     Workspace w;
-    int rc = check_args(a, "density_count", &w);
-    if (rc != AVEXHIP_OK) return rc;
-    if ((rc = check_rows(a, "density_count")) != AVEXHIP_OK) return rc;
-    if ((rc = check_cols(a, "density_count")) != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_count", &w));
+    AVXH_TRY(check_rows(a, "density_count"));
+    AVXH_TRY(check_cols(a, "density_count"));
     return walk<false>(a, w, (hipStream_t)stream);
 }
 
 extern "C" int avexhip_density_core(const avexhip_density_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "density_core", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_core", &w));
     AVX_REQUIRE(a->min_samples >= 1, "density_core: min_samples %d < 1", a->min_samples);
     dens_core_kernel<<<dim3(blocks256(a->n)), dim3(256), 0, (hipStream_t)stream>>>(a->n, w.nrm, w.count, a->min_samples, w.label, w.flags);
     AVX_LAUNCH_CHECK();
@@ -486,8 +473,7 @@ extern "C" int avexhip_density_core(const avexhip_density_args* a, void* stream)
 
 extern "C" int avexhip_density_round_begin(const avexhip_density_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "density_round_begin", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_round_begin", &w));
     dens_begin_kernel<<<dim3(blocks256(a->n)), dim3(256), 0, (hipStream_t)stream>>>(a->n, w.label, w.next);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
@@ -495,17 +481,15 @@ extern "C" int avexhip_density_round_begin(const avexhip_density_args* a, void* 
 
 extern "C" int avexhip_density_hook(const avexhip_density_args* a, void* stream) {
     Workspace w;
-    int rc = check_args(a, "density_hook", &w);
-    if (rc != AVEXHIP_OK) return rc;
-    if ((rc = check_rows(a, "density_hook")) != AVEXHIP_OK) return rc;
-    if ((rc = check_cols(a, "density_hook")) != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_hook", &w));
+    AVXH_TRY(check_rows(a, "density_hook"));
+    AVXH_TRY(check_cols(a, "density_hook"));
     return walk<true>(a, w, (hipStream_t)stream);
 }
 
 extern "C" int avexhip_density_round_end(const avexhip_density_args* a, int32_t* changed_out_dev, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "density_round_end", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_round_end", &w));
     AVX_REQUIRE(changed_out_dev, "density_round_end: null output");
     hipStream_t s = (hipStream_t)stream;
     AVX_HIP_CHECK(hipMemsetAsync(changed_out_dev, 0, 4, s));
@@ -519,8 +503,7 @@ extern "C" int avexhip_density_round_end(const avexhip_density_args* a, int32_t*
 extern "C" int avexhip_density_labels(const avexhip_density_args* a, int32_t* labels_out_dev, uint8_t* core_out_dev, int32_t* n_neighbors_out_dev,
                                       int32_t* summary_out_dev, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "density_labels", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_labels", &w));
     AVX_REQUIRE(labels_out_dev && core_out_dev && n_neighbors_out_dev && summary_out_dev, "density_labels: null output");
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_blocks = (a->n + DN_SCAN_ROWS - 1) / DN_SCAN_ROWS;
@@ -539,8 +522,7 @@ extern "C" int avexhip_density_labels(const avexhip_density_args* a, int32_t* la
 extern "C" int avexhip_density_summary(const avexhip_density_args* a, const int32_t* labels_dev, int n_clusters, int32_t* sizes_out_dev,
                                        int32_t* exemplar_out_dev, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "density_summary", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "density_summary", &w));
     AVX_REQUIRE(labels_dev && sizes_out_dev && exemplar_out_dev, "density_summary: null argument");
     AVX_REQUIRE(n_clusters >= 1 && n_clusters <= a->n, "density_summary: n_clusters %d outside [1, n]", n_clusters);
     hipStream_t s = (hipStream_t)stream;

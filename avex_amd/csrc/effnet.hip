@@ -1008,8 +1008,7 @@ int mbconv_front(const void* in, int B, int H, int W, int ld_in, int kin, const 
                     sizeof(float) * (size_t)B * tiles * cp_exp, part_bytes);
         a.part = part;
     }
-    const int rc = dtype == AVEXHIP_BF16 ? mb_dispatch<__bf16>(a, B, k, stride, kin, nullptr, s) : mb_dispatch<_Float16>(a, B, k, stride, kin, nullptr, s);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(dtype == AVEXHIP_BF16 ? mb_dispatch<__bf16>(a, B, k, stride, kin, nullptr, s) : mb_dispatch<_Float16>(a, B, k, stride, kin, nullptr, s));
     if (pool) {
         hipLaunchKernelGGL(pool_sum_kernel, dim3((cp_exp + 255) / 256, B), dim3(256), 0, s, part, (int)tiles, cp_exp, pool);
         AVX_LAUNCH_CHECK();

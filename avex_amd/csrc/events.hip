@@ -31,6 +31,7 @@
 //   ev_fill_kernel       rows past min(total, capacity): -1, -inf, NaN.
 #include <math.h>
 
+#include "block_prims.h"
 #include "common.h"
 
 namespace {
@@ -70,27 +71,22 @@ struct EvWs {
     size_t bytes;
 };
 
-template <typename T> static inline T* ev_take(char*& p, size_t n) {
-    T* r = (T*)p;
-    p += (n * sizeof(T) + 15) / 16 * 16;
-    return r;
-}
-
 static EvWs ev_carve(void* ws, int64_t n, int64_t c, int64_t r) {
     const size_t nch = (size_t)((n + EV_K - 1) / EV_K), rows = nch * EV_ROWS, C = (size_t)c;
+    const size_t step = 16;      // bytes: every array starts 16-byte aligned
     EvWs w;
     char* p = (char*)ws;
-    w.S = ev_take<u64>(p, C * rows);
-    w.Z = ev_take<u64>(p, C * rows);
-    w.F = ev_take<u64>(p, C * rows);
-    w.E = ev_take<u64>(p, C * rows);
-    w.pch = ev_take<int>(p, C * (nch + 1));
-    w.V = ev_take<long long>(p, (size_t)(r + 1) * C);
-    w.T = ev_take<long long>(p, (size_t)(r + 1));
-    w.pin = ev_take<EvPart>(p, C * nch);
-    w.pout = ev_take<EvPart>(p, C * nch);
-    w.summ = ev_take<unsigned char>(p, C * nch);
-    w.carry = ev_take<unsigned char>(p, C * nch);
+    w.S = take<u64>(p, C * rows, step);
+    w.Z = take<u64>(p, C * rows, step);
+    w.F = take<u64>(p, C * rows, step);
+    w.E = take<u64>(p, C * rows, step);
+    w.pch = take<int>(p, C * (nch + 1), step);
+    w.V = take<long long>(p, (size_t)(r + 1) * C, step);
+    w.T = take<long long>(p, (size_t)(r + 1), step);
+    w.pin = take<EvPart>(p, C * nch, step);
+    w.pout = take<EvPart>(p, C * nch, step);
+    w.summ = take<unsigned char>(p, C * nch, step);
+    w.carry = take<unsigned char>(p, C * nch, step);
     w.bytes = (size_t)(p - (char*)ws);
     return w;
 }
@@ -326,28 +322,6 @@ __global__ __launch_bounds__(EV_K) void ev_runs_kernel(EvParams p) {
     if (tid == 0) p.w.pch[(size_t)c * (p.nch + 1) + chunk] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
 }
 
-// inclusive scan over the 256 threads' values; returns this thread's inclusive value, *total the sum of all (wt: 4 shared words)
-template <typename T> static __device__ __forceinline__ T ev_block_scan(T v, T* wt, T* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wt[wave] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < EV_ROWS; ++w) {
-        before += w < wave ? wt[w] : (T)0;
-        all += wt[w];
-    }
-    __syncthreads();                                  // wt may be rewritten by the caller's next pass
-    *total = all;
-    return before + incl;
-}
-
 // One workgroup per class: starts per chunk -> starts in the chunks before; entry [chunks] = the class's total.
 __global__ __launch_bounds__(EV_K) void ev_count_kernel(EvParams p) {
     __shared__ int wt[EV_ROWS];
@@ -356,9 +330,9 @@ __global__ __launch_bounds__(EV_K) void ev_count_kernel(EvParams p) {
     for (int base = 0; base < p.nch; base += EV_K) {
         const int k = base + threadIdx.x;
         const int v = k < p.nch ? cnt[k] : 0;
-        int all;
-        const int incl = ev_block_scan<int>(v, wt, &all);
-        if (k < p.nch) cnt[k] = carry + incl - v;
+        int excl, all;
+        const int incl = block_scan<EV_ROWS>(v, 0, BlockSum(), wt, &excl, &all);
+        if (k < p.nch) cnt[k] = carry + incl - v;      // (incl - v, not excl: a subtraction where excl costs one more shuffle)
         carry += all;
     }
     if (threadIdx.x == 0) cnt[p.nch] = carry;
@@ -391,8 +365,8 @@ __global__ __launch_bounds__(EV_K) void ev_bounds_kernel(EvParams p) {
     for (int base = 0; base < p.C; base += EV_K) {
         const int c = base + threadIdx.x;
         const long long g = c < p.C ? (long long)ev_starts_below(p, c, x) : 0ll;
-        long long all;
-        const long long incl = ev_block_scan<long long>(g, wt, &all);
+        long long excl, all;
+        const long long incl = block_scan<EV_ROWS>(g, 0ll, BlockSum(), wt, &excl, &all);
         if (c < p.C) p.w.V[(size_t)r * p.C + c] = carry + incl - g;
         carry += all;
     }
@@ -626,8 +600,7 @@ extern "C" size_t avexhip_events_workspace_bytes(int64_t n_windows, int n_classe
 
 extern "C" int avexhip_events_scan(const avexhip_events_args* a, void* stream) {
     EvParams p;
-    const int rc = ev_check("events_scan", a, &p);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(ev_check("events_scan", a, &p));
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(EV_K);
     ev_classify_kernel<<<dim3((unsigned)p.nch * (unsigned)p.ntile), block, 0, s>>>(p);
@@ -648,8 +621,7 @@ extern "C" int avexhip_events_emit(const avexhip_events_args* a, const avexhip_e
     AVX_REQUIRE(r->capacity >= 0 && r->capacity <= 0x7fffffffll * EV_K, "events_emit: capacity %lld outside 0 .. 2^39", (long long)r->capacity);
     AVX_REQUIRE(r->sequence && r->class_id && r->first && r->last && r->peak && r->peak_window && r->mean, "events_emit: null output");
     EvParams p;
-    const int rc = ev_check("events_emit", a, &p);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(ev_check("events_emit", a, &p));
     p.cap = r->capacity;
     p.o_seq = r->sequence;
     p.o_cls = r->class_id;

@@ -15,13 +15,8 @@ constexpr int FT_LDS_BYTES = 4 * FT_TILE_BYTES;          // dynamic LDS of a lau
 
 static inline int64_t dpad_of(int d) { return ((int64_t)d + FT_BK - 1) / FT_BK * FT_BK; }
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the next `count` elements of a workspace carved in 256-byte steps
-template <typename T> static T* take(char*& p, size_t count) {
-    T* r = (T*)p;
-    p += align256(count * sizeof(T));
-    return r;
-}
+// floats per row of a stored similarity matrix over n columns (retrieval.hip, search.hip)
+static inline int64_t ldsim_of(int64_t n) { return (n + 63) / 64 * 64; }
 
 // order-preserving map of a float onto unsigned integers (-0 is folded onto +0 first by the caller)
 static __device__ __forceinline__ unsigned mono32(float v) {

@@ -7,11 +7,9 @@
 //
 // One wave64 handles a PAIR of frames packed as one complex sequence z[n] = a[n] + i b[n]
 // (n < 512, zero beyond the 400-sample window), so a single 512-point complex FFT yields both real
-// spectra.  512 = 8*8*8: three register-resident radix-8 passes with each lane holding 8 points,
-// exchanged through a per-wave LDS buffer (row stride 72 complex to stay bank-conflict free):
-//   pass 1  lane n2 holds x[64 n1 + n2], n1 = 0..7 (exactly how frames load coalesced from HBM)
-//   pass 2  lane (k1, m2) takes Y[k1][8 m1 + m2], m1 = 0..7
-//   pass 3  lane l = k1 + 8 j1 takes U[k1][j1][m2], m2 = 0..7 and ends with X[l + 64 j2]
+// spectra.  The transform is fft512.h's, shared with activity.hip: three register-resident radix-8
+// passes, lane n2 holding x[64 n1 + n2] (exactly how frames load coalesced from HBM), exchanged
+// through a per-wave LDS buffer;
 // then |A|^2, |B|^2 by conjugate symmetry, sparse triangular mel (<= ~10 taps per bin for 128 bins,
 // CSR built on the host from the reference's dense [257, n_mels] matrix), log, affine.
 #include <math.h>
@@ -19,45 +17,22 @@
 #include <vector>
 
 #include "common.h"
+#include "fft512.h"
 
 namespace {
 
-__device__ __forceinline__ float2 operator+(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 operator-(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // a * (-i)
-
-// in-place 8-point DFT, natural order in and out: x[k] <- sum_n x[n] exp(-2 pi i n k / 8)
-__device__ __forceinline__ void dft8(float2 (&x)[8]) {
-    const float c = 0.70710678118654752440f;
-    const float2 a0 = x[0] + x[4], a1 = x[0] - x[4], a2 = x[2] + x[6], a3 = mul_mi(x[2] - x[6]);
-    const float2 b0 = x[1] + x[5], b1 = x[1] - x[5], b2 = x[3] + x[7], b3 = mul_mi(x[3] - x[7]);
-    const float2 e0 = a0 + a2, e2 = a0 - a2, e1 = a1 + a3, e3 = a1 - a3;
-    const float2 o0 = b0 + b2, o2 = b0 - b2, o1 = b1 + b3, o3 = b1 - b3;
-    const float2 t1 = make_float2(c * (o1.x + o1.y), c * (o1.y - o1.x));   // o1 * W8^1
-    const float2 t2 = mul_mi(o2);                                          // o2 * W8^2
-    const float2 t3 = make_float2(c * (o3.y - o3.x), -c * (o3.x + o3.y));  // o3 * W8^3
-    x[0] = e0 + o0; x[4] = e0 - o0;
-    x[1] = e1 + t1; x[5] = e1 - t1;
-    x[2] = e2 + t2; x[6] = e2 - t2;
-    x[3] = e3 + t3; x[7] = e3 - t3;
-}
-
-constexpr int ZROW = 72;  // complex elements per LDS row (64 + 8 pad)
-// Every exchange buffer below is private to one wave, and a wave's LDS operations execute in order: the passes need no
-// workgroup barrier, only the compiler kept from moving LDS accesses across the exchange points.
-#define AVX_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-
 // Diagnostic build only (scripts/debug/conc_probe3.hip compiles this file with -DAVX_FBANK_TAPS): every wave dumps its
-// registers after each stage so a wrong result can be traced to the first stage that differs.  Never defined in the library.
+// registers after each stage of the transform so a wrong result can be traced to the first stage that differs.  Never defined in the library.
 #ifdef AVX_FBANK_TAPS
 __device__ float2* g_fbank_taps;
-#define AVX_TAP(stage) do { float2* t_ = g_fbank_taps + ((((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8 + (stage)) * 64 + lane) * 8; \
-                            _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) t_[q_] = x[q_]; } while (0)
-#else
-#define AVX_TAP(stage) do { } while (0)
+struct FbankTap {
+    int wave, lane;
+    __device__ __forceinline__ void operator()(int stage, const float2 (&x)[8]) const {
+        float2* t = g_fbank_taps + ((((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8 + stage) * 64 + lane) * 8;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = x[q];
+    }
+};
 #endif
 
 template <typename T>
@@ -136,59 +111,12 @@ __global__ __launch_bounds__(256) void fbank_kernel(avx::FbankDev fb, const floa
         live[fr] = __any(nz);
     }
 
-    // ---- 512-point complex FFT: three radix-8 passes ------------------------------------------
-    AVX_TAP(0);
+    // ---- 512-point complex FFT (fft512.h): Z[k] at z[k] ---------------------------------------
 #ifdef AVX_FBANK_TAPS
-    {   // the first dft8 spelled out with a tap after its first level (tap slot 7 = a0..a3, b0..b3; slot 1 = result)
-        const float c = 0.70710678118654752440f;
-        float2 y[8];
-        y[0] = x[0] + x[4]; y[1] = x[0] - x[4]; y[2] = x[2] + x[6]; y[3] = mul_mi(x[2] - x[6]);
-        y[4] = x[1] + x[5]; y[5] = x[1] - x[5]; y[6] = x[3] + x[7]; y[7] = mul_mi(x[3] - x[7]);
-        { float2* t_ = g_fbank_taps + ((((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8 + 7) * 64 + lane) * 8;
-          _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) t_[q_] = y[q_]; }
-        const float2 e0 = y[0] + y[2], e2 = y[0] - y[2], e1 = y[1] + y[3], e3 = y[1] - y[3];
-        const float2 o0 = y[4] + y[6], o2 = y[4] - y[6], o1 = y[5] + y[7], o3 = y[5] - y[7];
-        const float2 t1 = make_float2(c * (o1.x + o1.y), c * (o1.y - o1.x));
-        const float2 t2 = mul_mi(o2);
-        const float2 t3 = make_float2(c * (o3.y - o3.x), -c * (o3.x + o3.y));
-        x[0] = e0 + o0; x[4] = e0 - o0; x[1] = e1 + t1; x[5] = e1 - t1; x[2] = e2 + t2; x[6] = e2 - t2; x[3] = e3 + t3; x[7] = e3 - t3;
-    }
+    fft512_wave(x, z, tw, lane, FbankTap{wave, lane});
 #else
-    dft8(x);
+    fft512_wave(x, z, tw, lane);
 #endif
-    AVX_TAP(1);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; ++k1) x[k1] = cmul(x[k1], tw[lane * k1]);
-    AVX_TAP(2);
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1) z[k1 * ZROW + lane] = x[k1];
-    AVX_WAVE_SYNC();
-    {
-        const int k1 = lane >> 3, m2 = lane & 7;
-#pragma unroll
-        for (int m1 = 0; m1 < 8; ++m1) x[m1] = z[k1 * ZROW + 8 * m1 + m2];
-        AVX_TAP(3);
-        dft8(x);
-#pragma unroll
-        for (int j1 = 1; j1 < 8; ++j1) x[j1] = cmul(x[j1], tw[8 * m2 * j1]);
-        AVX_TAP(4);
-        AVX_WAVE_SYNC();
-#pragma unroll
-        for (int j1 = 0; j1 < 8; ++j1) z[k1 * ZROW + j1 * 8 + m2] = x[j1];
-    }
-    AVX_WAVE_SYNC();
-    {
-        const int k1 = lane & 7, j1 = lane >> 3;
-#pragma unroll
-        for (int m2 = 0; m2 < 8; ++m2) x[m2] = z[k1 * ZROW + j1 * 8 + m2];
-        AVX_TAP(5);
-        dft8(x);
-        AVX_TAP(6);
-        AVX_WAVE_SYNC();
-#pragma unroll
-        for (int j2 = 0; j2 < 8; ++j2) z[lane + 64 * j2] = x[j2];  // natural order Z[k]
-    }
-    AVX_WAVE_SYNC();
 
     // ---- split the two real spectra, power (beats.py:154-155) ----------------------------------
 #pragma unroll

@@ -21,9 +21,6 @@
 
 #include "common.h"
 
-// return the first AVEXHIP_* code that is not OK (its message is already set)
-#define AVXH_TRY(x) do { const int rc_ = (x); if (rc_ != AVEXHIP_OK) return rc_; } while (0)
-
 namespace avxh {
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

@@ -491,8 +491,7 @@ extern "C" int avexhip_ingest_batch(const void* raw_dev, size_t raw_bytes, const
     AVX_REQUIRE(((uintptr_t)raw_dev & 7) == 0 && ((uintptr_t)items_dev & 7) == 0 && ((uintptr_t)workspace_dev & 15) == 0,
                 "ingest_batch: raw_dev / items_dev must be 8-byte aligned, workspace_dev 16-byte aligned");
     IngestLayout L;
-    const int rc = ingest_layout(items_host, B, plans, n_plans, T_out, raw_bytes, true, &L);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(ingest_layout(items_host, B, plans, n_plans, T_out, raw_bytes, true, &L));
     if (wav_stride <= 0) wav_stride = T_out;
     AVX_REQUIRE(wav_stride >= T_out, "ingest_batch: wav_stride %lld < T_out %lld", (long long)wav_stride, (long long)T_out);
     if (workspace_bytes < L.total_bytes) {

@@ -20,8 +20,6 @@ constexpr int RANK_MAX_K = 32;
 constexpr int RANK_MAX_CAP = 16384;                // keys per sorted chunk (64 KiB of LDS)
 constexpr int RETR_MAX_DB = 1 << 19;               // relevance bits of one row: 64 KiB of LDS
 
-static inline int64_t ldsim_of(int64_t n_db) { return (n_db + 63) / 64 * 64; }
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // rows / max(||row||_2, 1e-12): f32_prepare_rows (f32_tile.h), which search.hip runs too
 __global__ __launch_bounds__(256) void retr_normalize_kernel(const float* __restrict__ x, int64_t ldx, int n, int d, int dpad, float* __restrict__ out) {

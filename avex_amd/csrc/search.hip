@@ -25,8 +25,6 @@ constexpr int SRCH_THREADS = 256;
 constexpr int SRCH_MAX_K = 1024;
 constexpr int64_t SRCH_MAX_ROWS = 0x7fffffffll;      // global rows are the low 32 key bits, inverted
 
-static inline int64_t ldsim_of(int64_t n) { return (n + 63) / 64 * 64; }
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // f32_prepare_rows and f32_tile_store_product (f32_tile.h) are the bodies of retr_normalize_kernel and retr_sim_kernel too
 __global__ __launch_bounds__(256) void srch_prepare_kernel(const float* __restrict__ x, int64_t ldx, int n, int d, int dpad, int normalise,

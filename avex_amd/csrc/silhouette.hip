@@ -287,8 +287,7 @@ extern "C" int avexhip_silhouette_max_n(void) { return SIL_MAX_N; }
 
 extern "C" int avexhip_silhouette_prepare(const avexhip_silhouette_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "silhouette_prepare", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "silhouette_prepare", &w));
     AVX_REQUIRE(a->x && a->ld_x >= a->d, "silhouette_prepare: rows missing");
     hipStream_t s = (hipStream_t)stream;
     const int dp = (int)dpad_of(a->d);
@@ -307,8 +306,7 @@ extern "C" int avexhip_silhouette_prepare(const avexhip_silhouette_args* a, void
 
 extern "C" int avexhip_silhouette_batch(const avexhip_silhouette_args* a, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "silhouette_batch", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "silhouette_batch", &w));
     AVX_REQUIRE(a->samples_out, "silhouette_batch: null output");
     AVX_REQUIRE(a->row0 >= 0 && a->nb >= 1 && a->nb <= a->batch && (int64_t)a->row0 + a->nb <= a->n_slots, "silhouette_batch: slots [%d, +%d) outside [0, %d) or above batch %d",
                 a->row0, a->nb, a->n_slots, a->batch);
@@ -336,8 +334,7 @@ extern "C" int avexhip_silhouette_batch(const avexhip_silhouette_args* a, void* 
 
 extern "C" int avexhip_silhouette_finalize(const avexhip_silhouette_args* a, double* summary_out_dev, void* stream) {
     Workspace w;
-    const int rc = check_args(a, "silhouette_finalize", &w);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(check_args(a, "silhouette_finalize", &w));
     AVX_REQUIRE(a->samples_out && summary_out_dev, "silhouette_finalize: null output");
     sil_mean_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(a->samples_out, a->n, w.nonfinite, summary_out_dev);
     AVX_LAUNCH_CHECK();

@@ -12,6 +12,7 @@
 // Every read is at base + start + j with j < valid, and the entry points refuse a table for which that leaves the recording.
 #include <math.h>
 
+#include "block_prims.h"
 #include "common.h"
 
 namespace {
@@ -19,8 +20,6 @@ namespace {
 constexpr int kWinThreads = 256;
 constexpr int kWinStep = kWinThreads * 4;        // samples one pass of a workgroup covers: thread t holds samples 4 t .. 4 t + 3 of it
 constexpr int kSelectThreads = 1024;
-
-__device__ __forceinline__ bool win_non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }      // exponent all ones
 
 // One workgroup per window.  Sample j of the window belongs to thread (j / 4) % 256, slot j % 4, pass j / 1024; a slot adds its squares
 // in pass order, a thread adds its slots as (0 + 1) + (2 + 3), a wave its lanes by a butterfly, thread 0 the waves as (0 + 1) + (2 + 3).
@@ -46,7 +45,7 @@ __global__ __launch_bounds__(kWinThreads) void window_stats_kernel(const float* 
         for (int e = 0; e < 4; ++e) {
             acc[e] += (double)v[e] * (double)v[e];               // the product of two fp32 values is exact in fp64
             mx = __builtin_fmaxf(mx, __builtin_fabsf(v[e]));
-            bad |= win_non_finite(v[e]);
+            bad |= non_finite(v[e]);
         }
     };
     if (wide) {
@@ -86,37 +85,16 @@ __global__ __launch_bounds__(kWinThreads) void window_stats_kernel(const float* 
     }
 }
 
-// One workgroup walks the table 1024 windows at a time: ballot + popcount inside a wave, the sixteen wave totals through LDS, the count of
-// the passes before in `carry`.  A kept window's position is the number of kept windows in front of it, so the list is in increasing
-// order whatever the timing.  The table is 32 bytes and the statistics 12 bytes per window; an hour at a 1 s hop is 3 600 windows.
+// One workgroup walks the table 1024 windows at a time (block_compact, block_prims.h): a kept window's position is the number of kept
+// windows in front of it, so the list is in increasing order whatever the timing.  The table is 32 bytes and the statistics 12 bytes per
+// window; an hour at a 1 s hop is 3 600 windows.
 __global__ __launch_bounds__(kSelectThreads) void window_select_kernel(const avexhip_window* __restrict__ win, const double* __restrict__ energy,
                                                                        const float* __restrict__ peak, int n_win, double thr_energy, float thr_peak,
                                                                        int* __restrict__ kept, int* __restrict__ count) {
-    __shared__ int wave_total[kSelectThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < n_win; base += kSelectThreads) {
-        const int i = base + threadIdx.x;
-        bool keep = false;
-        if (i < n_win) {
-            const int valid = win[i].valid;
-            keep = valid > 0 && energy[i] >= thr_energy * (double)valid && peak[i] >= thr_peak;      // a NaN fails both compares
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_total[wave] = __popcll(m);
-        __syncthreads();
-        int before = __popcll(m & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-        for (int q = 0; q < kSelectThreads / 64; ++q) {
-            const int t = wave_total[q];
-            before += q < wave ? t : 0;
-            total += t;
-        }
-        if (keep) kept[carry + before] = i;
-        carry += total;
-        __syncthreads();                                         // wave_total is rewritten by the next pass
-    }
-    if (threadIdx.x == 0) *count = carry;
+    block_compact<kSelectThreads>(n_win, [&](int i) {
+        const int valid = win[i].valid;
+        return valid > 0 && energy[i] >= thr_energy * (double)valid && peak[i] >= thr_peak;      // a NaN fails both compares
+    }, kept, count);
 }
 
 // grid (ceil(window_len / 1024), B): a thread owns four consecutive samples of one row and their mask bytes.  Window starts are
@@ -191,8 +169,7 @@ int windows_check(const char* what, const float* wav_dev, int64_t wav_samples, c
 extern "C" int avexhip_window_stats(const float* wav_dev, int64_t wav_samples, const avexhip_window* win_host, const avexhip_window* win_dev, int n_win,
                                     int window_len, double* energy_dev, float* peak_dev, void* stream) {
     AVX_REQUIRE(energy_dev && peak_dev, "window_stats: null argument");
-    const int rc = windows_check("window_stats", wav_dev, wav_samples, win_host, win_dev, n_win, window_len, 0, n_win);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(windows_check("window_stats", wav_dev, wav_samples, win_host, win_dev, n_win, window_len, 0, n_win));
     hipLaunchKernelGGL(window_stats_kernel, dim3((unsigned)n_win), dim3(kWinThreads), 0, (hipStream_t)stream, wav_dev, win_dev, energy_dev, peak_dev);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
@@ -216,8 +193,7 @@ extern "C" int avexhip_window_gather(const float* wav_dev, int64_t wav_samples, 
     AVX_REQUIRE(out_dev && mask_dev, "window_gather: null argument");
     AVX_REQUIRE(B >= 1 && B <= 65535, "window_gather: B=%d outside 1..65535", B);
     AVX_REQUIRE(index_dev || (first >= 0 && n_win >= 1 && first <= n_win - B), "window_gather: windows %d .. %d leave the table's %d", first, first + B - 1, n_win);
-    const int rc = windows_check("window_gather", wav_dev, wav_samples, win_host, win_dev, n_win, window_len, index_dev ? 0 : first, index_dev ? n_win : first + B);
-    if (rc != AVEXHIP_OK) return rc;
+    AVXH_TRY(windows_check("window_gather", wav_dev, wav_samples, win_host, win_dev, n_win, window_len, index_dev ? 0 : first, index_dev ? n_win : first + B));
     if (out_stride <= 0) out_stride = window_len;
     AVX_REQUIRE(out_stride >= window_len, "window_gather: out_stride %lld < window_len %d", (long long)out_stride, window_len);
     const int wide_out = ((uintptr_t)out_dev & 15) == 0 && out_stride % 4 == 0;

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(1024) void aggr_mfma(int iters, float* __restrict__
 // per stage: number of waves whose tap differs; first differing (wave, lane, q) with both values
 __global__ void compare_taps(const float2* a, const float2* b, size_t nwaves, unsigned* counts, unsigned long long* first, float* vals) {
     const size_t w = blockIdx.x;
-    for (int st = 0; st < 8; ++st) {
+    for (int st = 0; st < 7; ++st) {      // (slot 7 of a wave's eight is unused)
         const float2* pa = a + (w * 8 + st) * 512; const float2* pb = b + (w * 8 + st) * 512;
         __shared__ int bad;
         if (threadIdx.x == 0) bad = 0;
@@ -65,7 +65,7 @@ int main() {
     };
     CK(hipMemset(tA, 0, tap_elems * 8));
     run(tA, sb); CK(hipDeviceSynchronize());
-    const char* names[8] = {"0 windowed input", "1 after dft8 #1", "2 after twiddle #1", "3 after LDS exchange #1", "4 after dft8+twiddle #2", "5 after LDS exchange #2", "6 after dft8 #3", "7 dft8 #1 level 1 (a0..a3, b0..b3)"};
+    const char* names[7] = {"0 windowed input", "1 after dft8 #1", "2 after twiddle #1", "3 after LDS exchange #1", "4 after dft8+twiddle #2", "5 after LDS exchange #2", "6 after dft8 #3"};      // fft512_wave's tap points
     for (int trial = 0; trial < 4; ++trial) {
         CK(hipMemset(tB, 0, tap_elems * 8)); CK(hipMemset(counts, 0, 64)); CK(hipMemset(first, 0, 64));
         CK(hipDeviceSynchronize());
@@ -77,7 +77,7 @@ int main() {
         unsigned hc[16]; unsigned long long hf[8]; float hv[32];
         CK(hipMemcpy(hc, counts, 64, hipMemcpyDeviceToHost)); CK(hipMemcpy(hf, first, 64, hipMemcpyDeviceToHost)); CK(hipMemcpy(hv, vals, 128, hipMemcpyDeviceToHost));
         printf("== trial %d (%s), %zu waves\n", trial, trial ? "beside the MFMA kernel" : "alone", nwaves);
-        for (int st : {0, 7, 1, 2, 3, 4, 5, 6}) {
+        for (int st = 0; st < 7; ++st) {
             printf("   stage %-26s: %u waves differ, %u values", names[st], hc[st], hc[8 + st]);
             if (hf[st]) { const unsigned long long id = hf[st] - 1; printf("   first: wave %llu lane %llu q %llu  serial (%g, %g) now (%g, %g)", id / 512, (id % 512) / 8, id % 8, hv[4 * st], hv[4 * st + 1], hv[4 * st + 2], hv[4 * st + 3]); }
             printf("\n");

@@ -10,8 +10,9 @@ extra = [a for a in sys.argv[2:] if a.startswith("-")]
 path = src if os.path.exists(src) else os.path.join(ROOT, "avex_amd", "csrc", src)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-fno-gpu-rdc", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
        "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", "/dev/null"] + extra
-if os.path.basename(path) in ("fbank.hip", "wavconv.hip", "melspec.hip", "lstm.hip"):
-    cmd.append("-fno-slp-vectorize")
+sys.path.insert(0, ROOT)
+from avex_amd.build import EXTRA_FLAGS      # the per-file flags the library is built with
+cmd += EXTRA_FLAGS.get(os.path.basename(path), [])
 err = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}

@@ -212,6 +212,19 @@ def test_without_a_frame_count_the_list_is_the_level_gate(built_lib, synth):
         assert 0 < len(kept) < ws.n_windows
 
 
+def test_decisions_over_more_windows_than_one_pass_of_the_select(built_lib):
+    """Nine recordings cut into windows of 768 samples (two frames each at hop 256, none in a recording's short last window): more than
+    1 024 windows, so the kept list is written in a second pass behind the first one's count."""
+    arrays = [A.synthetic(seed=r) for r in range(9)]
+    arrays[3] = arrays[3] * np.float32(0.001)                           # bursts at -70 dBFS: the level gate drops the whole recording
+    for mode in ("any", "all"):
+        gate = ActivityGate(A.BANDS, snr_db=A.SNR_DB, hop=256, mode=mode, min_active_frames=1)
+        ws, act, kept = _check_decisions(arrays, gate, 768, 768, min_rms_db=-45.0)
+        assert ws.n_windows > 1024 and not any(ws.ranges[3][0] <= k < ws.ranges[3][1] for k in kept)
+        if mode == "any":
+            assert sum(k < 1024 for k in kept) > 64 and sum(k >= 1024 for k in kept) > 8 and len(kept) < ws.n_windows // 2
+
+
 # ------------------------------------------------------------------------------------------------------------- 4. end to end
 class _StandIn:
     """What recordings._embed asks of a model; its embedding is four exact facts about the window."""

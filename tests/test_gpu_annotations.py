@@ -202,6 +202,30 @@ def test_a_chain_that_crosses_a_segment_boundary_at_a_chunk_boundary():
     assert want_p[:128].tolist() == list(range(128)) and want_r[128] == -1 and want_p[128:].tolist() == list(range(129, 229))
 
 
+def test_more_scan_chunks_than_one_pass_of_the_carry():
+    """1 024 segments (classes) that each hold the same staggered chain of 33 predictions, every second one with a reference event in
+    front: 512 * 65 + 512 * 66 compatible pairs, more than 256 scan chunks, so the one workgroup that carries the state over the chunk
+    functions takes a second pass and carries a composed state into it -- inside a chain, where a wrong state flips every later
+    decision of the segment.  (One segment of each kind is counted with compatible_pairs; all of a kind are copies.)"""
+    n, n_seg = 33, 1024
+    case = Case(1, n_seg, PERIOD * (n + 2))
+    for c in range(n_seg):
+        _chain(case, 0, c, n, n, first_cell=PERIOD, lead_ref=c % 2 == 1)
+    rows = case.rows()
+    lo, hi = annotations.window_cells(case.plan)
+    table = case.table(case.annotations())
+    per_kind = []
+    for c in (0, 1):
+        spans = [(int(lo[f]), int(hi[l])) for _, cc, f, l in rows if cc == c]
+        a, b = table["seg_offsets"][c:c + 2].tolist()
+        per_kind.append(len(A.compatible_pairs(spans, list(zip(table["lo"][a:b].tolist(), table["hi"][a:b].tolist())), 0.3)))
+    assert per_kind == [2 * n - 1, 2 * n]
+    total = n_seg // 2 * sum(per_kind)
+    assert total > 256 * annotations.CHUNK_PAIRS and (256 * annotations.CHUNK_PAIRS) % sum(per_kind) not in (0, per_kind[0])      # the pass boundary is inside a chain
+    _, want_p, want_r = _check_match(case, 0.3)
+    assert (want_p >= 0).all() and (want_r == -1).sum() == n_seg // 2          # every prediction matched; the last event of a chain with a lead is left over
+
+
 def _mixed_case():
     """Every shape of segment in one call: stars both ways, exact copies, zero-length predictions, segments with only predictions, only
     reference events or neither, and many short segments that share a chunk."""

@@ -132,6 +132,22 @@ def test_state_is_carried_across_whole_chunks(built_lib):
     assert (got["first"].tolist(), got["last"].tolist()) == ([K + 3], [3 * K])
 
 
+def test_more_chunks_than_one_pass_of_the_count(built_lib):
+    """One class over 256 chunks and one window: the prefix of the event starts over the chunks takes a second pass of 256 with the
+    first pass's total as its carry.  Sparse events, one of them across the last chunk boundary."""
+    K = _K()
+    n = 256 * K + 1
+    x = np.full((n, 1), 0.5, dtype=np.float32)                                            # holds ...
+    starts = np.arange(37, n - 1000, 997)
+    x[starts], x[starts + 5] = 2.0, -1.0                                                  # ... between sets and clears five windows later,
+    x[starts[::3] + 2] = 2.25                                                             # a peak behind the first window in every third event
+    x[256 * K - 2] = 2.0                                                                  # and a set that no clear follows: windows 256 K - 2 .. 256 K
+    got, want, st = _decode_both(x, [0, n], (1, "median", 0, 1))
+    _assert_events(got, want, st["mean_terms"])
+    assert len(want["first"]) == len(starts) + 1 > 64 and (want["first"][-1], want["last"][-1]) == (256 * K - 2, 256 * K)
+    assert np.array_equal(want["last"][:-1], starts + 4) and want["peak_window"][0] == starts[0] + 2
+
+
 def test_many_short_sequences_share_a_chunk(built_lib):
     lengths = [1 + (7 * j) % 40 for j in range(200)]
     offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
