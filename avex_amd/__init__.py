@@ -16,6 +16,7 @@ from .examples import ExampleBank, detect_events_by_example
 from .density import dbscan, k_distance
 from .activity import ActivityGate, band_activity
 from .annotations import Annotations, score_events, sweep_thresholds
+from .soundscape import IndexSpec, acoustic_indices, spectral_stats
 
 __version__ = "0.1.0"
 
@@ -25,4 +26,5 @@ __all__ = [
     "get_checkpoint_path", "load_label_mapping", "ModelBase", "ModelSpec", "AudioConfig", "EmbeddingIndex", "query_by_example",
     "decode_events", "detect_events", "ExampleBank", "detect_events_by_example", "dbscan", "k_distance",
     "ActivityGate", "band_activity", "Annotations", "score_events", "sweep_thresholds",
+    "IndexSpec", "acoustic_indices", "spectral_stats",
 ]

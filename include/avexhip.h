@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 22
+#define AVEXHIP_ABI_VERSION 23
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -985,6 +985,76 @@ int avexhip_annot_overlap(const int64_t* span_lo_dev, const int64_t* span_hi_dev
 int avexhip_annot_count(const avexhip_annot_match_args* args, void* stream);
 int avexhip_annot_match(const avexhip_annot_match_args* args, const int64_t* pair_offsets_dev, int32_t* match_of_pred_dev,
                         int32_t* match_of_ref_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Acoustic indices over recordings (ABI 23): what each stretch of a recording looks like before any model is chosen -- the long-term
+ * average spectrum and the standard soundscape indices -- from the resident waveforms above and the frames of the activity gate.
+ *   frames     as avexhip_activity_frames: n_fft = 512, F_r = (n_r - 512) / hop + 1 frames (0 when n_r < 512), no padding, y = x * w in
+ *              fp32 with tables_dev's periodic Hann table.  P[t, k] = |X_t[k]|^2 for k = 0 .. 256 and A = sqrt(P), fp32; full scale is
+ *              AVEXHIP_SOUNDSCAPE_FULL_SCALE = 16384 (a full-scale sine on a bin has |X| = 128).  One frame per transform: P[t, :] is a
+ *              function of the frame's own 512 samples.  A frame of zeros gives +0 in every bin, one holding a NaN or an Inf NaN.
+ *   segments   segment g of recording r holds its frames [g S, min((g + 1) S, F_r)), S = segment_frames; G_r = ceil(F_r / S), the last
+ *              one may be short; the segments of all recordings lie back to back (first_segment).
+ *   runs       (avexhip_soundscape_frames) one workgroup per run of up to AVEXHIP_SOUNDSCAPE_RUN_FRAMES consecutive frames of one
+ *              segment (first_run): frame_power_dev[f] = the sum of P[f, k] over k, and a row of partial sums per run in partials_dev
+ *              (avexhip_soundscape_partials_bytes(runs), runs = the sum over segments of ceil(n / 64)).
+ *   reduce     per (segment, bin) over the segment's n frames in time order, [G, 257]: mean_power = sum P / n, mean_amplitude =
+ *              sum A / n, abs_diff = sum over t >= 1 of |A[t] - A[t-1]| inside the segment (0 when n = 1), count_above (int32) = the
+ *              frames with P > threshold (strict; a NaN is not above).  nonfinite_dev[g] = the segment's NaN frames; with one, the three
+ *              float statistics are NaN in every bin and count_above counts the finite frames.
+ *   indices    [G, 8] fp64 from those fp32 statistics, one workgroup per segment, in the order aci, adi, aei, bi, ndsi, hf, ht, h:
+ *                aci   sum over band of abs_diff / (n mean_amplitude); bins with mean_amplitude = 0 add 0
+ *                adi   p_j = (sum of count_above over ADI band j) / (n bins_j), q_j = p_j / sum p: -sum q ln q (q = 0 adds 0)
+ *                aei   sum_i sum_j |p_i - p_j| / (2 J sum p); adi and aei are NaN when sum p = 0
+ *                bi    L_k = 10 log10(max(mean_power, 1e-12 P_FS) / P_FS) over bio: sum (L_k - min L) * bin_khz
+ *                ndsi  (b - a) / (b + a), b and a the sums of mean_power over bio and anthro; NaN when a + b = 0
+ *                hf    q_k = mean_power / its sum over band: -sum q ln q / ln K, K the bins of band; NaN when the sum is 0 or K < 2
+ *                ht    q_t = frame_power / its sum over the segment: -sum q ln q / ln n; NaN when the sum is 0 or n < 2
+ *                h     hf * ht
+ *              every column NaN for a segment with a non-finite frame.
+ * Sums run in one fixed order and nothing is atomic: a segment's numbers depend on its recording's samples, hop, S and the threshold
+ * alone, the same bits in any company and on every run.  rec_host / rec_dev: the same table on the host (read for the argument checks)
+ * and on the device.  Every entry point refuses with AVEXHIP_ERR_INVALID before anything is launched: null or misaligned pointers, hop
+ * outside 32 .. 512, segment_frames outside 1 .. 2^24, a recording that leaves wav_dev, first_frame / first_segment / first_run /
+ * total_frames / total_segments that do not follow from the samples, hop and S, bins outside 0 <= lo < hi <= 257, n_adi outside 1 .. 32,
+ * a NaN or negative threshold; a partials buffer that is too small gives AVEXHIP_ERR_WORKSPACE.  No segment: success, nothing launched.
+ * Nothing here allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_SOUNDSCAPE_RUN_FRAMES 64
+#define AVEXHIP_SOUNDSCAPE_MAX_SEGMENT_FRAMES 16777216      /* 2^24: n is exact in fp32 */
+#define AVEXHIP_SOUNDSCAPE_MAX_ADI_BANDS 32
+#define AVEXHIP_SOUNDSCAPE_INDICES 8
+#define AVEXHIP_SOUNDSCAPE_FULL_SCALE 16384.0f
+typedef struct {
+    int64_t base;            /* first sample of the recording in wav_dev, counted in floats */
+    int64_t n_samples;       /* samples of the recording */
+    int64_t first_frame;     /* frames of the recordings in front of it */
+    int32_t first_segment;   /* segments of the recordings in front of it */
+    int32_t first_run;       /* runs of the recordings in front of it */
+} avexhip_soundscape_recording;
+typedef struct {
+    int32_t band[2];         /* bins lo .. hi - 1 of aci and hf */
+    int32_t bio[2];          /* of bi, and of ndsi's biophony */
+    int32_t anthro[2];       /* of ndsi's anthrophony */
+    int32_t n_adi;           /* J, 1 .. 32 */
+    int32_t reserved;
+    int32_t adi[AVEXHIP_SOUNDSCAPE_MAX_ADI_BANDS][2];
+    double bin_khz;          /* sr / 512 / 1000 */
+} avexhip_soundscape_index_spec;
+size_t avexhip_soundscape_partials_bytes(int64_t n_runs);      /* 0: a count it refuses */
+int avexhip_soundscape_frames(const float* wav_dev, int64_t wav_samples, const avexhip_soundscape_recording* rec_host,
+                              const avexhip_soundscape_recording* rec_dev, int n_rec, int hop, int segment_frames, float threshold,
+                              const float* tables_dev, int64_t total_frames, int64_t total_segments, void* partials_dev, size_t partials_bytes,
+                              float* frame_power_dev, void* stream);
+int avexhip_soundscape_reduce(const avexhip_soundscape_recording* rec_host, const avexhip_soundscape_recording* rec_dev, int n_rec, int hop,
+                              int segment_frames, int64_t total_frames, int64_t total_segments, const void* partials_dev, size_t partials_bytes,
+                              float* mean_power_dev, float* mean_amplitude_dev, float* abs_diff_dev, int32_t* count_above_dev,
+                              int32_t* nonfinite_dev, void* stream);
+int avexhip_soundscape_indices(const avexhip_soundscape_recording* rec_host, const avexhip_soundscape_recording* rec_dev, int n_rec, int hop,
+                               int segment_frames, int64_t total_frames, int64_t total_segments, const avexhip_soundscape_index_spec* spec,
+                               const float* mean_power_dev, const float* mean_amplitude_dev, const float* abs_diff_dev,
+                               const int32_t* count_above_dev, const int32_t* nonfinite_dev, const float* frame_power_dev, double* indices_dev,
+                               void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
