@@ -241,11 +241,8 @@ __global__ __launch_bounds__(64) void activity_count_kernel(const avexhip_window
             cnt += v > thr ? 1 : 0;
             mx = nan_max(mx, v);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            cnt += __shfl_xor(cnt, o, 64);
-            mx = nan_max(mx, __shfl_xor(mx, o, 64));
-        }
+        cnt = wave_reduce(cnt, BlockSum());
+        mx = wave_reduce(mx, [](float a, float b) { return nan_max(a, b); });
         if (lane == 0) {
             active[(int64_t)w * n_bands + b] = cnt;
             max_energy[(int64_t)w * n_bands + b] = mx;

@@ -28,6 +28,7 @@
 //   clus_contingency / scores   integer contingency table, then ARI / NMI / V-measure in fp64 by scikit-learn's formulas
 //
 // Limits: k <= 4096, n_init <= 64, n <= 2^24.
+#include "block_prims.h"
 #include "f32_tile.h"
 
 namespace {
@@ -44,30 +45,6 @@ static inline int trials_of(int k) {
     static const int ceil_exp[] = {3, 8, 21, 55, 149, 404, 1097, 2981, 8104};
     for (int m = 0; m < 9 && k >= ceil_exp[m]; ++m) ++t;
     return t;
-}
-
-template <int THREADS> static __device__ __forceinline__ double block_sum_f64(double v, double* red, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-template <int THREADS> static __device__ __forceinline__ long long block_sum_i64(long long v, long long* red, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const long long r = red[0];
-    __syncthreads();
-    return r;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -123,7 +100,7 @@ __global__ __launch_bounds__(256) void clus_tol_kernel(const double* __restrict_
         for (int ch = 0; ch < NCHUNK; ++ch) c += part[(int64_t)ch * dpad + col];
         s += c / (double)n;
     }
-    const double tot = block_sum_f64<256>(s, red, threadIdx.x);
+    const double tot = block_tree_sum<256>(s, red);
     if (threadIdx.x == 0) tol_abs[0] = tot / (double)d * tol;
 }
 
@@ -210,7 +187,7 @@ __global__ __launch_bounds__(1024) void clus_seed_pick_kernel(const float* __res
         const float* __restrict__ m = mind + (int64_t)(r * T_in + t) * n;
         double s = 0.0;
         for (int i = tid; i < n; i += 1024) s += (double)m[i];
-        const double tot = block_sum_f64<1024>(s, red, tid);
+        const double tot = block_tree_sum<1024>(s, red);
         if (tid == 0) pots[t] = tot;
     }
     if (tid == 0) {
@@ -317,6 +294,7 @@ __global__ __launch_bounds__(256) void clus_assign_kernel(const float* __restric
     const bool one_restart = rst[0] == rst[1];      // wave-uniform: both 32-column groups belong to one restart (always when kpad % 64 == 0)
     auto key_of = [&](int j, float a) __attribute__((always_inline)) {
         const float dist = cn[j] - 2.0f * a;
+        // not rank_key: the SMALLEST key wins (nearest centre, then lower j), so the index is not inverted and KEY_NONE is all ones
         return ok[j] ? ((unsigned long long)mono32(dist + 0.0f) << 32) | (unsigned long long)(unsigned)jj[j] : KEY_NONE;
     };
     auto row_min = [&](unsigned long long key) __attribute__((always_inline)) {
@@ -357,7 +335,7 @@ __global__ __launch_bounds__(256) void clus_assign_kernel(const float* __restric
 
 __global__ __launch_bounds__(256) void clus_post_kernel(const unsigned long long* __restrict__ best, int n, int k, const int32_t* __restrict__ status,
                                                          int32_t* __restrict__ labels, int32_t* __restrict__ changed) {
-    __shared__ long long red[256];
+    __shared__ long long red[4];
     const int r = blockIdx.y, tid = threadIdx.x;
     if (status[r] == 2) return;
     const int i = blockIdx.x * 256 + tid;
@@ -369,7 +347,7 @@ __global__ __launch_bounds__(256) void clus_post_kernel(const unsigned long long
         ch = labels[(int64_t)r * n + i] != lab;
         labels[(int64_t)r * n + i] = lab;
     }
-    const long long tot = block_sum_i64<256>(ch, red, tid);
+    const long long tot = block_reduce<4>(ch, BlockSum(), red);
     if (tid == 0 && tot) atomicAdd(changed + r, (int)tot);
 }
 
@@ -435,7 +413,7 @@ __global__ __launch_bounds__(256) void clus_update_kernel(const float* __restric
 __global__ __launch_bounds__(1024) void clus_relocate_kernel(const float* __restrict__ xc, const float* __restrict__ xnorm, int n, int dpad, int k, int kpad,
                                                               const int32_t* __restrict__ labels, const int32_t* __restrict__ status,
                                                               unsigned long long* __restrict__ best, float* __restrict__ sums, int32_t* __restrict__ counts) {
-    __shared__ unsigned long long red[1024];
+    __shared__ unsigned long long red[16];
     __shared__ int empties[CLUS_MAX_K];
     __shared__ int n_empty;
     const int tid = threadIdx.x, r = blockIdx.x;
@@ -458,23 +436,14 @@ __global__ __launch_bounds__(1024) void clus_relocate_kernel(const float* __rest
         for (int i = tid; i < n; i += 1024) {
             const unsigned long long key = bk[i];
             if (key == KEY_NONE) continue;
-            const unsigned u = (unsigned)(key >> 32);
-            const float part = __uint_as_float((u & 0x80000000u) ? u ^ 0x80000000u : ~u);
-            const float dist = part + xnorm[i];
-            const unsigned long long cand = ((unsigned long long)mono32(dist + 0.0f) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
+            const float dist = mono32_inv((unsigned)(key >> 32)) + xnorm[i];      // the assign key's high word
+            const unsigned long long cand = rank_key(dist + 0.0f, (unsigned)i);
             m = cand > m ? cand : m;
         }
-        red[tid] = m;
-        __syncthreads();
-        for (int s = 512; s > 0; s >>= 1) {
-            if (tid < s) red[tid] = red[tid + s] > red[tid] ? red[tid + s] : red[tid];
-            __syncthreads();
-        }
-        const unsigned long long top = red[0];
-        __syncthreads();
+        const unsigned long long top = block_reduce<16>(m, BlockMax(), red);      // red is next written behind the barrier that ends this round
         if (top == 0ull) return;      // block-uniform: no point left
         const int dst = empties[it];
-        const int p = (int)(0xFFFFFFFFu - (unsigned)(top & 0xFFFFFFFFull));
+        const int p = (int)rank_key_index(top);
         const int src = labels[(int64_t)r * n + p];
         float* s_src = sums + ((int64_t)r * kpad + src) * dpad;
         float* s_dst = sums + ((int64_t)r * kpad + dst) * dpad;
@@ -523,7 +492,7 @@ __global__ __launch_bounds__(1024) void clus_decide_kernel(int dpad, int k, int 
         shift += (double)df * (double)df;
         centres[at] = v;
     }
-    const double tot = block_sum_f64<1024>(shift, red, tid);
+    const double tot = block_tree_sum<1024>(shift, red);
     if (tid == 0) {
         const int it = n_iter[r] + 1;
         n_iter[r] = it;
@@ -576,7 +545,7 @@ __global__ __launch_bounds__(256) void clus_inertia_kernel(const float* __restri
             }
         }
     }
-    const double tot = block_sum_f64<256>((double)s, red, tid);
+    const double tot = block_tree_sum<256>((double)s, red);
     if (tid == 0) ipart[(int64_t)r * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -639,7 +608,7 @@ __global__ __launch_bounds__(256) void clus_contingency_kernel(const int32_t* __
 __global__ __launch_bounds__(256) void clus_scores_kernel(const int32_t* __restrict__ table, int na, int nb, long long* __restrict__ marg,
                                                            double* __restrict__ out) {
     __shared__ double redd[256];
-    __shared__ long long redi[256];
+    __shared__ long long redi[6][4];      // block_reduce has no trailing barrier: the six sums take a row each
     const int tid = threadIdx.x;
     long long* ra = marg;
     long long* cb = marg + na;
@@ -669,12 +638,12 @@ __global__ __launch_bounds__(256) void clus_scores_kernel(const int32_t* __restr
         sb += cb[j] * cb[j];
         cbn += cb[j] > 0;
     }
-    ss = block_sum_i64<256>(ss, redi, tid);
-    sa = block_sum_i64<256>(sa, redi, tid);
-    sb = block_sum_i64<256>(sb, redi, tid);
-    nn = block_sum_i64<256>(nn, redi, tid);
-    ca = block_sum_i64<256>(ca, redi, tid);
-    cbn = block_sum_i64<256>(cbn, redi, tid);
+    ss = block_reduce<4>(ss, BlockSum(), redi[0]);
+    sa = block_reduce<4>(sa, BlockSum(), redi[1]);
+    sb = block_reduce<4>(sb, BlockSum(), redi[2]);
+    nn = block_reduce<4>(nn, BlockSum(), redi[3]);
+    ca = block_reduce<4>(ca, BlockSum(), redi[4]);
+    cbn = block_reduce<4>(cbn, BlockSum(), redi[5]);
     const double N = (double)nn, logN = log(N);
     // entropies and mutual information
     double ha = 0.0, hb = 0.0, mi = 0.0;
@@ -693,9 +662,9 @@ __global__ __launch_bounds__(256) void clus_scores_kernel(const int32_t* __restr
                 mi += fabs(t) < 2.220446049250313e-16 ? 0.0 : t;
             }
         }
-    ha = -block_sum_f64<256>(ha, redd, tid);
-    hb = -block_sum_f64<256>(hb, redd, tid);
-    mi = block_sum_f64<256>(mi, redd, tid);
+    ha = -block_tree_sum<256>(ha, redd);
+    hb = -block_tree_sum<256>(hb, redd);
+    mi = block_tree_sum<256>(mi, redd);
     if (tid != 0) return;
     if (ca <= 1) ha = 0.0;
     if (cbn <= 1) hb = 0.0;

@@ -281,11 +281,21 @@ static __device__ __forceinline__ float hsum2(f32x2 x) {
     return r;
 }
 
-static __device__ __forceinline__ float wave_sum(float v) {
+// The operators of the wave and workgroup reductions and scans (below, block_prims.h)
+struct BlockSum {
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct BlockMax {
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; }
+};
+// The xor butterfly 32 .. 1 over the 64 lanes of a wave, v = op(v, the partner lane's v) at every step: every lane ends with the same
+// value when op(a, b) == op(b, a) bit for bit (sums, maxima).  Every lane of the wave must make the call.
+template <typename T, typename Op> static __device__ __forceinline__ T wave_reduce(T v, Op op) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     return v;
 }
+static __device__ __forceinline__ float wave_sum(float v) { return wave_reduce(v, BlockSum()); }
 // max(a, x) that keeps a NaN from either side, like torch.max over a dimension (fmaxf returns its non-NaN operand): the pooled maxima
 static __device__ __forceinline__ float nan_max(float a, float x) { return (x > a || x != x) ? x : a; }
 static __device__ __forceinline__ bool non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }      // NaN or Inf: exponent all ones
@@ -293,9 +303,7 @@ static __device__ __forceinline__ f32x4 nan_max4(f32x4 a, f32x4 x) {
     return (f32x4){nan_max(a[0], x[0]), nan_max(a[1], x[1]), nan_max(a[2], x[2]), nan_max(a[3], x[3])};
 }
 static __device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
+    return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
 // XCD-aware, bijective block remap: blocks that share blockIdx % 8 share an XCD (and its L2);

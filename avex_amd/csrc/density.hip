@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void dens_sizes_kernel(int64_t n, const int32_
     if (i < n) {
         c = labels[i];
         c = c < n_clusters ? c : -1;
-        if (c >= 0 && label[i] != DN_NONE) key = ((unsigned long long)(unsigned)count[i] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
+        if (c >= 0 && label[i] != DN_NONE) key = rank_key((unsigned)count[i], (unsigned)i);
     }
     unsigned long long todo = __ballot(c >= 0);
     while (todo) {
@@ -347,12 +347,7 @@ __global__ __launch_bounds__(256) void dens_sizes_kernel(int64_t n, const int32_
         const int lc = __shfl(c, leader);
         const bool same = c == lc;
         const unsigned long long mask = __ballot(same);
-        unsigned long long k = same ? key : 0ull;
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) {
-            const unsigned long long o = __shfl_xor(k, s);
-            k = o > k ? o : k;
-        }
+        const unsigned long long k = wave_reduce(same ? key : 0ull, BlockMax());
         if (lane == leader) {
             atomicAdd(sizes + lc, __popcll(mask));
             if (k) atomicMax(keys + lc, k);
@@ -365,7 +360,7 @@ __global__ __launch_bounds__(256) void dens_exemplar_kernel(int n_clusters, cons
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n_clusters) return;
     const unsigned long long k = keys[c];
-    exemplar[c] = k ? (int32_t)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)) : -1;
+    exemplar[c] = k ? (int32_t)rank_key_index(k) : -1;
 }
 
 static int check_args(const avexhip_density_args* a, const char* what, Workspace* w) {

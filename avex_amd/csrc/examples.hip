@@ -11,9 +11,8 @@
 //   ex_tile_kernel        workgroup (column tile, 128-query tile): f32_tile_product as it is (queries are the A operand, as in
 //                         srch_sim_kernel: the bits of a similarity are those a search returns), the tile written to LDS over the operand
 //                         buffers (row stride EX_LDD, the padding of silhouette.hip), then thread (query row, parity) scans the columns of
-//                         every second segment of the tile and keeps the top_m largest keys
-//                             key = (mono32(sim + 0.0f) << 32) | (0xFFFFFFFF - row_id)        the search key with the insertion row
-//                         in a register list (depth a template parameter, insertion fully unrolled), NaN similarities skipped, unused
+//                         every second segment of the tile and keeps the top_m largest keys rank_key(similarity, row_id) (f32_tile.h: the
+//                         search key with the insertion row) in a register list (depth a template parameter, insertion fully unrolled), NaN similarities skipped, unused
 //                         entries 0.  The list goes to part[segment][batch row][top_m].
 //   ex_reduce_kernel      thread (query, class): the lists of the class's consecutive segments merged into its top_m, their similarities
 //                         added in fp32 in descending order from the largest, divided by float(count); NaN when there is none.  Launched
@@ -56,10 +55,6 @@ template <int DEPTH> static __device__ __forceinline__ void ex_insert(ex_key_t (
         }
     }
 }
-static __device__ __forceinline__ float ex_key_sim(ex_key_t key) {
-    const unsigned u = (unsigned)(key >> 32);
-    return __uint_as_float((u >> 31) ? u ^ 0x80000000u : ~u);
-}
 
 __global__ __launch_bounds__(256) void ex_prepare_kernel(const float* __restrict__ x, int64_t ldx, int n, int d, int dpad, int normalise,
                                                          float* __restrict__ out) {
@@ -82,7 +77,7 @@ template <int DEPTH> __global__ __launch_bounds__(256) void ex_tile_kernel(TileA
     unsigned* rid = (unsigned*)(smem + EX_TILE_BYTES);
     const int tid = threadIdx.x;
     const int t = blockIdx.x, c0 = t * FT_BN, q0 = blockIdx.y * FT_BM;
-    if (tid < FT_BN) rid[tid] = c0 + tid < p.m ? 0xFFFFFFFFu - (unsigned)p.row_id[c0 + tid] : 0u;      // behind the operand buffers: free at once
+    if (tid < FT_BN) rid[tid] = c0 + tid < p.m ? rank_key_low((unsigned)p.row_id[c0 + tid]) : 0u;      // behind the operand buffers: free at once
     f32x16 acc[2][2];
     f32_tile_product(p.Q, p.nb, q0, p.bank, p.m, c0, p.dpad, acc);
     __syncthreads();      // every wave has read its last operand tile: the buffers become the similarity tile
@@ -118,7 +113,7 @@ template <int DEPTH> __global__ __launch_bounds__(256) void ex_tile_kernel(TileA
                 const int col = 4 * q + e;
                 const float sim = v[e];
                 const bool in = col >= lo && col <= hi && sim == sim;
-                const ex_key_t key = ((ex_key_t)mono32(sim + 0.0f) << 32) | (ex_key_t)id[e];
+                const ex_key_t key = rank_key_from_low(sim + 0.0f, id[e]);
                 ex_insert(L, in ? key : 0ull);
             }
         }
@@ -167,7 +162,7 @@ template <int DEPTH> __global__ __launch_bounds__(256) void ex_reduce_kernel(Red
 #pragma unroll
     for (int i = 0; i < DEPTH; ++i)
         if (i < p.top_m && L[i] != 0ull) {      // descending, from the largest
-            const float v = ex_key_sim(L[i]);
+            const float v = rank_key_value(L[i]);
             sum = cnt ? sum + v : v;
             ++cnt;
         }
@@ -177,7 +172,7 @@ template <int DEPTH> __global__ __launch_bounds__(256) void ex_reduce_kernel(Red
         return;
     }
     p.scores[(int64_t)n * p.ld_scores + c] = p.margin ? val - p.bg_in[n] : val;
-    if (p.nearest) p.nearest[(int64_t)n * p.ld_nearest + c] = cnt ? (int32_t)(0xFFFFFFFFu - (unsigned)(L[0] & 0xFFFFFFFFull)) : -1;
+    if (p.nearest) p.nearest[(int64_t)n * p.ld_nearest + c] = cnt ? (int32_t)rank_key_index(L[0]) : -1;
 }
 
 // out[k][col] = (sum over rows first[k] .. first[k] + count[k] - 1, in order, from 0.0f) / float(count[k]); zero beyond d

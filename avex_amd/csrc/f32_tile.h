@@ -18,11 +18,28 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // floats per row of a stored similarity matrix over n columns (retrieval.hip, search.hip)
 static inline int64_t ldsim_of(int64_t n) { return (n + 63) / 64 * 64; }
 
-// order-preserving map of a float onto unsigned integers (-0 is folded onto +0 first by the caller)
+// order-preserving map of a float onto unsigned integers (-0 is folded onto +0 first by the caller), and its inverse
 static __device__ __forceinline__ unsigned mono32(float v) {
     const unsigned u = __float_as_uint(v);
     return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
+static __device__ __forceinline__ float mono32_inv(unsigned u) { return __uint_as_float((u >> 31) ? u ^ 0x80000000u : ~u); }
+
+// The rank key of retrieval, search, few-shot examples, k-means relocation and the density exemplars: (mono32(v) << 32) | (0xFFFFFFFF - index).
+// Unsigned 64-bit order = value descending, then index ascending, so a maximum is "the best, the first on ties"; keys of different
+// indices differ, and 0 is "no key" (no real key is 0: index < 2^32 - 1).  The caller passes v + 0.0f, which folds -0 onto +0; NaN
+// sorts above +inf unless the caller drops it.  The high word may be any unsigned value instead of a float (density: a count).
+static __device__ __forceinline__ unsigned rank_key_low(unsigned index) { return 0xFFFFFFFFu - index; }      // the low word; its own inverse
+static __device__ __forceinline__ unsigned long long rank_key(unsigned hi, unsigned index) {
+    return ((unsigned long long)hi << 32) | (unsigned long long)rank_key_low(index);
+}
+static __device__ __forceinline__ unsigned long long rank_key(float v, unsigned index) { return rank_key(mono32(v), index); }
+// the same key from a low word the caller made with rank_key_low and kept (examples.hip holds a tile's in LDS)
+static __device__ __forceinline__ unsigned long long rank_key_from_low(float v, unsigned low) {
+    return ((unsigned long long)mono32(v) << 32) | (unsigned long long)low;
+}
+static __device__ __forceinline__ unsigned rank_key_index(unsigned long long key) { return rank_key_low((unsigned)(key & 0xFFFFFFFFull)); }
+static __device__ __forceinline__ float rank_key_value(unsigned long long key) { return mono32_inv((unsigned)(key >> 32)); }
 
 // acc = A[a0 .. a0 + 128) . B[b0 .. b0 + 128)^T for a workgroup of 256 threads with FT_LDS_BYTES of dynamic LDS.  A (na rows) and B (nb rows)
 // are row-major with dpad floats per row (dpad % 32 == 0, zero beyond the real width).  Wave (wr, wc) = (wid >> 1, wid & 1) owns rows
@@ -125,9 +142,7 @@ static __device__ __forceinline__ void f32_prepare_rows(const float* __restrict_
     }
     float ss = 0.f;
     for (int c = lane; c < d; c += 64) ss = __builtin_fmaf(r[c], r[c], ss);
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) ss += __shfl_xor(ss, s);
-    float nrm = __builtin_sqrtf(ss);
+    float nrm = __builtin_sqrtf(wave_sum(ss));
     nrm = nrm < 1e-12f ? 1e-12f : nrm;
     float* o = out + (int64_t)row * dpad;
     for (int c = lane; c < dpad; c += 64) o[c] = c < d ? r[c] / nrm : 0.f;

@@ -11,6 +11,8 @@
 //                           of {positives, negatives} is sorted in LDS (bitonic, chunks of <= 16 Ki keys); every element of the other side
 //                           does a lower- and an upper-bound search in it.
 //   retr_finalize_kernel    validity rules of the reference + the fp64 means, in a fixed order (bit-reproducible).
+// The top-k key is rank_key (f32_tile.h); reductions, sort and append are those of block_prims.h.
+#include "block_prims.h"
 #include "f32_tile.h"
 
 namespace {
@@ -59,31 +61,6 @@ struct RankArgs {
     int32_t* topk;
 };
 
-static __device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(v, o);
-        v = t > v ? t : v;
-    }
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    unsigned long long m = red[0];
-#pragma unroll
-    for (int w = 1; w < RANK_THREADS / 64; ++w) m = red[w] > m ? red[w] : m;
-    return m;
-}
-
-static __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    unsigned long long m = red[0];
-#pragma unroll
-    for (int w = 1; w < RANK_THREADS / 64; ++w) m += red[w];
-    return m;
-}
-
 // number of keys < x (LE = false) or <= x (LE = true) among the np2 ascending keys of a (np2 a power of two; the tail beyond the real
 // keys is +inf).  Branch-free: the probe addresses of the first steps are the same in every lane (LDS broadcast).
 template <bool LE> static __device__ __forceinline__ int count_below(const float* a, int np2, float x) {
@@ -98,7 +75,8 @@ template <bool LE> static __device__ __forceinline__ int count_below(const float
 
 __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ unsigned long long red[8][RANK_THREADS / 64];
+    constexpr int WAVES = RANK_THREADS / 64;
+    __shared__ unsigned long long red[5][WAVES];      // block_reduce has no trailing barrier: reductions back to back take a row each
     __shared__ int fill;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int b = blockIdx.x;
@@ -136,8 +114,8 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
         if (in && n == self) relself = rel ? 1 : 0;
         if (in && n != self) {
             npos += rel ? 1 : 0;
-            const unsigned long long key = ((unsigned long long)mono32(srow[n] + 0.0f) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
-            if (key > thr) {      // higher similarity first, then lower index
+            const unsigned long long key = rank_key(srow[n] + 0.0f, (unsigned)n);
+            if (key > thr) {
                 int j = k - 1;
                 while (j > 0 && list[(j - 1) * RANK_THREADS + tid] < key) {
                     list[j * RANK_THREADS + tid] = list[(j - 1) * RANK_THREADS + tid];
@@ -148,8 +126,8 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
             }
         }
     }
-    const int P = (int)block_sum_u64((unsigned long long)npos, red[0], tid);                  // the barrier inside publishes mask[]
-    const int rel_total = P + (int)block_sum_u64((unsigned long long)relself, red[1], tid);
+    const int P = (int)block_reduce<WAVES>((unsigned long long)npos, BlockSum(), red[0]);      // the barrier inside publishes mask[]
+    const int rel_total = P + (int)block_reduce<WAVES>((unsigned long long)relself, BlockSum(), red[1]);
     const int n_eff = nd - ((self >= 0 && self < nd) ? 1 : 0);
     const int Q = n_eff - P;
 
@@ -161,10 +139,10 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
             continue;
         }
         const unsigned long long cur = head < k ? list[head * RANK_THREADS + tid] : 0ull;
-        const unsigned long long best = block_max_u64(cur, red[2 + (r & 1)], tid);
+        const unsigned long long best = block_reduce<WAVES>(cur, BlockMax(), red[2 + (r & 1)]);      // the rows alternate: the next round writes the other
         if (best != 0ull && cur == best) ++head;      // keys carry their column: unique
         if (tid == 0) {
-            const int idx = best != 0ull ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
+            const int idx = best != 0ull ? (int)rank_key_index(best) : -1;
             p.topk[(int64_t)b * RANK_MAX_K + r] = idx;
             if (idx >= 0) nhit += (int)((mask[idx >> 6] >> (idx & 63)) & 1ull);
         }
@@ -193,13 +171,9 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
                 const int n = base + lane;
                 const bool rel = (mask[base >> 6] >> lane) & 1ull;
                 const bool sel = n < c1 && n != self && rel == pos_small;
-                const unsigned long long bal = __ballot(sel);
-                if (bal != 0ull) {
-                    int at = 0;
-                    if (lane == 0) at = atomicAdd(&fill, (int)__popcll(bal));
-                    at = __shfl(at, 0);
-                    if (sel) keys[at + (int)__popcll(bal & ((1ull << lane) - 1ull))] = srow[n] + 0.0f;
-                }
+                // the load is unconditional (a lane past the row reads its last column), so that it is in flight under the ballot and the
+                // atomic; a chunk holds at most cap keys of the smaller side: the bound is a safety net that never rejects
+                wave_append(sel, srow[n < nd ? n : nd - 1] + 0.0f, keys, &fill, p.cap);
             }
             __syncthreads();
             const int cnt = fill;
@@ -208,18 +182,7 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
             while (np2 < cnt) np2 <<= 1;
             for (int i = cnt + tid; i < np2; i += RANK_THREADS) keys[i] = __builtin_inff();
             __syncthreads();
-            for (int size = 2; size <= np2; size <<= 1)
-                for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                    for (int t = tid; t < (np2 >> 1); t += RANK_THREADS) {
-                        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                        const float x = keys[i], y = keys[j];
-                        if ((x > y) == ((i & size) == 0)) {
-                            keys[i] = y;
-                            keys[j] = x;
-                        }
-                    }
-                    __syncthreads();
-                }
+            block_bitonic_sort<RANK_THREADS>(keys, np2, [](float a, float b) { return a < b; });      // ascending
             for (int base = wid * 64; base < nd; base += RANK_THREADS) {
                 const int n = base + lane;
                 const bool rel = (mask[base >> 6] >> lane) & 1ull;
@@ -234,7 +197,7 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
             }
         }
     }
-    const unsigned long long tot = block_sum_u64(u2, red[4], tid);
+    const unsigned long long tot = block_reduce<WAVES>(u2, BlockSum(), red[4]);
     if (tid == 0) p.u2[b] = (long long)tot;
 }
 
@@ -244,7 +207,8 @@ __global__ __launch_bounds__(RANK_THREADS) void retr_rank_kernel(RankArgs p) {
 // the AUC, one with no negative left.  Cross-set (:386-399, 640-660): no positive = skipped in both; no negative = skipped in the AUC.
 __global__ __launch_bounds__(256) void retr_finalize_kernel(const long long* __restrict__ u2, const int32_t* __restrict__ stats, int nq, int self_set,
                                                              int k, double* __restrict__ out) {
-    __shared__ double red[4][256];
+    typedef double f64x4 __attribute__((ext_vector_type(4)));      // the four sums as one value: one tree, each column in its own order
+    __shared__ f64x4 red[256];
     const int tid = threadIdx.x;
     double a = 0.0, an = 0.0, pr = 0.0, pn = 0.0;
     for (int i = tid; i < nq; i += 256) {
@@ -260,17 +224,9 @@ __global__ __launch_bounds__(256) void retr_finalize_kernel(const long long* __r
             pn += 1.0;
         }
     }
-    red[0][tid] = a;
-    red[1][tid] = an;
-    red[2][tid] = pr;
-    red[3][tid] = pn;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int c = 0; c < 4; ++c) red[c][tid] += red[c][tid + s];
-        __syncthreads();
-    }
-    if (tid < 4) out[tid] = red[tid][0];
+    const f64x4 tot = block_tree_sum<256>((f64x4){a, an, pr, pn}, red);
+    if (tid == 0)
+        for (int c = 0; c < 4; ++c) out[c] = tot[c];
 }
 
 struct Workspace {

@@ -5,10 +5,10 @@
 //   srch_sim_kernel       S[b][n] = q_b . d_n for one query batch against one chunk: f32_tile_product (f32_tile.h) with a store, the shape
 //                         of retr_sim_kernel.  The sum of a similarity runs over its two rows in an order the tile fixes: it does not depend
 //                         on the chunk, the batch or the tile the pair falls in.
-//   srch_select_kernel    one workgroup per query: the running list of the K' best keys merged with the chunk's similarities.
-//                             key = (mono32(sim + 0.0f) << 32) | (0xFFFFFFFF - global row)        higher similarity first, then lower row
-//                         Keys are unique, so "the K' largest keys of everything seen so far" is one set, whatever the chunking, and the
-//                         list is that set in descending order: the result does not depend on how the rows were split into chunks.
+//   srch_select_kernel    one workgroup per query: the running list of the K' best keys merged with the chunk's similarities; a key is
+//                         rank_key(similarity, global row) (f32_tile.h): higher similarity first, then lower row.  Keys are unique, so
+//                         "the K' largest keys of everything seen so far" is one set, whatever the chunking, and the list is that set in
+//                         descending order: the result does not depend on how the rows were split into chunks.
 //                         Pass 0 forms the keys and drops columns (NaN, the query's own row, the exclusion rule, keys under the list's
 //                         last entry when the list is full) by overwriting their similarity in the workspace with NaN.  A radix select on
 //                         the key (8 bits per pass, most significant first, a histogram in LDS, stops as soon as a bucket is taken whole)
@@ -17,6 +17,7 @@
 //                         LDS integer atomics only count (histogram bins, compaction slots); the sort of unique keys removes the slot order.
 //   srch_finish_kernel    one workgroup per query: greedy temporal non-maximum suppression over the K' candidates (optional), then keys ->
 //                         scores (the similarity's bits), rows, and the hits' recording / start / end.
+#include "block_prims.h"
 #include "f32_tile.h"
 
 namespace {
@@ -64,8 +65,15 @@ struct SelectArgs {
 static __device__ __forceinline__ double srch_min(double a, double b) { return (a < b || a != a) ? a : b; }
 static __device__ __forceinline__ double srch_max(double a, double b) { return (a > b || a != a) ? a : b; }
 
-static __device__ __forceinline__ unsigned long long srch_key(float s, unsigned grow) {
-    return ((unsigned long long)mono32(s + 0.0f) << 32) | (unsigned long long)(0xFFFFFFFFu - grow);
+// The entries of a descending key list are a prefix: the first index in [0, n) that holds 0 (n when none does), by a search every thread
+// makes for itself (the same addresses in every lane)
+static __device__ __forceinline__ int srch_entries(const unsigned long long* list, int n) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (list[mid] != 0ull) lo = mid + 1; else hi = mid;
+    }
+    return lo;
 }
 
 __global__ __launch_bounds__(SRCH_THREADS) void srch_select_kernel(SelectArgs p) {
@@ -82,17 +90,9 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_select_kernel(SelectArgs p)
     unsigned long long* __restrict__ list = p.lists + (int64_t)b * kp;
 
     for (int i = tid; i < kp; i += SRCH_THREADS) old_[i] = list[i];
+    if (tid == 0) fill = 0;      // the compaction's counter, published by this barrier
     __syncthreads();
-    // the list is sorted: its entries are a prefix; n_old by a search every thread makes for itself (LDS broadcast)
-    int n_old = 0;
-    {
-        int lo = 0, hi = kp;      // first index holding 0
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (old_[mid] != 0ull) lo = mid + 1; else hi = mid;
-        }
-        n_old = lo;
-    }
+    const int n_old = srch_entries(old_, kp);
     const unsigned long long floor_key = n_old == kp ? old_[kp - 1] : 0ull;      // a full list: nothing under its last entry can enter
 
     // ---- pass 0: drop columns, count the rest -------------------------------------------------------------------------------------
@@ -113,16 +113,11 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_select_kernel(SelectArgs p)
                 drop = srch_min(qe, de) > srch_max(qs, ds);      // a positive overlap: min(end) > max(start), no arithmetic
             }
         }
-        if (!drop) drop = srch_key(s, grow) < floor_key;
+        if (!drop) drop = rank_key(s + 0.0f, grow) < floor_key;
         if (drop) srow[n] = __builtin_nanf("");
         else ++mine;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-    if (lane == 0) wsum[wid] = mine;
-    if (tid == 0) fill = 0;
-    __syncthreads();
-    const int n_new = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int n_new = block_reduce<SRCH_THREADS / 64>(mine, BlockSum(), wsum);
     if (n_new == 0) return;      // block-uniform: the list stands
     const int total = n_new + n_old;
 
@@ -138,7 +133,7 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_select_kernel(SelectArgs p)
             for (int n = tid; n < nd; n += SRCH_THREADS) {
                 const float s = srow[n];
                 if (s != s) continue;
-                const unsigned long long key = srch_key(s, p.row0 + (unsigned)n);
+                const unsigned long long key = rank_key(s + 0.0f, p.row0 + (unsigned)n);
                 if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255ull)], 1);
             }
             for (int i = tid; i < n_old; i += SRCH_THREADS) {
@@ -173,48 +168,21 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_select_kernel(SelectArgs p)
         unsigned long long key = 0ull;
         if (n < nd) {
             const float s = srow[n];
-            if (s == s) key = srch_key(s, p.row0 + (unsigned)n);
+            if (s == s) key = rank_key(s + 0.0f, p.row0 + (unsigned)n);
         }
-        const bool sel = key != 0ull && key >= thr;
-        const unsigned long long bal = __ballot(sel);
-        if (bal != 0ull) {
-            int at = 0;
-            if (lane == 0) at = atomicAdd(&fill, (int)__popcll(bal));
-            at = __shfl(at, 0);
-            at += (int)__popcll(bal & ((1ull << lane) - 1ull));
-            if (sel && at < SRCH_MAX_K) surv[at] = key;
-        }
+        wave_append(key != 0ull && key >= thr, key, surv, &fill, SRCH_MAX_K);
     }
     for (int base = wid * 64; base < n_old; base += SRCH_THREADS) {
         const int i = base + lane;
         const unsigned long long key = i < n_old ? old_[i] : 0ull;
-        const bool sel = key != 0ull && key >= thr;
-        const unsigned long long bal = __ballot(sel);
-        if (bal != 0ull) {
-            int at = 0;
-            if (lane == 0) at = atomicAdd(&fill, (int)__popcll(bal));
-            at = __shfl(at, 0);
-            at += (int)__popcll(bal & ((1ull << lane) - 1ull));
-            if (sel && at < SRCH_MAX_K) surv[at] = key;
-        }
+        wave_append(key != 0ull && key >= thr, key, surv, &fill, SRCH_MAX_K);
     }
     __syncthreads();
     int np2 = 2;
     while (np2 < n_keep) np2 <<= 1;
     for (int i = n_keep + tid; i < np2; i += SRCH_THREADS) surv[i] = 0ull;
     __syncthreads();
-    for (int size = 2; size <= np2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (np2 >> 1); t += SRCH_THREADS) {
-                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const unsigned long long x = surv[i], y = surv[j];
-                if ((x < y) == ((i & size) == 0)) {
-                    surv[i] = y;
-                    surv[j] = x;
-                }
-            }
-            __syncthreads();
-        }
+    block_bitonic_sort<SRCH_THREADS>(surv, np2, [](unsigned long long a, unsigned long long b) { return a > b; });      // descending
     for (int i = tid; i < kp; i += SRCH_THREADS) list[i] = i < n_keep ? surv[i] : 0ull;
 }
 
@@ -248,8 +216,8 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_finish_kernel(FinishArgs p)
 
     for (int i = tid; i < kp; i += SRCH_THREADS) {
         const unsigned long long key = list[i];
-        const long long row = key != 0ull ? (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)) : -1ll;
-        const bool meta = row >= 0 && row < p.n_rows && p.d_rec != nullptr;
+        const long long row = (long long)rank_key_index(key);
+        const bool meta = key != 0ull && row < p.n_rows && p.d_rec != nullptr;
         c_rec[i] = meta ? p.d_rec[row] : -1;
         c_start[i] = meta ? p.d_start[row] : nan;
         c_end[i] = meta ? p.d_end[row] : nan;
@@ -258,12 +226,7 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_finish_kernel(FinishArgs p)
 
     int n_kept = 0;
     if (!p.nms) {
-        int lo = 0, hi = kp < k ? kp : k;            // the entries are a prefix: the first index holding 0, by a search every thread makes
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (list[mid] != 0ull) lo = mid + 1; else hi = mid;
-        }
-        n_kept = lo;
+        n_kept = srch_entries(list, kp < k ? kp : k);
         for (int i = tid; i < n_kept; i += SRCH_THREADS) kept[i] = (short)i;
     } else {
         // best first: a candidate falls when a hit already kept is of its recording and overlaps it by more than max_overlap x the shorter
@@ -298,9 +261,8 @@ __global__ __launch_bounds__(SRCH_THREADS) void srch_finish_kernel(FinishArgs p)
         if (j < n_kept) {
             const int c = kept[j];
             const unsigned long long key = list[c];
-            const unsigned u = (unsigned)(key >> 32);
-            p.scores[o] = __uint_as_float((u >> 31) ? u ^ 0x80000000u : ~u);
-            p.rows[o] = (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+            p.scores[o] = rank_key_value(key);
+            p.rows[o] = (int64_t)rank_key_index(key);
             p.rec[o] = c_rec[c];
             p.start[o] = c_start[c];
             p.end[o] = c_end[c];

@@ -24,6 +24,7 @@
 //
 // The symmetry of the distance matrix is not used: every pair is computed twice.
 // Limits: n <= 524288, n_labels <= 4096.
+#include "block_prims.h"
 #include "f32_tile.h"
 
 namespace {
@@ -78,9 +79,7 @@ __global__ __launch_bounds__(256) void sil_gather_kernel(const float* __restrict
     }
     float nrm = 1.f;
     if (cosine) {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) ss += __shfl_xor(ss, s);
-        nrm = __builtin_sqrtf(ss);
+        nrm = __builtin_sqrtf(wave_sum(ss));
         nrm = nrm < 1e-12f ? 1e-12f : nrm;
     }
     for (int c = lane; c < dpad; c += 64) o[c] = c < d ? (cosine ? r[c] / nrm : r[c]) : 0.f;
@@ -244,14 +243,9 @@ __global__ __launch_bounds__(256) void sil_mean_kernel(const double* __restrict_
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int i = tid; i < n; i += 256) s += samples[i];
-    red[tid] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
+    const double tot = block_tree_sum<256>(s, red);
     if (tid == 0) {
-        summary[0] = red[0] / (double)n;
+        summary[0] = tot / (double)n;
         summary[1] = nonfinite[0] == 0 ? 1.0 : 0.0;
     }
 }

@@ -50,12 +50,7 @@ __global__ __launch_bounds__(256) void wavconv0_moments_kernel(const float* __re
     }
     // wave sums (xor butterflies: every lane ends with the same value), then the four waves in a fixed order
 #pragma unroll
-    for (int i = 0; i < WC_NM; ++i) {
-        double v = m[i];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-        m[i] = v;
-    }
+    for (int i = 0; i < WC_NM; ++i) m[i] = wave_reduce(m[i], BlockSum());
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int i = 0; i < WC_NM; ++i) red[tid >> 6][i] = m[i];

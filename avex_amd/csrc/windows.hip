@@ -70,9 +70,7 @@ __global__ __launch_bounds__(kWinThreads) void window_stats_kernel(const float* 
         for (int e = 0; e < 4; ++e) v[e] = j0 + e < valid ? src[j0 + e] : 0.f;
         see(v);
     }
-    double s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);  // a + b == b + a bit for bit: every lane ends with the same sum
+    const double s = wave_reduce((acc[0] + acc[1]) + (acc[2] + acc[3]), BlockSum());
     mx = wave_max(mx);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { wave_sum_d[wave] = s; wave_max_f[wave] = mx; }

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Do two builds of libavexhip.so compute the same thing?
 
-    python scripts/ab_outputs.py LIB_A LIB_B [--timeout SECONDS]
+    python scripts/ab_outputs.py LIB_A LIB_B [--set forwards|analytics] [--timeout SECONDS]
 
-Runs one fixed set of small forwards under each library -- a fresh child process per library (AVEX_AMD_LIB), one after the other, each
+Runs one fixed set of small forwards (or, with --set analytics, of small calls of the analytics modules) under each library -- a fresh child process per library (AVEX_AMD_LIB), one after the other, each
 under its own time limit; the first child that fails ends the run -- and compares every output array with np.array_equal, every
 last_profile() name list and every BeatsGraph.nodes.  For refactors of host code (launchers, layer loops): the second library is usually
 a build of the parent commit (AVEX_AMD_LIB_SUFFIX=parent python -m avex_amd.build in a worktree of it).
@@ -13,6 +13,11 @@ The set takes the smallest shapes that reach every branch of the layer loops and
 (4 464 rows: over the fold threshold), both residual streams, batch-invariant, unpooled and pooled hooks with and without padding, graph
 captures, the loop-shape variants of synth.BEATS_VARIANTS, EAT (513 tokens: nine-tile attention + tail), AVES, EfficientNet-B0 behind the
 mel plan with taps, the probes on the stack handle, and tests/test_gpu_source_build.py's FORWARD set.  Exit status 0: everything equal.
+
+The analytics set calls the public functions of search, retrieval, examples, clustering (k-means, scores, silhouette), density and activity
+on seeded NumPy inputs, at the smallest shapes that reach every shared block of their kernels (block_prims.h, the rank key of f32_tile.h):
+tied keys through all eight radix passes, lists deeper than a chunk, the chunked rank sort, relocation through several empty clusters,
+floor ranks on tied and NaN energies.  For refactors of those kernels; it finishes in seconds.
 """
 import argparse
 import json
@@ -137,15 +142,88 @@ def child(out_path: str) -> None:
         json.dump(dict(lib=_capi.LIB_PATH, profiles=profiles, nodes=nodes), f)
 
 
+def child_analytics(out_path: str) -> None:
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _retrieval_ref as RR
+    from avex_amd import _capi, activity, clustering, density, examples, recordings, retrieval, search
+
+    arrays = {}
+
+    def keep(tag, out):
+        for k, v in (out.items() if isinstance(out, dict) else enumerate(out)):
+            if isinstance(v, torch.Tensor):
+                arrays[f"{tag}.{k}"] = v.cpu().numpy()
+            elif isinstance(v, (bool, int, float, str, np.generic, np.ndarray)):
+                arrays[f"{tag}.{k}"] = np.asarray(v)
+            elif v is not None:                                  # nothing a function returns goes uncompared without notice
+                raise TypeError(f"{tag}.{k}: a {type(v).__name__} is neither a tensor, an array nor a scalar")
+
+    rng = np.random.default_rng(23)
+    # ---- search: 300 rows in chunks of 128 (three merges); rows 100..163 are row 7 again: keys that tie in their high word ----
+    rows = rng.standard_normal((300, 40)).astype(np.float32)
+    rows[100:164] = rows[7]
+    q = rng.standard_normal((5, 40)).astype(np.float32)
+    q[0] = rows[7]
+    ix = search.EmbeddingIndex(40, metric="cosine", chunk_rows=128)
+    start = (np.arange(300) % 50) * 0.25
+    ix.add(rows, recording=(np.arange(300) // 50).astype(np.int32), start_s=start, end_s=start + 1.0)
+    keep("search.k8.nms", ix.search(q, 8, nms=0.5))
+    keep("search.k8", ix.search(q, 8))
+    keep("search.k300", ix.search(q, 300))                       # deeper than a chunk: every key survives (total <= kp)
+    # ---- retrieval: self-set and cross-set, and the chunk-threshold shape (chunked sort, count_below) ----
+    lab = rng.integers(0, 4, size=300)
+    keep("retrieval.self", retrieval.retrieval_stats(rows, lab, k=5))
+    keep("retrieval.cross", retrieval.retrieval_stats(q, lab[:5], rows, lab, k=5))
+    cq, cqi, cdb, cdi = RR.chunked_case(n0=16385, d=8, per_class=1)
+    keep("retrieval.chunked", retrieval.retrieval_stats(cq, cqi, cdb, cdi, k=5))
+    # ---- examples: classes of 5, 17 and 130 rows (one and two tiles) and a background, margin mode, nearest ----
+    bank = examples.ExampleBank(40)
+    blab = np.concatenate([np.repeat(np.arange(3), (5, 17, 130)), np.full(11, -1)])
+    order = rng.permutation(len(blab))
+    bank.add(rng.standard_normal((len(blab), 40)).astype(np.float32), blab[order])
+    eq = rng.standard_normal((9, 40)).astype(np.float32)
+    keep("examples.margin", bank.score(eq, top_m=3, mode="margin", return_nearest=True))
+    keep("examples.similarity", bank.score(eq, top_m=3, return_nearest=True))
+    # ---- clustering: 3 distinct points for 12 clusters (relocation through several empties), the scores of two label vectors ----
+    pts = rng.standard_normal((3, 16)).astype(np.float32)
+    keep("kmeans", clustering.kmeans(pts[rng.integers(0, 3, size=200)], 12, n_init=2))
+    keep("clustering_scores", clustering.clustering_scores(rng.integers(0, 5, size=200), rng.integers(0, 7, size=200)))
+    # ---- density, silhouette ----
+    dx = (rng.standard_normal((6, 33))[rng.integers(0, 6, size=257)] + 0.05 * rng.standard_normal((257, 33))).astype(np.float32)
+    keep("dbscan.cosine", density.dbscan(dx, 0.01, 4, metric="cosine"))
+    keep("dbscan.euclidean", density.dbscan(dx, 0.6, 4, metric="euclidean"))
+    sx, sl = rng.standard_normal((200, 16)).astype(np.float32), rng.integers(0, 5, size=200)
+    for metric in ("euclidean", "cosine"):
+        arrays[f"silhouette.{metric}.samples"] = clustering.silhouette_samples(sx, sl, metric=metric).cpu().numpy()
+        arrays[f"silhouette.{metric}.score"] = np.asarray(clustering.silhouette_score(sx, sl, metric=metric))
+    # ---- activity: 3 s at 16 kHz with a silent second (ties at key 0) and one NaN sample; the floor at three ranks ----
+    wav = (0.01 * rng.standard_normal(48000)).astype(np.float32)
+    wav[16000:32000] = 0.0
+    wav[40000] = np.nan
+    ws = recordings.RecordingWindows([torch.from_numpy(wav).cuda()], 16000, 8000, 4000)
+    for pct in (0.0, 20.0, 100.0):
+        act = activity.band_activity(ws, activity.ActivityGate([(500, 2000), (2000, 8000)], hop=160, floor_percentile=pct))
+        keep(f"activity.p{pct:g}", dict(frame_energy=act.frame_energy, floor=act.floor, nonfinite=act.nonfinite_frames, n_frames=act.n_frames,
+                                        active=act.active_frames, max_energy=act.max_energy, kept=act.select()))
+    torch.cuda.synchronize()
+    np.savez(out_path, **arrays)
+    with open(out_path + ".json", "w") as f:
+        json.dump(dict(lib=_capi.LIB_PATH, profiles={}, nodes={}), f)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("lib_a")
     ap.add_argument("lib_b")
+    ap.add_argument("--set", choices=("forwards", "analytics"), default="forwards", help="which fixed set to run")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--child", metavar="OUT", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        child(a.child)
+        (child if a.set == "forwards" else child_analytics)(a.child)
         return 0
     import numpy as np
     res = []
@@ -156,7 +234,7 @@ def main() -> int:
             env = dict(os.environ, AVEX_AMD_LIB=lib)
             env.pop("AVEX_AMD_LIB_SUFFIX", None)
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--child", out], env=env, timeout=a.timeout)
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--set", a.set, "--child", out], env=env, timeout=a.timeout)
             except subprocess.TimeoutExpired:
                 print(f"ab_outputs: the run under {lib} did not finish in {a.timeout} s; stopping")
                 return 3
