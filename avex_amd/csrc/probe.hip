@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void layer_mix_kernel(MixArgs a, int64_t n, fl
 constexpr int DT = 128, DK = 16, DLD = DT + 4;
 
 __device__ __forceinline__ float probe_act(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.f);
+    if (act == 1) return v < 0.f ? 0.f : v;      // not fmaxf(v, 0): that is 0 for a NaN, and torch.relu keeps it
     if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
     if (act == 3) return tanhf(v);
     return v;

@@ -219,8 +219,10 @@ def test_sequence_probes_match_reference_goldens(built_lib, golden_dir):
 
 @pytest.mark.parametrize("B,T,D,H", [(5, 496, 64, 128), (6, 64, 96, 256), (3, 48, 64, 320), (2, 24, 64, 576), (5, 40, 64, 300), (3, 30, 32, 100)])
 def test_lstm_layer_long_sequence(built_lib, B, T, D, H):
-    """The recurrence kernel at the probe's real length (496 steps) and in its three thread layouts (four / two / one thread per hidden unit:
-    H <= 256, <= 512, <= 1024), batches that are no multiple of the clips per workgroup, both directions, against torch.nn.LSTM in fp64."""
+    """The recurrence kernel at the probe's real length (496 steps) and in its four thread layouts (four / three / two / one thread per hidden
+    unit: H <= 256, <= 341, <= 512, <= 1024), both directions, against torch.nn.LSTM in fp64.  With six clips at the most every launch here
+    runs ONE clip per workgroup; two and four clips per workgroup, and clip counts that are no multiple of them, are in
+    test_gpu_probe_kernels.py."""
     from avex_amd import kernels as K
     torch.manual_seed(3)
     lstm = torch.nn.LSTM(D, H, batch_first=True, bidirectional=True).double().eval()
