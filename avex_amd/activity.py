@@ -26,30 +26,23 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _capi
 from ._capi import check, lib
+from ._frames import N_BINS, N_FFT, _number, _tables_on, _to_device, frame_count, recording_table, tables      # noqa: F401 (names callers find here)
 
 __all__ = ["ActivityGate", "BandActivity", "band_activity", "band_bins", "frame_count", "window_frames", "N_FFT", "MAX_BANDS"]
 
-N_FFT = 512
-N_BINS = N_FFT // 2 + 1
 MAX_BANDS = 8                             # AVEXHIP_ACTIVITY_MAX_BANDS
 MIN_HOP = 32                              # AVEXHIP_ACTIVITY_MIN_HOP
 BLOCK_FRAMES = 8                          # frames per workgroup of avexhip_activity_frames (avexhip_activity_recording.first_block)
 MODES = ("any", "all")                    # AVEXHIP_ACTIVITY_ANY, AVEXHIP_ACTIVITY_ALL
 # avexhip_activity_recording, field for field
 RECORDING_DTYPE = np.dtype([("base", "<i8"), ("n_samples", "<i8"), ("first_frame", "<i8"), ("first_block", "<i4"), ("floor_rank", "<i4")])
-
-
-def _number(x: Any, what: str) -> float:
-    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)):
-        raise ValueError(f"{what}={x!r}: a finite number expected")
-    return float(x)
 
 
 @dataclass(frozen=True)
@@ -130,38 +123,12 @@ def band_bins(bands, sr: int) -> np.ndarray:
     return out
 
 
-def frame_count(n_samples: int, hop: int) -> int:
-    return 0 if n_samples < N_FFT else (int(n_samples) - N_FFT) // int(hop) + 1
-
-
 def window_frames(start: int, valid: int, hop: int) -> Tuple[int, int]:
     """``(f_lo, n_frames)`` of a window: the frames that lie wholly inside ``[start, start + valid)``."""
     f_lo = -(-int(start) // int(hop))
     end = int(start) + int(valid) - N_FFT
     f_hi = -1 if end < 0 else end // int(hop)
     return f_lo, max(0, f_hi - f_lo + 1)
-
-
-def tables() -> np.ndarray:
-    """float32 ``[1536]``: the periodic Hann window, then the pairs ``(cos, -sin)(2 pi k / 512)``, computed in float64 and rounded."""
-    a = 2.0 * np.pi * np.arange(N_FFT, dtype=np.float64) / N_FFT
-    tw = np.stack([np.cos(a), -np.sin(a)], axis=1).reshape(-1)
-    return np.concatenate([0.5 - 0.5 * np.cos(a), tw]).astype(np.float32)
-
-
-_TABLES: Dict[torch.device, torch.Tensor] = {}
-
-
-def _tables_on(dev: torch.device) -> torch.Tensor:
-    if dev not in _TABLES:                # once per device, a blocking copy: every stream that comes later finds the table there
-        _TABLES[dev] = torch.from_numpy(tables()).to(dev)
-    return _TABLES[dev]
-
-
-def _to_device(a: np.ndarray, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """A host array -> (its pinned copy, the device copy in flight); the caller keeps the pinned one until the stream has passed."""
-    pinned = torch.from_numpy(a.view(np.uint8).reshape(-1)).pin_memory()
-    return pinned, pinned.to(dev, non_blocking=True)
 
 
 class BandActivity:
@@ -179,23 +146,16 @@ class BandActivity:
         self.bins = gate.bins(ws.sr)
         dev = ws.wav.device
         n_rec, n_bands, n_win, hop = len(ws.ranges), len(self.bins), ws.n_windows, gate.hop
-        first = np.asarray([w0 for w0, _ in ws.ranges], dtype=np.int64)
-        self._rec = np.zeros(n_rec, dtype=RECORDING_DTYPE)
-        self._rec["base"], self._rec["n_samples"] = ws._table["base"][first], ws._table["n_samples"][first]
-        counts = np.asarray([frame_count(int(n), hop) for n in self._rec["n_samples"]], dtype=np.int64)
-        ends = np.cumsum(counts)
-        self._rec["first_frame"] = ends - counts
+        self._rec, counts = recording_table(ws, RECORDING_DTYPE, hop)
         blocks = (counts + BLOCK_FRAMES - 1) // BLOCK_FRAMES
-        self._rec["first_block"] = np.cumsum(blocks) - blocks
-        self._rec["floor_rank"] = [gate.floor_rank(int(c)) for c in counts]
-        self.total_frames = int(ends[-1])
-        self.frame_ranges: List[Tuple[int, int]] = [(int(e - c), int(e)) for c, e in zip(counts, ends)]
+        self._rec["first_block"], self._rec["floor_rank"] = np.cumsum(blocks) - blocks, [gate.floor_rank(int(c)) for c in counts]
+        self.total_frames = int(counts.sum())
+        self.frame_ranges: List[Tuple[int, int]] = [(int(f), int(f + c)) for f, c in zip(self._rec["first_frame"], counts)]
         self._win_rec = np.ascontiguousarray(ws.recording, dtype=np.int32)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             self._pinned_rec, self._rec_dev = _to_device(self._rec, dev)
             self._pinned_win_rec, self._win_rec_dev = _to_device(self._win_rec, dev)
-            tab = _tables_on(dev)
             self.frame_energy = torch.empty((n_bands, self.total_frames), dtype=torch.float32, device=dev)
             self.floor = torch.empty((n_rec, n_bands), dtype=torch.float32, device=dev)
             self.nonfinite_frames = torch.empty(n_rec, dtype=torch.int32, device=dev)
@@ -204,8 +164,8 @@ class BandActivity:
             self.max_energy = torch.empty((n_win, n_bands), dtype=torch.float32, device=dev)
             energy_ptr = self.frame_energy.data_ptr() if self.total_frames else None
             rec_host, rec_dev = self._rec.ctypes.data, self._rec_dev.data_ptr()
-            check(lib().avexhip_activity_frames(ws.wav.data_ptr(), ws.wav.numel(), rec_host, rec_dev, n_rec, hop, self.bins.ctypes.data, n_bands, tab.data_ptr(),
-                                                self.total_frames, energy_ptr, stream), "activity_frames")
+            check(lib().avexhip_activity_frames(ws.wav.data_ptr(), ws.wav.numel(), rec_host, rec_dev, n_rec, hop, self.bins.ctypes.data, n_bands,
+                                                _tables_on(dev).data_ptr(), self.total_frames, energy_ptr, stream), "activity_frames")
             check(lib().avexhip_activity_floor(energy_ptr, self.total_frames, rec_host, rec_dev, n_rec, hop, n_bands, self.floor.data_ptr(),
                                                self.nonfinite_frames.data_ptr(), stream), "activity_floor")
             check(lib().avexhip_activity_count(ws._table.ctypes.data, ws._table_dev.data_ptr(), self._win_rec.ctypes.data, self._win_rec_dev.data_ptr(), n_win,

@@ -5,23 +5,22 @@
 //                            on the bit patterns (energies are >= +0, so the patterns order like the numbers; NaN sorts above +Inf)
 //   activity_count_kernel    per (window, band) the frames with E > max(floor, floor_min) * ratio, and the largest energy
 //   activity_select_kernel   window_select_kernel's condition and one more on those counts, through the same block_compact (block_prims.h)
-// The transform is shared with fbank.hip (fft512.h): one wave64 per PAIR of frames packed as z = a + i b, three register-resident radix-8
-// passes exchanged through a per-wave LDS buffer at row stride 72.  A workgroup takes eight consecutive frames of ONE recording and stages their span
-// ((8 - 1) hop + 512 samples) in LDS once, so overlapping frames cost one HBM read per sample; pairs are (2 i, 2 i + 1) of the recording,
-// so a frame's energies depend on its recording and the hop alone.  Every read is at base + j with j < n_samples of a recording the
-// entry point has checked against the buffer.
+// The transform is shared with fbank.hip (fft512.h): one wave64 per PAIR of frames packed as z = a + i b.  The walk over the frames is
+// shared with soundscape.hip (rec_frames.h: the frame count, the workgroup's recording, the span and twiddle staging, the refusals of
+// a recording, a hop and a bin band): a workgroup takes eight consecutive frames of ONE recording and stages their span ((8 - 1) hop +
+// 512 samples) in LDS once, so overlapping frames cost one HBM read per sample; pairs are (2 i, 2 i + 1) of the recording, so a frame's
+// energies depend on its recording and the hop alone.
 #include <math.h>
 
 #include "block_prims.h"
 #include "common.h"
 #include "fft512.h"
+#include "rec_frames.h"
 
 namespace {
 
-constexpr int kActFrame = 512;                   // n_fft, fixed
 constexpr int kActBlockFrames = 8;               // frames per workgroup of the frames kernel: four waves, a pair each
-constexpr int kActSpan = (kActBlockFrames - 1) * 512 + kActFrame + 8;      // floats of LDS for the span at hop 512, up to 3 lead-in samples, a whole last chunk
-constexpr int kActBins = 257;
+constexpr int kActSpan = (kActBlockFrames - 1) * 512 + kRecFrame + 8;      // floats of LDS for the span at hop 512, up to 3 lead-in samples, a whole last chunk
 constexpr int kFloorThreads = 1024;
 constexpr int kActSelectThreads = 1024;
 
@@ -29,8 +28,6 @@ struct ActBands {
     int n;
     int lo[AVEXHIP_ACTIVITY_MAX_BANDS], hi[AVEXHIP_ACTIVITY_MAX_BANDS];      // bins lo .. hi - 1
 };
-
-__host__ __device__ __forceinline__ int64_t act_frames_of(int64_t n_samples, int hop) { return n_samples < kActFrame ? 0 : (n_samples - kActFrame) / hop + 1; }
 
 // grid: one workgroup per eight frames of a recording (avexhip_activity_recording::first_block numbers them), 256 threads.
 // tables: [512] window, then [512] (cos, -sin)(2 pi k / 512).
@@ -42,37 +39,15 @@ __global__ __launch_bounds__(256) void activity_frames_kernel(const float* __res
     __shared__ float2 tw[512];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the recording of this workgroup: the last one whose first_block is <= blockIdx.x (recordings without a frame share their successor's)
-    int lo = 0, hi = n_rec - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rec[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const avexhip_activity_recording it = rec[lo];
-    const int64_t F = act_frames_of(it.n_samples, hop);
+    const avexhip_activity_recording it = rec[last_at_most(n_rec, (int)blockIdx.x, [&](int i) { return rec[i].first_block; })];
+    const int64_t F = frames_of(it.n_samples, hop);
     const int64_t f0 = (int64_t)((int)blockIdx.x - it.first_block) * kActBlockFrames;
     if (f0 >= F) return;                                         // (block-uniform; the entry point launches no such workgroup)
     const int nf = F - f0 < kActBlockFrames ? (int)(F - f0) : kActBlockFrames;
 
-    // ---- the span of the workgroup's frames -> LDS, 16 bytes per lane wherever a whole aligned chunk lies inside the recording -----
-    const int64_t s0 = it.base + f0 * hop;                       // first sample, counted in wav
-    const int64_t a0 = s0 & ~(int64_t)3;                         // wav is 16-byte aligned (checked on the host)
-    const int lead = (int)(s0 - a0);
-    const int len = lead + (nf - 1) * hop + kActFrame;           // <= 3 + 7 * 512 + 512
-    const int64_t r_lo = it.base, r_hi = it.base + it.n_samples;
-    for (int c = threadIdx.x * 4; c < len; c += 256 * 4) {
-        const int64_t i = a0 + c;
-        f32x4 q;
-        if (i >= r_lo && i + 4 <= r_hi) {
-            q = *(const f32x4*)(wav + i);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = (i + e >= r_lo && i + e < r_hi) ? wav[i + e] : 0.f;
-        }
-        *(f32x4*)(span + c) = q;
-    }
-    const float2* twg = (const float2*)(tables + kActFrame);
-    tw[threadIdx.x] = twg[threadIdx.x];
-    tw[threadIdx.x + 256] = twg[threadIdx.x + 256];
+    // ---- the span of the workgroup's frames -> LDS: lead <= 3, (nf - 1) hop + 512 <= 7 * 512 + 512 -----------------------------------------
+    const int lead = stage_span(span, wav, it.base + f0 * hop, (nf - 1) * hop + kRecFrame, it.base, it.base + it.n_samples);
+    stage_twiddles(tw, tables);
     __syncthreads();
 
     const int fa = 2 * wave;                                     // this wave's pair, counted inside the workgroup
@@ -116,7 +91,7 @@ __global__ __launch_bounds__(256) void activity_frames_kernel(const float* __res
     for (int q = 0; q < 5; ++q) {
         const int k = lane + 64 * q;
         pa[q] = 0.f; pb[q] = 0.f;
-        if (k < kActBins) {
+        if (k < kRecBins) {
             const float2 zk = z[k], zn = z[(512 - k) & 511];
             const float ar = 0.5f * (zk.x + zn.x), ai = 0.5f * (zk.y - zn.y);
             const float br = 0.5f * (zk.y + zn.y), bi = -0.5f * (zk.x - zn.x);
@@ -155,7 +130,7 @@ __global__ __launch_bounds__(kFloorThreads) void activity_floor_kernel(const flo
     __shared__ int sel_digit, sel_below, bad_total;
     const int tid = threadIdx.x, r = blockIdx.x, b = blockIdx.y;
     const avexhip_activity_recording it = rec[r];
-    const int F = (int)act_frames_of(it.n_samples, hop);         // < 2^31 (checked on the host)
+    const int F = (int)frames_of(it.n_samples, hop);         // < 2^31 (checked on the host)
     if (F == 0) {                                                // (block-uniform)
         if (tid == 0) {
             floor_out[(int64_t)r * n_bands + b] = NAN;
@@ -226,7 +201,7 @@ __global__ __launch_bounds__(64) void activity_count_kernel(const avexhip_window
     const int r = win_rec[w];
     const int64_t first = rec[r].first_frame;
     const int64_t f_lo = (it.start + hop - 1) / hop;
-    const int64_t end = it.start + it.valid - kActFrame;
+    const int64_t end = it.start + it.valid - kRecFrame;
     const int64_t f_hi = end < 0 ? -1 : end / hop;
     const int nf = f_hi >= f_lo ? (int)(f_hi - f_lo + 1) : 0;
     if (lane == 0) n_frames[w] = nf;
@@ -270,14 +245,12 @@ int activity_recordings_check(const char* what, const avexhip_activity_recording
     AVX_REQUIRE(rec_host && rec_dev, "%s: null argument", what);
     AVX_REQUIRE(((uintptr_t)rec_dev & 7) == 0, "%s: rec_dev must be 8-byte aligned", what);
     AVX_REQUIRE(n_rec >= 1, "%s: n_rec=%d", what, n_rec);
-    AVX_REQUIRE(hop >= AVEXHIP_ACTIVITY_MIN_HOP && hop <= kActFrame, "%s: hop=%d outside %d..%d", what, hop, AVEXHIP_ACTIVITY_MIN_HOP, kActFrame);
+    AVXH_TRY(hop_check(what, hop));
     int64_t frames = 0, blocks = 0;
     for (int r = 0; r < n_rec; ++r) {
         const avexhip_activity_recording& it = rec_host[r];
-        AVX_REQUIRE(it.n_samples >= 1 && it.base >= 0, "%s: recording %d: %lld samples at %lld", what, r, (long long)it.n_samples, (long long)it.base);
-        AVX_REQUIRE(wav_samples < 0 || it.base <= wav_samples - it.n_samples, "%s: recording %d: %lld samples at %lld leave the buffer's %lld samples", what, r,
-                    (long long)it.n_samples, (long long)it.base, (long long)wav_samples);
-        const int64_t F = act_frames_of(it.n_samples, hop);
+        AVXH_TRY(recording_check(what, r, it.n_samples, it.base, wav_samples));
+        const int64_t F = frames_of(it.n_samples, hop);
         AVX_REQUIRE(it.first_frame == frames && (int64_t)it.first_block == blocks, "%s: recording %d: first_frame=%lld first_block=%d, expected %lld and %lld", what, r,
                     (long long)it.first_frame, it.first_block, (long long)frames, (long long)blocks);
         AVX_REQUIRE(it.floor_rank >= 0 && (int64_t)it.floor_rank < (F > 0 ? F : 1), "%s: recording %d: floor_rank=%d outside its %lld frames", what, r, it.floor_rank,
@@ -312,8 +285,7 @@ extern "C" int avexhip_activity_frames(const float* wav_dev, int64_t wav_samples
     for (int b = 0; b < n_bands; ++b) {
         bands.lo[b] = bands_host[2 * b];
         bands.hi[b] = bands_host[2 * b + 1];
-        AVX_REQUIRE(bands.lo[b] >= 0 && bands.lo[b] < bands.hi[b] && bands.hi[b] <= kActBins, "activity_frames: band %d: bins %d..%d outside 0 <= lo < hi <= %d", b,
-                    bands.lo[b], bands.hi[b], kActBins);
+        AVXH_TRY(bin_band_check("activity_frames", "band", b, bands.lo[b], bands.hi[b]));
     }
     int64_t blocks = 0;
     AVXH_TRY(activity_recordings_check("activity_frames", rec_host, rec_dev, n_rec, hop, wav_samples, total_frames, &blocks));

@@ -8,6 +8,11 @@
 //   kernel[p][j] = sinc(t) * window(t) * base / orig,   t = ((j - width) / orig - p / new) * base  clamped to +-lowpass_width
 //   out[q * new + p] = sum_j kernel[p][j] * x[q * orig + j - width]   (zero outside the clip),   length ceil(new * T / orig)
 // PARITY UNPINNED against torchaudio (absent from both machines); the checker is oracle/ingest_oracle.py.
+//
+// Every arithmetic chain is written once and called by the per-file kernel and by the batched one, which is what makes a row of
+// avexhip_ingest_batch the bits of the per-file path: pcm_mono_sample (decode, channel mean), sinc_stage + sinc_taps (the polyphase
+// filter), interp_wings (resampy's two filter wings).  The kernels differ in which inputs a workgroup stages and in what lies behind a
+// clip's end.  A plan is one ResamplePlan, read by avexhip_resample_forward on the host and, by value in a table, by the batched kernels.
 #include <math.h>
 
 #include <vector>
@@ -16,11 +21,10 @@
 
 namespace {
 
-// interleaved PCM [frames][channels] of the given sample format -> mono fp32 [frames] (mean over channels), normalised like
-// soundfile / torchaudio do for float32 output: int16 / 32768, int24 / 2^23, int32 / 2^31, uint8 (x - 128) / 128
-__global__ __launch_bounds__(256) void pcm_to_mono_kernel(const unsigned char* __restrict__ raw, int fmt, int channels, int64_t frames, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= frames) return;
+// Frame i of interleaved PCM [frames][channels] of the given sample format -> one mono fp32 sample (the channels added in channel order,
+// then divided by their number), normalised like soundfile / torchaudio do for float32 output: int16 / 32768, int24 / 2^23, int32 / 2^31,
+// uint8 (x - 128) / 128; fmt 0 is float32, 64 float64.  `bad` collects non-finite float samples.
+__device__ __forceinline__ float pcm_mono_sample(const unsigned char* __restrict__ raw, int fmt, int channels, int64_t i, bool& bad) {
     float acc = 0.f;
     for (int c = 0; c < channels; ++c) {
         const int64_t e = i * channels + c;
@@ -32,11 +36,34 @@ __global__ __launch_bounds__(256) void pcm_to_mono_kernel(const unsigned char* _
             int s = (int)p[0] | ((int)p[1] << 8) | ((int)(signed char)p[2] << 16);
             v = (float)s * (1.0f / 8388608.0f);
         } else if (fmt == 8) v = ((float)raw[e] - 128.0f) * (1.0f / 128.0f);
-        else if (fmt == 64) v = (float)((const double*)raw)[e];
-        else v = ((const float*)raw)[e];                      // fmt == 0: float32
+        else {
+            v = fmt == 64 ? (float)((const double*)raw)[e] : ((const float*)raw)[e];
+            bad |= non_finite(v);
+        }
         acc += v;
     }
-    out[i] = channels > 1 ? acc / (float)channels : acc;
+    return channels > 1 ? acc / (float)channels : acc;
+}
+
+__global__ __launch_bounds__(256) void pcm_to_mono_kernel(const unsigned char* __restrict__ raw, int fmt, int channels, int64_t frames, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= frames) return;
+    bool bad = false;                                           // (not reported here: a NaN stays a NaN in the output)
+    out[i] = pcm_mono_sample(raw, fmt, channels, i, bad);
+}
+
+// The polyphase sinc filter.  sinc_stage: xs[s] = input sample first + s for s < span, zero outside [lo, hi) (src[k] = sample k of the
+// clip; 256 threads, the caller's barrier follows).  sinc_taps: one output from its table row and its `taps` staged inputs, one fmaf chain.
+__device__ __forceinline__ void sinc_stage(float* xs, int span, int64_t first, const float* __restrict__ src, int64_t lo, int64_t hi) {
+    for (int s = threadIdx.x; s < span; s += 256) {
+        const int64_t k = first + s;
+        xs[s] = (k >= lo && k < hi) ? src[k] : 0.f;
+    }
+}
+__device__ __forceinline__ float sinc_taps(const float* __restrict__ row, const float* xin, int taps) {
+    float acc = 0.f;
+    for (int j = 0; j < taps; ++j) acc = __builtin_fmaf(row[j], xin[j], acc);
+    return acc;
 }
 
 // One workgroup = 256 consecutive output samples of one clip.  The input samples they touch are staged in LDS; the polyphase table
@@ -49,27 +76,48 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
     const int64_t q0 = i0 / newr, q1 = (i0 + 255) / newr;
     const int64_t lo = q0 * orig - width;                       // first input sample any of the 256 outputs reads
     const int span = (int)((q1 - q0) * orig) + taps;
-    const float* src = x + (int64_t)b * x_stride;
-    for (int s = threadIdx.x; s < span; s += 256) {
-        const int64_t j = lo + s;
-        xs[s] = (j >= 0 && j < T) ? src[j] : 0.f;
-    }
+    sinc_stage(xs, span, lo, x + (int64_t)b * x_stride, 0, T);
     __syncthreads();
     const int64_t i = i0 + threadIdx.x;
     if (i >= n_out) return;
     const int64_t q = i / newr;
     const int p = (int)(i - q * newr);
-    const float* row = table + (int64_t)p * taps;
-    const float* xin = xs + (int)((q - q0) * orig);
-    float acc = 0.f;
-    for (int j = 0; j < taps; ++j) acc = __builtin_fmaf(row[j], xin[j], acc);
-    out[(int64_t)b * out_stride + i] = acc;
+    out[(int64_t)b * out_stride + i] = sinc_taps(table + (int64_t)p * taps, xs + (int)((q - q0) * orig), taps);
 }
 
 // resampy's interpolating resampler (librosa.resample(..., res_type="kaiser_best"), birdset_train_splits.py:190-196): output sample t sits
 // at input time t / ratio; its two filter wings walk a half-window table (64 zero crossings x 512 samples each, Kaiser-windowed sinc)
 // in steps of scale * 512 entries, every weight linearly interpolated between neighbouring table entries.  One thread per output
 // sample; table and input through the caches (the table is 128 KB, a wing touches every index_step-th entry of it).
+// interp_wings: output sample t of a clip of T samples at src, before the scaling by `post`.
+__device__ __forceinline__ float interp_wings(const float* __restrict__ src, int64_t T, int64_t t, const float* __restrict__ win, const float* __restrict__ delta,
+                                              int nwin, int num_table, int index_step, double scale, double time_increment) {
+    float acc = 0.f;
+    const double time_register = (double)t * time_increment;
+    const int64_t n = (int64_t)time_register;
+    double frac = scale * (time_register - (double)n);
+    double index_frac = frac * num_table;
+    int offset = (int)index_frac;
+    float eta = (float)(index_frac - offset);
+    int64_t i_max = (nwin - offset) / index_step;
+    i_max = i_max < n + 1 ? i_max : n + 1;
+    for (int64_t i = 0; i < i_max; ++i) {
+        const int k = offset + (int)i * index_step;
+        acc = __builtin_fmaf(__builtin_fmaf(eta, delta[k], win[k]), src[n - i], acc);
+    }
+    frac = scale - frac;
+    index_frac = frac * num_table;
+    offset = (int)index_frac;
+    eta = (float)(index_frac - offset);
+    int64_t k_max = (nwin - offset) / index_step;
+    k_max = k_max < T - n - 1 ? k_max : T - n - 1;
+    for (int64_t k = 0; k < k_max; ++k) {
+        const int q = offset + (int)k * index_step;
+        acc = __builtin_fmaf(__builtin_fmaf(eta, delta[q], win[q]), src[n + k + 1], acc);
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void resample_interp_kernel(const float* __restrict__ x, int64_t T, int64_t x_stride, const float* __restrict__ win,
                                                               const float* __restrict__ delta, int nwin, int num_table, int index_step, double scale,
                                                               double time_increment, int64_t n_res, float post, float* __restrict__ out, int64_t n_out,
@@ -78,47 +126,32 @@ __global__ __launch_bounds__(256) void resample_interp_kernel(const float* __res
     if (t >= n_out) return;
     const int b = blockIdx.y;
     float acc = 0.f;
-    if (t < n_res) {                                            // librosa's fix_length zero-fills beyond resampy's int(T * ratio) samples
-        const float* src = x + (int64_t)b * x_stride;
-        const double time_register = (double)t * time_increment;
-        const int64_t n = (int64_t)time_register;
-        double frac = scale * (time_register - (double)n);
-        double index_frac = frac * num_table;
-        int offset = (int)index_frac;
-        float eta = (float)(index_frac - offset);
-        int64_t i_max = (nwin - offset) / index_step;
-        i_max = i_max < n + 1 ? i_max : n + 1;
-        for (int64_t i = 0; i < i_max; ++i) {
-            const int k = offset + (int)i * index_step;
-            acc = __builtin_fmaf(__builtin_fmaf(eta, delta[k], win[k]), src[n - i], acc);
-        }
-        frac = scale - frac;
-        index_frac = frac * num_table;
-        offset = (int)index_frac;
-        eta = (float)(index_frac - offset);
-        int64_t k_max = (nwin - offset) / index_step;
-        k_max = k_max < T - n - 1 ? k_max : T - n - 1;
-        for (int64_t k = 0; k < k_max; ++k) {
-            const int q = offset + (int)k * index_step;
-            acc = __builtin_fmaf(__builtin_fmaf(eta, delta[q], win[q]), src[n + k + 1], acc);
-        }
-    }
+    // librosa's fix_length zero-fills beyond resampy's int(T * ratio) samples
+    if (t < n_res) acc = interp_wings(x + (int64_t)b * x_stride, T, t, win, delta, nwin, num_table, index_step, scale, time_increment);
     out[(int64_t)b * out_stride + t] = acc * post;
 }
 
 int gcd_i(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
 
-}  // namespace
+// the modified Bessel function I0 by its power series, at most max_terms terms
+double bessel_i0(double z, int max_terms) {
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < max_terms; ++k) { t *= (z / (2.0 * k)) * (z / (2.0 * k)); s += t; if (t < 1e-18 * s) break; }
+    return s;
+}
 
-struct avexhip_resample_plan {
-    int orig = 0, newr = 0, width = 0, taps = 0;
-    float* table = nullptr;
-    // interpolating (resampy) plans: table = [win | delta], each nwin floats
-    bool interp = false;
-    int nwin = 0, num_table = 0, index_step = 0;
-    double ratio = 1.0, scale = 1.0;
+// a plan as host and device read it
+struct ResamplePlan {
+    float* table = nullptr;                    // device memory, owned by the avexhip_resample_plan
+    int orig = 0, newr = 0, width = 0, taps = 0;                 // sinc plans
+    int interp = 0, nwin = 0, num_table = 0, index_step = 0;     // interpolating (resampy) plans: table = [win | delta], each nwin floats
+    double scale = 1.0, time_increment = 1.0, ratio = 1.0;
     float post = 1.f;
 };
+
+}  // namespace
+
+struct avexhip_resample_plan { ResamplePlan d; };
 
 extern "C" avexhip_resample_plan* avexhip_resample_plan_create(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, double kaiser_beta) {
     if (orig_freq <= 0 || new_freq <= 0 || lowpass_filter_width <= 0 || !(rolloff > 0.0 && rolloff <= 1.0)) {
@@ -136,25 +169,23 @@ extern "C" avexhip_resample_plan* avexhip_resample_plan_create(int orig_freq, in
     }
     std::vector<float> tab((size_t)newr * taps);
     const double lpw = (double)lowpass_filter_width;
-    auto bessel_i0 = [](double z) { double s = 1.0, t = 1.0; for (int k = 1; k < 64; ++k) { t *= (z / (2.0 * k)) * (z / (2.0 * k)); s += t; if (t < 1e-18 * s) break; } return s; };
     for (int p = 0; p < newr; ++p)
         for (int j = 0; j < taps; ++j) {
             double t = ((double)(j - width) / orig - (double)p / newr) * base;
             t = t < -lpw ? -lpw : (t > lpw ? lpw : t);
             double w;
-            if (kaiser_beta > 0.0) { const double r = t / lpw; w = bessel_i0(kaiser_beta * sqrt(1.0 - r * r)) / bessel_i0(kaiser_beta); }
+            if (kaiser_beta > 0.0) { const double r = t / lpw; w = bessel_i0(kaiser_beta * sqrt(1.0 - r * r), 64) / bessel_i0(kaiser_beta, 64); }
             else { const double c = cos(t * M_PI / lpw / 2.0); w = c * c; }
             const double a = t * M_PI;
             const double sinc = a == 0.0 ? 1.0 : sin(a) / a;
             tab[(size_t)p * taps + j] = (float)(sinc * w * base / orig);
         }
     avexhip_resample_plan* pl = new avexhip_resample_plan();
-    pl->orig = orig; pl->newr = newr; pl->width = width; pl->taps = taps;
-    if (hipMalloc((void**)&pl->table, sizeof(float) * tab.size()) != hipSuccess ||
-        hipMemcpy(pl->table, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    pl->d.orig = orig; pl->d.newr = newr; pl->d.width = width; pl->d.taps = taps;
+    if (hipMalloc((void**)&pl->d.table, sizeof(float) * tab.size()) != hipSuccess ||
+        hipMemcpy(pl->d.table, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
         avexhip_set_error("resample_plan_create: device allocation failed");
-        if (pl->table) (void)hipFree(pl->table);
-        delete pl;
+        avexhip_resample_plan_destroy(pl);
         return nullptr;
     }
     return pl;
@@ -172,14 +203,13 @@ extern "C" avexhip_resample_plan* avexhip_resample_interp_plan_create(int orig_f
     const int num_bits = 1 << precision;
     const int n = num_bits * num_zeros;
     const double ratio = (double)new_freq / (double)orig_freq;
-    auto bessel_i0 = [](double z) { double s = 1.0, t = 1.0; for (int k = 1; k < 256; ++k) { t *= (z / (2.0 * k)) * (z / (2.0 * k)); s += t; if (t < 1e-18 * s) break; } return s; };
     std::vector<double> w((size_t)n + 1);
-    const double i0b = bessel_i0(kaiser_beta);
+    const double i0b = bessel_i0(kaiser_beta, 256);
     for (int i = 0; i <= n; ++i) {
         const double a = rolloff * (double)num_zeros * (double)i / (double)n;       // rolloff * linspace(0, num_zeros, n + 1)
         const double sinc = a == 0.0 ? 1.0 : sin(M_PI * a) / (M_PI * a);
         const double r = (double)i / (double)n;                                      // kaiser(2 n + 1)[n + i]
-        const double taper = bessel_i0(kaiser_beta * sqrt(1.0 - r * r)) / i0b;
+        const double taper = bessel_i0(kaiser_beta * sqrt(1.0 - r * r), 256) / i0b;
         w[i] = rolloff * sinc * taper * (ratio < 1.0 ? ratio : 1.0);                 // resampy scales the window when it decimates
     }
     std::vector<float> tab(2 * ((size_t)n + 1));
@@ -188,15 +218,15 @@ extern "C" avexhip_resample_plan* avexhip_resample_interp_plan_create(int orig_f
         tab[(size_t)n + 1 + i] = i < n ? (float)(w[i + 1] - w[i]) : 0.f;
     }
     avexhip_resample_plan* pl = new avexhip_resample_plan();
-    pl->interp = true; pl->orig = orig_freq; pl->newr = new_freq; pl->nwin = n + 1; pl->num_table = num_bits;
-    pl->ratio = ratio; pl->scale = ratio < 1.0 ? ratio : 1.0;
-    pl->index_step = (int)(pl->scale * num_bits);
-    pl->post = scale_energy ? (float)(1.0 / sqrt(ratio)) : 1.f;
-    if (pl->index_step < 1 || hipMalloc((void**)&pl->table, sizeof(float) * tab.size()) != hipSuccess ||
-        hipMemcpy(pl->table, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    ResamplePlan& d = pl->d;
+    d.interp = 1; d.orig = orig_freq; d.newr = new_freq; d.nwin = n + 1; d.num_table = num_bits;
+    d.ratio = ratio; d.time_increment = 1.0 / ratio; d.scale = ratio < 1.0 ? ratio : 1.0;
+    d.index_step = (int)(d.scale * num_bits);
+    d.post = scale_energy ? (float)(1.0 / sqrt(ratio)) : 1.f;
+    if (d.index_step < 1 || hipMalloc((void**)&d.table, sizeof(float) * tab.size()) != hipSuccess ||
+        hipMemcpy(d.table, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
         avexhip_set_error("resample_interp_plan_create: %d -> %d Hz: ratio too small for the table, or device allocation failed", orig_freq, new_freq);
-        if (pl->table) (void)hipFree(pl->table);
-        delete pl;
+        avexhip_resample_plan_destroy(pl);
         return nullptr;
     }
     return pl;
@@ -204,21 +234,25 @@ extern "C" avexhip_resample_plan* avexhip_resample_interp_plan_create(int orig_f
 
 extern "C" void avexhip_resample_plan_destroy(avexhip_resample_plan* p) {
     if (!p) return;
-    if (p->table) (void)hipFree(p->table);
+    if (p->d.table) (void)hipFree(p->d.table);
     delete p;
 }
 
 extern "C" int64_t avexhip_resample_out_length(const avexhip_resample_plan* p, int64_t T) {
     if (!p || T <= 0) return 0;
-    if (p->interp) return (int64_t)ceil((double)T * p->ratio);      // librosa: n_samples = ceil(len * ratio), resampy's int(len * ratio) zero-padded up to it
-    return ((int64_t)p->newr * T + p->orig - 1) / p->orig;
+    if (p->d.interp) return (int64_t)ceil((double)T * p->d.ratio);      // librosa: n_samples = ceil(len * ratio), resampy's int(len * ratio) zero-padded up to it
+    return ((int64_t)p->d.newr * T + p->d.orig - 1) / p->d.orig;
 }
 
-extern "C" int avexhip_resample_forward(const avexhip_resample_plan* p, const float* x_dev, int B, int64_t T, int64_t x_stride, float* out_dev,
+// bytes of LDS a workgroup of a sinc plan stages at most
+static size_t sinc_lds_bytes(const ResamplePlan& d) { return sizeof(float) * (size_t)((256 / d.newr + 2) * d.orig + d.taps); }
+
+extern "C" int avexhip_resample_forward(const avexhip_resample_plan* pl, const float* x_dev, int B, int64_t T, int64_t x_stride, float* out_dev,
                                         int64_t out_stride, void* stream) {
-    AVX_REQUIRE(p && x_dev && out_dev, "resample_forward: null argument");
+    AVX_REQUIRE(pl && x_dev && out_dev, "resample_forward: null argument");
     AVX_REQUIRE(B > 0 && T > 0 && B <= 65535, "resample_forward: bad shape B=%d T=%lld", B, (long long)T);
-    const int64_t n_out = avexhip_resample_out_length(p, T);
+    const ResamplePlan* p = &pl->d;
+    const int64_t n_out = avexhip_resample_out_length(pl, T);
     if (x_stride <= 0) x_stride = T;
     if (out_stride <= 0) out_stride = n_out;
     AVX_REQUIRE(B == 1 || x_stride >= T, "resample_forward: x_stride %lld < %lld input samples (rows would overlap)", (long long)x_stride, (long long)T);
@@ -226,14 +260,12 @@ extern "C" int avexhip_resample_forward(const avexhip_resample_plan* p, const fl
     if (p->interp) {
         const int64_t n_res = (int64_t)((double)T * p->ratio);
         hipLaunchKernelGGL(resample_interp_kernel, dim3((unsigned)((n_out + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, x_dev, T, x_stride, p->table,
-                           p->table + p->nwin, p->nwin, p->num_table, p->index_step, p->scale, 1.0 / p->ratio, n_res, p->post, out_dev, n_out, out_stride);
+                           p->table + p->nwin, p->nwin, p->num_table, p->index_step, p->scale, p->time_increment, n_res, p->post, out_dev, n_out, out_stride);
         AVX_LAUNCH_CHECK();
         return AVEXHIP_OK;
     }
-    const int span_max = (256 / p->newr + 2) * p->orig + p->taps;
-    const size_t lds = sizeof(float) * (size_t)span_max;
     AVX_ENSURE_LDS(resample_kernel, 160 * 1024);
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((n_out + 255) / 256), B), dim3(256), lds, (hipStream_t)stream, x_dev, T, x_stride, p->table, p->orig,
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((n_out + 255) / 256), B), dim3(256), sinc_lds_bytes(*p), (hipStream_t)stream, x_dev, T, x_stride, p->table, p->orig,
                        p->newr, p->width, p->taps, out_dev, n_out, out_stride);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
@@ -256,29 +288,22 @@ extern "C" int avexhip_pcm_to_mono_f32(const void* raw_dev, int sample_format, i
 // clips with a NaN / Inf replaced by zeros, a window of the clip or zero padding up to the model length, the padding mask.
 //   ingest_mono_kernel      every item's raw samples -> mono fp32, only the input span its window (and the filter halo) reads;
 //                           float payloads are scanned whole for NaN / Inf (flag per item)
-//   ingest_resample_kernel  row b, sample j = sample start_b + j of the item's full-clip resampling (same fmaf chains as
-//                           resample_kernel / resample_interp_kernel, so the same bits), zeros behind `valid`, the mask, zero rows
-//                           for flagged items
+//   ingest_resample_kernel  row b, sample j = sample start_b + j of the item's full-clip resampling (sinc_stage + sinc_taps or
+//                           interp_wings, the calls resample_kernel / resample_interp_kernel make: the same bits), zeros behind
+//                           `valid`, the mask, zero rows for flagged items
 // ------------------------------------------------------------------------------------------------------------------------
 namespace {
 
 constexpr int kIngestMaxPlans = 16;
 constexpr int kIngestMonoBlocks = 64;          // blocks per item in the mono stage; each walks its item's chunks with this stride
 
-struct IngestPlanDev {
-    const float* table;
-    int orig, newr, width, taps;               // sinc plans
-    int interp, nwin, num_table, index_step;   // interpolating plans
-    double scale, time_increment, ratio;
-    float post;
-};
-struct IngestPlanTable { IngestPlanDev p[kIngestMaxPlans]; };
+struct IngestPlanTable { ResamplePlan p[kIngestMaxPlans]; };
 
 __host__ __device__ inline int ingest_sample_bytes(int fmt) { return fmt == 8 ? 1 : fmt == 16 ? 2 : fmt == 24 ? 3 : fmt == 64 ? 8 : 4; }
 
 // [lo, hi): the mono samples of a clip of T frames that the outputs start .. start + valid - 1 of its resampling read (pl == nullptr:
 // the clip is at the target rate already).  The same integer / double arithmetic as the kernels, so host and device agree.
-__host__ __device__ inline void ingest_span(const IngestPlanDev* pl, int64_t T, int64_t start, int64_t valid, int64_t* lo, int64_t* hi) {
+__host__ __device__ inline void ingest_span(const ResamplePlan* pl, int64_t T, int64_t start, int64_t valid, int64_t* lo, int64_t* hi) {
     int64_t a = 0, b = 0;
     if (valid > 0) {
         const int64_t last = start + valid - 1;
@@ -302,28 +327,6 @@ __host__ __device__ inline void ingest_span(const IngestPlanDev* pl, int64_t T, 
     *lo = a; *hi = b;
 }
 
-// one item's sample i, channels averaged: pcm_to_mono_kernel's arithmetic; `bad` collects non-finite float samples
-__device__ __forceinline__ float ingest_mono_sample(const unsigned char* __restrict__ raw, int fmt, int channels, int64_t i, bool& bad) {
-    float acc = 0.f;
-    for (int c = 0; c < channels; ++c) {
-        const int64_t e = i * channels + c;
-        float v;
-        if (fmt == 16) v = (float)((const short*)raw)[e] * (1.0f / 32768.0f);
-        else if (fmt == 32) v = (float)((const int*)raw)[e] * (1.0f / 2147483648.0f);
-        else if (fmt == 24) {
-            const unsigned char* p = raw + 3 * e;
-            int s = (int)p[0] | ((int)p[1] << 8) | ((int)(signed char)p[2] << 16);
-            v = (float)s * (1.0f / 8388608.0f);
-        } else if (fmt == 8) v = ((float)raw[e] - 128.0f) * (1.0f / 128.0f);
-        else {
-            v = fmt == 64 ? (float)((const double*)raw)[e] : ((const float*)raw)[e];
-            bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;      // exponent all ones: NaN or Inf
-        }
-        acc += v;
-    }
-    return channels > 1 ? acc / (float)channels : acc;
-}
-
 // grid (kIngestMonoBlocks, B).  Integer PCM: the span only.  Float payloads: the whole clip (the NaN / Inf test covers every sample the
 // reference's Collater would see), stores inside the span only.
 __global__ __launch_bounds__(256) void ingest_mono_kernel(const unsigned char* __restrict__ raw, const avexhip_ingest_item* __restrict__ items,
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(256) void ingest_mono_kernel(const unsigned char* _
     float* dst = ws + (int64_t)b * ws_stride;
     bool bad = false;
     for (int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)kIngestMonoBlocks * 256) {
-        const float v = ingest_mono_sample(src, it.sample_format, it.channels, i, bad);
+        const float v = pcm_mono_sample(src, it.sample_format, it.channels, i, bad);
         if (i >= lo && i < hi) dst[i - lo] = v;
     }
     if (bad) flags[b] = 1;                     // every writer stores the same value
@@ -355,7 +358,7 @@ __global__ __launch_bounds__(256) void ingest_resample_kernel(const avexhip_inge
     const int64_t valid = it.valid;
     float acc = 0.f;
     if (j0 < valid && flags[b] == 0) {                              // workgroup-uniform
-        const IngestPlanDev* pl = it.plan >= 0 ? &plans.p[it.plan] : nullptr;
+        const ResamplePlan* pl = it.plan >= 0 ? &plans.p[it.plan] : nullptr;
         int64_t lo, hi;
         ingest_span(pl, it.frames, it.start, valid, &lo, &hi);
         const float* src = ws + (int64_t)b * ws_stride - lo;        // src[k] = mono sample k of the clip, for lo <= k < hi
@@ -369,50 +372,19 @@ __global__ __launch_bounds__(256) void ingest_resample_kernel(const avexhip_inge
             const int64_t q0 = i0 / newr, q1 = ilast / newr;
             const int64_t first = q0 * orig - pl->width;             // first input sample any of the workgroup's outputs reads
             const int span = (int)((q1 - q0) * orig) + taps;
-            for (int s = threadIdx.x; s < span; s += 256) {
-                const int64_t k = first + s;
-                xs[s] = (k >= lo && k < hi) ? src[k] : 0.f;          // [lo, hi) is what [0, T) holds of the reads: zero outside, as resample_kernel
-            }
+            sinc_stage(xs, span, first, src, lo, hi);                // [lo, hi) is what [0, T) holds of the reads: zero outside, as resample_kernel
             __syncthreads();
             if (j < valid) {
                 const int64_t i = it.start + j;
                 const int64_t q = i / newr;
                 const int p = (int)(i - q * newr);
-                const float* row = pl->table + (int64_t)p * taps;
-                const float* xin = xs + (int)((q - q0) * orig);
-                for (int k = 0; k < taps; ++k) acc = __builtin_fmaf(row[k], xin[k], acc);
+                acc = sinc_taps(pl->table + (int64_t)p * taps, xs + (int)((q - q0) * orig), taps);
             }
         } else if (j < valid) {
             const int64_t t = it.start + j;
             const int64_t n_res = (int64_t)((double)T * pl->ratio);
-            if (t < n_res) {
-                const float* win = pl->table;
-                const float* delta = pl->table + pl->nwin;
-                const int nwin = pl->nwin, num_table = pl->num_table, index_step = pl->index_step;
-                const double scale = pl->scale;
-                const double time_register = (double)t * pl->time_increment;
-                const int64_t n = (int64_t)time_register;
-                double frac = scale * (time_register - (double)n);
-                double index_frac = frac * num_table;
-                int offset = (int)index_frac;
-                float eta = (float)(index_frac - offset);
-                int64_t i_max = (nwin - offset) / index_step;
-                i_max = i_max < n + 1 ? i_max : n + 1;
-                for (int64_t i = 0; i < i_max; ++i) {
-                    const int k = offset + (int)i * index_step;
-                    acc = __builtin_fmaf(__builtin_fmaf(eta, delta[k], win[k]), src[n - i], acc);
-                }
-                frac = scale - frac;
-                index_frac = frac * num_table;
-                offset = (int)index_frac;
-                eta = (float)(index_frac - offset);
-                int64_t k_max = (nwin - offset) / index_step;
-                k_max = k_max < T - n - 1 ? k_max : T - n - 1;
-                for (int64_t k = 0; k < k_max; ++k) {
-                    const int q = offset + (int)k * index_step;
-                    acc = __builtin_fmaf(__builtin_fmaf(eta, delta[q], win[q]), src[n + k + 1], acc);
-                }
-            }
+            if (t < n_res)
+                acc = interp_wings(src, T, t, pl->table, pl->table + pl->nwin, pl->nwin, pl->num_table, pl->index_step, pl->scale, pl->time_increment);
             acc = acc * pl->post;
         }
     }
@@ -436,15 +408,10 @@ int ingest_layout(const avexhip_ingest_item* items, int B, const avexhip_resampl
     size_t lds = 0;
     for (int i = 0; i < n_plans; ++i) {
         const avexhip_resample_plan* p = plans[i];
-        AVX_REQUIRE(p && p->table, "ingest_batch: plan %d is null", i);
-        IngestPlanDev& d = L->table.p[i];
-        d.table = p->table; d.orig = p->orig; d.newr = p->newr; d.width = p->width; d.taps = p->taps;
-        d.interp = p->interp ? 1 : 0; d.nwin = p->nwin; d.num_table = p->num_table; d.index_step = p->index_step;
-        d.scale = p->scale; d.time_increment = 1.0 / p->ratio; d.ratio = p->ratio; d.post = p->post;
-        if (!p->interp) {
-            const size_t need = sizeof(float) * (size_t)((256 / p->newr + 2) * p->orig + p->taps);
-            lds = need > lds ? need : lds;
-        }
+        AVX_REQUIRE(p && p->d.table, "ingest_batch: plan %d is null", i);
+        L->table.p[i] = p->d;
+        const size_t need = p->d.interp ? 0 : sinc_lds_bytes(p->d);
+        lds = need > lds ? need : lds;
     }
     int64_t stride = 1;
     for (int b = 0; b < B; ++b) {

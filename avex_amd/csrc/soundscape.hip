@@ -11,39 +11,27 @@
 // frame's P[t, :] is then a function of its own 512 samples (packed beside a loud frame, a quiet one's bins carry the partner's rounding
 // noise, eps * |X_loud|; for per-bin amplitudes that is not tolerable).  A frame of zeros gives +0 in every bin by arithmetic alone; a
 // frame that holds a NaN or an Inf is set to NaN in every bin (an Inf alone would leave +Inf in some).  No atomics, sums in one fixed
-// order: the same bits on every run and in any company.  Every read of wav is at base + j with j < n_samples of a recording the entry
-// point has checked against the buffer; every partial row, statistic row and frame index follows from the checked table.
+// order: the same bits on every run and in any company.  The walk over the frames is activity.hip's (rec_frames.h: the frame count, the
+// recording of a run or a segment, the span and twiddle staging, the refusals of a recording, a hop and a bin band); every partial row,
+// statistic row and frame index follows from the checked table.
 #include <math.h>
 
 #include "block_prims.h"
 #include "common.h"
 #include "fft512.h"
+#include "rec_frames.h"
 
 namespace {
 
-constexpr int kSsFrame = 512;                                    // n_fft, fixed
-constexpr int kSsBins = 257;
 constexpr int kSsRun = AVEXHIP_SOUNDSCAPE_RUN_FRAMES;            // frames per workgroup of the stats kernel
 constexpr int kSsStep = 4;                                       // frames per step: one per wave
-constexpr int kSsSpan = (kSsStep - 1) * 512 + kSsFrame + 8;      // floats of LDS for a step's span at hop 512, up to 3 lead-in samples, a whole last chunk
+constexpr int kSsSpan = (kSsStep - 1) * 512 + kRecFrame + 8;      // floats of LDS for a step's span at hop 512, up to 3 lead-in samples, a whole last chunk
 constexpr int kSsPRow = 260;
 // a partial row, in 4-byte words: the four sums, the first and the last amplitude row of the run, the run's non-finite frames
-constexpr int kPartPow = 0, kPartAmp = kSsBins, kPartDiff = 2 * kSsBins, kPartCount = 3 * kSsBins, kPartFirst = 4 * kSsBins, kPartLast = 5 * kSsBins,
-              kPartBad = 6 * kSsBins, kPartWords = 6 * kSsBins + 2;
+constexpr int kPartPow = 0, kPartAmp = kRecBins, kPartDiff = 2 * kRecBins, kPartCount = 3 * kRecBins, kPartFirst = 4 * kRecBins, kPartLast = 5 * kRecBins,
+              kPartBad = 6 * kRecBins, kPartWords = 6 * kRecBins + 2;
 
-__host__ __device__ __forceinline__ int64_t ss_frames_of(int64_t n_samples, int hop) { return n_samples < kSsFrame ? 0 : (n_samples - kSsFrame) / hop + 1; }
 __host__ __device__ __forceinline__ int ss_runs_per_segment(int S) { return (S + kSsRun - 1) / kSsRun; }
-
-// the last recording whose `first` (first_run or first_segment) is <= i: recordings without a frame share their successor's
-template <typename First>
-__device__ __forceinline__ int ss_recording_of(int n_rec, int i, First first) {
-    int lo = 0, hi = n_rec - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (first(mid) <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // grid: one workgroup per run (avexhip_soundscape_recording::first_run numbers them), 256 threads.  tables: [512] window, then [512]
 // (cos, -sin)(2 pi k / 512).  LDS: 8 224 + 18 432 + 4 096 + 4 160 + 16 bytes = 34 928.
@@ -56,9 +44,9 @@ __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __re
     __shared__ float prow[kSsStep][kSsPRow];
     __shared__ int bad_of[kSsStep];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = ss_recording_of(n_rec, (int)blockIdx.x, [&](int i) { return rec[i].first_run; });
+    const int r = last_at_most(n_rec, (int)blockIdx.x, [&](int i) { return rec[i].first_run; });
     const avexhip_soundscape_recording it = rec[r];
-    const int64_t F = ss_frames_of(it.n_samples, hop);
+    const int64_t F = frames_of(it.n_samples, hop);
     const int per_seg = ss_runs_per_segment(S);
     const int run = (int)blockIdx.x - it.first_run;
     const int64_t seg = run / per_seg;
@@ -69,9 +57,7 @@ __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __re
     const int nf = seg_n - in_seg < kSsRun ? (int)(seg_n - in_seg) : kSsRun;
     const int64_t f0 = seg * S + in_seg;                         // the run's first frame, counted inside its recording
 
-    const float2* twg = (const float2*)(tables + kSsFrame);
-    tw[tid] = twg[tid];
-    tw[tid + 256] = twg[tid + 256];
+    stage_twiddles(tw, tables);
 
     // thread t owns bin t; thread 0 bin 256 as well
     const int n_own = tid == 0 ? 2 : 1;
@@ -82,22 +68,8 @@ __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __re
     for (int st = 0; st < nf; st += kSsStep) {                   // (block-uniform trip count)
         const int ns = nf - st < kSsStep ? nf - st : kSsStep;
         __syncthreads();                                         // the step before has read span and prow
-        // ---- the span of the step's frames -> LDS, 16 bytes per lane wherever a whole aligned chunk lies inside the recording ----------
-        const int64_t s0 = it.base + (f0 + st) * hop;            // first sample, counted in wav
-        const int64_t a0 = s0 & ~(int64_t)3;                     // wav is 16-byte aligned (checked on the host)
-        const int lead = (int)(s0 - a0);
-        const int len = lead + (ns - 1) * hop + kSsFrame;        // <= 3 + 3 * 512 + 512
-        for (int c = tid * 4; c < len; c += 256 * 4) {
-            const int64_t i = a0 + c;
-            f32x4 q;
-            if (i >= r_lo && i + 4 <= r_hi) {
-                q = *(const f32x4*)(wav + i);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) q[e] = (i + e >= r_lo && i + e < r_hi) ? wav[i + e] : 0.f;
-            }
-            *(f32x4*)(span + c) = q;
-        }
+        // ---- the span of the step's frames -> LDS: lead <= 3, (ns - 1) hop + 512 <= 3 * 512 + 512 ---------------------------------------
+        const int lead = stage_span(span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
         __syncthreads();
 
         if (wave < ns) {                                         // (wave-uniform; only wave syncs inside)
@@ -118,7 +90,7 @@ __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __re
 #pragma unroll
             for (int q = 0; q < 5; ++q) {
                 const int k = lane + 64 * q;
-                if (k < kSsBins) {
+                if (k < kRecBins) {
                     const float2 zk = z[k];
                     const float p = bad ? NAN : zk.x * zk.x + zk.y * zk.y;
                     prow[wave][k] = p;
@@ -173,9 +145,9 @@ struct SsSegment {
     int n, first_run, n_runs;
 };
 __device__ __forceinline__ SsSegment ss_segment_of(const avexhip_soundscape_recording* __restrict__ rec, int n_rec, int hop, int S, int g) {
-    const int r = ss_recording_of(n_rec, g, [&](int i) { return rec[i].first_segment; });
+    const int r = last_at_most(n_rec, g, [&](int i) { return rec[i].first_segment; });
     const avexhip_soundscape_recording it = rec[r];
-    const int64_t F = ss_frames_of(it.n_samples, hop);
+    const int64_t F = frames_of(it.n_samples, hop);
     const int64_t gl = g - it.first_segment;
     SsSegment s;
     const int64_t left = F - gl * S;
@@ -199,7 +171,7 @@ __global__ __launch_bounds__(256) void soundscape_reduce_kernel(const avexhip_so
     for (int u = 0; u < sg.n_runs; ++u) n_bad += ((const int*)(part0 + (int64_t)u * kPartWords))[kPartBad];      // (every thread: the NaN rule below)
     if (tid == 0) nonfinite[g] = n_bad;
     const float n = (float)sg.n;                                 // exact: S <= 2^24
-    for (int k = tid; k < kSsBins; k += 256) {
+    for (int k = tid; k < kRecBins; k += 256) {
         float s_pow = 0.f, s_amp = 0.f, s_diff = 0.f, last = 0.f;
         int cnt = 0;
         for (int u = 0; u < sg.n_runs; ++u) {
@@ -211,7 +183,7 @@ __global__ __launch_bounds__(256) void soundscape_reduce_kernel(const avexhip_so
             last = part[kPartLast + k];
             cnt += ((const int*)part)[kPartCount + k];
         }
-        const int64_t o = (int64_t)g * kSsBins + k;
+        const int64_t o = (int64_t)g * kRecBins + k;
         mean_power[o] = n_bad ? NAN : s_pow / n;
         mean_amplitude[o] = n_bad ? NAN : s_amp / n;
         abs_diff[o] = n_bad ? NAN : s_diff;
@@ -240,10 +212,10 @@ __global__ __launch_bounds__(256) void soundscape_indices_kernel(const avexhip_s
         if (tid < AVEXHIP_SOUNDSCAPE_INDICES) dst[tid] = NAN;
         return;
     }
-    const float* mp = mean_power + (int64_t)g * kSsBins;
-    const float* ma = mean_amplitude + (int64_t)g * kSsBins;
-    const float* ad = abs_diff + (int64_t)g * kSsBins;
-    const int* ca = count_above + (int64_t)g * kSsBins;
+    const float* mp = mean_power + (int64_t)g * kRecBins;
+    const float* ma = mean_amplitude + (int64_t)g * kRecBins;
+    const float* ad = abs_diff + (int64_t)g * kRecBins;
+    const int* ca = count_above + (int64_t)g * kRecBins;
     const double n = (double)sg.n;
     const double full_scale = (double)AVEXHIP_SOUNDSCAPE_FULL_SCALE;
     auto block_sum = [&](double v) {
@@ -255,7 +227,7 @@ __global__ __launch_bounds__(256) void soundscape_indices_kernel(const avexhip_s
 
     // ---- aci, ndsi, the spectrum's total, the quietest bin of bio_band ---------------------------------------------------------------
     double v_aci = 0.0, v_bio = 0.0, v_anthro = 0.0, v_band = 0.0, v_min = INFINITY;
-    for (int k = tid; k < kSsBins; k += 256) {
+    for (int k = tid; k < kRecBins; k += 256) {
         const double p = (double)mp[k], a = (double)ma[k];
         if (within(k, spec.band)) {
             v_aci += a == 0.0 ? 0.0 : (double)ad[k] / (n * a);
@@ -275,7 +247,7 @@ __global__ __launch_bounds__(256) void soundscape_indices_kernel(const avexhip_s
 
     // ---- bi, hf -----------------------------------------------------------------------------------------------------------------------
     double v_bi = 0.0, v_hf = 0.0;
-    for (int k = tid; k < kSsBins; k += 256) {
+    for (int k = tid; k < kRecBins; k += 256) {
         const double p = (double)mp[k];
         if (within(k, spec.bio)) {
             const double floor_p = 1e-12 * full_scale;
@@ -345,15 +317,13 @@ int soundscape_recordings_check(const char* what, const avexhip_soundscape_recor
     AVX_REQUIRE(rec_host && rec_dev, "%s: null argument", what);
     AVX_REQUIRE(((uintptr_t)rec_dev & 7) == 0, "%s: rec_dev must be 8-byte aligned", what);
     AVX_REQUIRE(n_rec >= 1, "%s: n_rec=%d", what, n_rec);
-    AVX_REQUIRE(hop >= AVEXHIP_ACTIVITY_MIN_HOP && hop <= kSsFrame, "%s: hop=%d outside %d..%d", what, hop, AVEXHIP_ACTIVITY_MIN_HOP, kSsFrame);
+    AVXH_TRY(hop_check(what, hop));
     AVX_REQUIRE(S >= 1 && S <= AVEXHIP_SOUNDSCAPE_MAX_SEGMENT_FRAMES, "%s: segment_frames=%d outside 1..%d", what, S, AVEXHIP_SOUNDSCAPE_MAX_SEGMENT_FRAMES);
     int64_t frames = 0, segments = 0, runs = 0;
     for (int r = 0; r < n_rec; ++r) {
         const avexhip_soundscape_recording& it = rec_host[r];
-        AVX_REQUIRE(it.n_samples >= 1 && it.base >= 0, "%s: recording %d: %lld samples at %lld", what, r, (long long)it.n_samples, (long long)it.base);
-        AVX_REQUIRE(wav_samples < 0 || it.base <= wav_samples - it.n_samples, "%s: recording %d: %lld samples at %lld leave the buffer's %lld samples", what, r,
-                    (long long)it.n_samples, (long long)it.base, (long long)wav_samples);
-        const int64_t F = ss_frames_of(it.n_samples, hop);
+        AVXH_TRY(recording_check(what, r, it.n_samples, it.base, wav_samples));
+        const int64_t F = frames_of(it.n_samples, hop);
         AVX_REQUIRE(it.first_frame == frames && (int64_t)it.first_segment == segments && (int64_t)it.first_run == runs,
                     "%s: recording %d: first_frame=%lld first_segment=%d first_run=%d, expected %lld, %lld and %lld", what, r, (long long)it.first_frame,
                     it.first_segment, it.first_run, (long long)frames, (long long)segments, (long long)runs);
@@ -432,14 +402,10 @@ extern "C" int avexhip_soundscape_indices(const avexhip_soundscape_recording* re
                     ss_aligned4(nonfinite_dev) && ss_aligned4(frame_power_dev) && ((uintptr_t)indices_dev & 7) == 0,
                 "soundscape_indices: indices_dev must be 8-byte aligned, the other device arrays 4-byte aligned");
     const struct { const char* name; const int32_t* b; } named[3] = {{"band", spec->band}, {"bio_band", spec->bio}, {"anthro_band", spec->anthro}};
-    for (const auto& it : named)
-        AVX_REQUIRE(it.b[0] >= 0 && it.b[0] < it.b[1] && it.b[1] <= kSsBins, "soundscape_indices: %s: bins %d..%d outside 0 <= lo < hi <= %d", it.name, it.b[0],
-                    it.b[1], kSsBins);
+    for (const auto& it : named) AVXH_TRY(bin_band_check("soundscape_indices", it.name, -1, it.b[0], it.b[1]));
     AVX_REQUIRE(spec->n_adi >= 1 && spec->n_adi <= AVEXHIP_SOUNDSCAPE_MAX_ADI_BANDS, "soundscape_indices: n_adi=%d outside 1..%d", spec->n_adi,
                 AVEXHIP_SOUNDSCAPE_MAX_ADI_BANDS);
-    for (int j = 0; j < spec->n_adi; ++j)
-        AVX_REQUIRE(spec->adi[j][0] >= 0 && spec->adi[j][0] < spec->adi[j][1] && spec->adi[j][1] <= kSsBins,
-                    "soundscape_indices: adi band %d: bins %d..%d outside 0 <= lo < hi <= %d", j, spec->adi[j][0], spec->adi[j][1], kSsBins);
+    for (int j = 0; j < spec->n_adi; ++j) AVXH_TRY(bin_band_check("soundscape_indices", "adi band", j, spec->adi[j][0], spec->adi[j][1]));
     AVX_REQUIRE(spec->bin_khz > 0.0 && spec->bin_khz < INFINITY, "soundscape_indices: bin_khz=%g: a finite width > 0 expected", spec->bin_khz);
     AVXH_TRY(soundscape_recordings_check("soundscape_indices", rec_host, rec_dev, n_rec, hop, segment_frames, -1, total_frames, total_segments, nullptr));
     if (total_segments == 0) return AVEXHIP_OK;

@@ -9,11 +9,13 @@
 //   window_select_kernel   flags from two thresholds -> the kept window numbers in increasing order and their count (prefix sum, no atomics)
 //   window_gather_kernel   rows and masks of a list (or a contiguous range) of windows, one launch
 // All three read a device table of avexhip_window (recording base, start, valid), so windows of several recordings share a launch.
-// Every read is at base + start + j with j < valid, and the entry points refuse a table for which that leaves the recording.
+// Every read is at base + start + j with j < valid, and the entry points refuse a table for which that leaves the recording, or whose
+// recording leaves the buffer (recording_check, rec_frames.h: the refusal activity.hip and soundscape.hip make of theirs).
 #include <math.h>
 
 #include "block_prims.h"
 #include "common.h"
+#include "rec_frames.h"
 
 namespace {
 
@@ -152,9 +154,7 @@ int windows_check(const char* what, const float* wav_dev, int64_t wav_samples, c
     AVX_REQUIRE(wav_samples >= 1, "%s: wav_samples=%lld", what, (long long)wav_samples);
     for (int w = lo; w < hi; ++w) {
         const avexhip_window& it = win_host[w];
-        AVX_REQUIRE(it.n_samples >= 1 && it.base >= 0 && it.base <= wav_samples - it.n_samples,
-                    "%s: window %d: a recording of %lld samples at %lld leaves the buffer's %lld samples", what, w, (long long)it.n_samples, (long long)it.base,
-                    (long long)wav_samples);
+        AVXH_TRY(recording_check(what, w, it.n_samples, it.base, wav_samples, true));
         AVX_REQUIRE(it.valid >= 0 && it.valid <= window_len, "%s: window %d: valid=%d outside 0..window_len=%d", what, w, it.valid, window_len);
         AVX_REQUIRE(it.start >= 0 && it.start <= it.n_samples - it.valid, "%s: window %d: %lld + %d leaves the recording's %lld samples", what, w,
                     (long long)it.start, it.valid, (long long)it.n_samples);

@@ -23,7 +23,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _capi, ingest
+from . import _capi, _frames, ingest
 from ._capi import check, lib
 
 __all__ = ["plan_recording_windows", "RecordingWindows", "windows", "embed_recording", "embed_recordings"]
@@ -125,8 +125,7 @@ class RecordingWindows:
         self._table["n_samples"] = np.asarray([x.numel() for x in waves], dtype=np.int64)[self.recording]
         self._table["start"], self._table["valid"] = self.starts, self.valids
         with torch.cuda.device(dev):
-            self._table_pinned = torch.from_numpy(self._table.view(np.uint8).reshape(-1)).pin_memory()      # kept: the copy below is asynchronous
-            self._table_dev = self._table_pinned.to(dev, non_blocking=True)
+            self._table_pinned, self._table_dev = _frames._to_device(self._table, dev)      # the pinned copy is kept: the device copy is asynchronous
             self.energy = torch.empty(n, dtype=torch.float64, device=dev)
             self.peak = torch.empty(n, dtype=torch.float32, device=dev)
             check(lib().avexhip_window_stats(self.wav.data_ptr(), self.wav.numel(), self._table.ctypes.data, self._table_dev.data_ptr(), n, self.window_len,

@@ -41,19 +41,18 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _capi, activity
 from ._capi import check, lib
+from ._frames import N_BINS, N_FFT, _number, _tables_on, _to_device, frame_count, recording_table
 
 __all__ = ["IndexSpec", "SpectralStats", "SoundscapeIndices", "spectral_stats", "acoustic_indices", "acoustic_indices_of", "segment_plan", "INDEX_NAMES",
            "P_FS"]
 
-N_FFT = activity.N_FFT
-N_BINS = activity.N_BINS
 P_FS = 16384.0                            # AVEXHIP_SOUNDSCAPE_FULL_SCALE
 RUN_FRAMES = 64                           # AVEXHIP_SOUNDSCAPE_RUN_FRAMES
 MAX_SEGMENT_FRAMES = 1 << 24              # AVEXHIP_SOUNDSCAPE_MAX_SEGMENT_FRAMES
@@ -70,7 +69,7 @@ def _band(x: Any, what: str) -> Tuple[float, float]:
         lo, hi = x
     except (TypeError, ValueError) as e:
         raise ValueError(f"{what}={x!r}: a (lo_hz, hi_hz) pair expected") from e
-    lo, hi = activity._number(lo, what), activity._number(hi, what)
+    lo, hi = _number(lo, what), _number(hi, what)
     if not 0.0 <= lo < hi:
         raise ValueError(f"{what} ({lo}, {hi}): 0 <= lo_hz < hi_hz expected")
     return lo, hi
@@ -102,7 +101,7 @@ class IndexSpec:
         if isinstance(self.hop, bool) or not isinstance(self.hop, (int, np.integer)) or not activity.MIN_HOP <= self.hop <= N_FFT:
             raise ValueError(f"hop={self.hop!r}: an integer in {activity.MIN_HOP}..{N_FFT} expected")
         object.__setattr__(self, "hop", int(self.hop))
-        s = activity._number(self.segment_s, "segment_s")
+        s = _number(self.segment_s, "segment_s")
         if s <= 0.0:
             raise ValueError(f"segment_s={s}: a number > 0 expected")
         object.__setattr__(self, "segment_s", s)
@@ -115,7 +114,7 @@ class IndexSpec:
         object.__setattr__(self, "bio_band", _band(self.bio_band, "bio_band"))
         object.__setattr__(self, "anthro_band", _band(self.anthro_band, "anthro_band"))
         for name in ("adi_step_hz", "adi_max_hz"):
-            v = activity._number(getattr(self, name), name)
+            v = _number(getattr(self, name), name)
             if v <= 0.0:
                 raise ValueError(f"{name}={v}: a number > 0 expected")
             object.__setattr__(self, name, v)
@@ -158,7 +157,7 @@ def segment_plan(n_samples: Sequence[int], hop: int, segment_frames: int, sr: in
     hop, S = int(hop), int(segment_frames)
     if S < 1:
         raise ValueError(f"segment_frames={S}: at least one frame per segment")
-    frames = np.asarray([activity.frame_count(int(n), hop) for n in n_samples], dtype=np.int64)
+    frames = np.asarray([frame_count(int(n), hop) for n in n_samples], dtype=np.int64)
     segments = (frames + S - 1) // S
     g_end, f_end = np.cumsum(segments), np.cumsum(frames)
     recording = np.repeat(np.arange(len(frames), dtype=np.int32), segments)
@@ -187,28 +186,20 @@ class SpectralStats:
         dev = ws.wav.device
         hop, S = spec.hop, spec.segment_frames(ws.sr)
         self.hop, self.segment_frames = hop, S
-        n_rec = len(ws.ranges)
-        first = np.asarray([w0 for w0, _ in ws.ranges], dtype=np.int64)
-        self._rec = np.zeros(n_rec, dtype=RECORDING_DTYPE)
-        self._rec["base"], self._rec["n_samples"] = ws._table["base"][first], ws._table["n_samples"][first]
+        self._rec, frames = recording_table(ws, RECORDING_DTYPE, hop)
         plan = segment_plan(self._rec["n_samples"], hop, S, ws.sr)
-        frames, segments = plan["frames"], plan["segments"]
-        per_segment = (S + RUN_FRAMES - 1) // RUN_FRAMES
-        runs = (frames // S) * per_segment + (frames % S + RUN_FRAMES - 1) // RUN_FRAMES
-        self._rec["first_frame"] = np.cumsum(frames) - frames
-        self._rec["first_segment"] = np.cumsum(segments) - segments
-        self._rec["first_run"] = np.cumsum(runs) - runs
+        segments = plan["segments"]
+        runs = (frames // S) * ((S + RUN_FRAMES - 1) // RUN_FRAMES) + (frames % S + RUN_FRAMES - 1) // RUN_FRAMES
+        self._rec["first_segment"], self._rec["first_run"] = np.cumsum(segments) - segments, np.cumsum(runs) - runs
         self.total_frames, self.n_segments, self.n_runs = int(frames.sum()), int(segments.sum()), int(runs.sum())
         if max(self.total_frames, self.n_runs) >= 1 << 31:
             raise ValueError(f"{self.total_frames} frames: more than 2^31 - 1 (a longer hop, or fewer recordings per call)")
-        self.frame_ranges: List[Tuple[int, int]] = plan["frame_ranges"]
-        self.segment_ranges: List[Tuple[int, int]] = plan["segment_ranges"]
+        self.frame_ranges, self.segment_ranges = plan["frame_ranges"], plan["segment_ranges"]
         self.recording, self.n_frames, self.start_s, self.end_s = plan["recording"], plan["n_frames"], plan["start_s"], plan["end_s"]
         G = self.n_segments
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
-            self._pinned_rec, self._rec_dev = activity._to_device(self._rec, dev)
-            tab = activity._tables_on(dev)
+            self._pinned_rec, self._rec_dev = _to_device(self._rec, dev)
             self._partials_bytes = int(lib().avexhip_soundscape_partials_bytes(self.n_runs))
             self._partials = torch.empty(self._partials_bytes // 4, dtype=torch.float32, device=dev)
             self.frame_power = torch.empty(self.total_frames, dtype=torch.float32, device=dev)
@@ -217,7 +208,7 @@ class SpectralStats:
             self.abs_diff = torch.empty((G, N_BINS), dtype=torch.float32, device=dev)
             self.count_above = torch.empty((G, N_BINS), dtype=torch.int32, device=dev)
             self.nonfinite_frames = torch.empty(G, dtype=torch.int32, device=dev)
-            self._frames(stream, tab)
+            self._frames(stream, _tables_on(dev))
             self._reduce(stream)
 
     def _ptr(self, t: torch.Tensor) -> Optional[int]:

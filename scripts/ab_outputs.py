@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do two builds of libavexhip.so compute the same thing?
 
-    python scripts/ab_outputs.py LIB_A LIB_B [--set forwards|analytics] [--timeout SECONDS]
+    python scripts/ab_outputs.py LIB_A LIB_B [--set forwards|analytics|audio] [--timeout SECONDS]
 
 Runs one fixed set of small forwards (or, with --set analytics, of small calls of the analytics modules) under each library -- a fresh child process per library (AVEX_AMD_LIB), one after the other, each
 under its own time limit; the first child that fails ends the run -- and compares every output array with np.array_equal, every
@@ -18,6 +18,12 @@ The analytics set calls the public functions of search, retrieval, examples, clu
 on seeded NumPy inputs, at the smallest shapes that reach every shared block of their kernels (block_prims.h, the rank key of f32_tile.h):
 tied keys through all eight radix passes, lists deeper than a chunk, the chunked rank sort, relocation through several empty clusters,
 floor ranks on tied and NaN energies.  For refactors of those kernels; it finishes in seconds.
+
+The audio set does the same for ingest, recordings, activity and soundscape (the chains of ingest.hip, the frame walk of rec_frames.h):
+every sample format, mono and stereo, without a plan and under a Hann sinc, a Kaiser sinc and an interpolating plan, per file and as
+batch rows from inside the clip and padded; a float clip with a NaN; two recordings (40 000 and 700 samples, one NaN sample) in one
+buffer at bases that are and are not multiples of 4: window statistics, gathers, a select, the activity gate at hops 160 and 512, the
+acoustic indices at hops 256 and 512 with segments of several runs and a partial last one.
 """
 import argparse
 import json
@@ -214,16 +220,108 @@ def child_analytics(out_path: str) -> None:
         json.dump(dict(lib=_capi.LIB_PATH, profiles={}, nodes={}), f)
 
 
+def child_audio(out_path: str) -> None:
+    import numpy as np
+    import torch
+    import struct
+    sys.path.insert(0, ROOT)
+    from avex_amd import _capi, activity, ingest, recordings, soundscape
+    from avex_amd._capi import check, lib
+
+    def _wav(x, sr, fmt):
+        """[frames, channels] float in [-1, 1) -> RIFF/WAVE bytes: 8 / 16 / 24 / 32-bit integer PCM, 0 = float32, 64 = float64."""
+        bits = {0: 32, 64: 64}.get(fmt, fmt)
+        if fmt in (0, 64):
+            data = x.astype("<f4" if fmt == 0 else "<f8").tobytes()
+        elif fmt == 8:
+            data = np.clip(x * 128 + 128, 0, 255).astype(np.uint8).tobytes()
+        elif fmt == 24:
+            v = (x * 8388607).astype(np.int32)
+            data = np.stack([v & 255, (v >> 8) & 255, (v >> 16) & 255], -1).astype(np.uint8).tobytes()
+        else:
+            data = (x * (2 ** (fmt - 1) - 1)).astype("<i2" if fmt == 16 else "<i4").tobytes()
+        ch = x.shape[1]
+        hdr = struct.pack("<HHIIHH", 3 if fmt in (0, 64) else 1, ch, sr, sr * ch * bits // 8, ch * bits // 8, bits)
+        return b"RIFF" + struct.pack("<I", 20 + len(hdr) + len(data)) + b"WAVE" + b"fmt " + struct.pack("<I", len(hdr)) + hdr + b"data" + struct.pack("<I", len(data)) + data
+
+    arrays = {}
+    rng = np.random.default_rng(29)
+    # ---- ingest: every sample format, mono and stereo, under the four kinds of plan; per file and in a batch ----
+    kaiser = ingest.Resampler(22050, 16000, lowpass_filter_width=16, rolloff=0.945, beta=14.77)
+    interp = ingest.Resampler(32000, 16000, res_type="kaiser_best")
+    T = 1000
+    for plan, sr, res_type in (("none", 16000, None), ("hann", 44100, None), ("kaiser", 22050, None), ("interp", 32000, "kaiser_best")):
+        tags, clips, starts = [], [], []
+        for fmt in (8, 16, 24, 32, 0, 64):
+            for ch in (1, 2):
+                frames = int(rng.integers(3000, 9001))
+                data = _wav(rng.uniform(-0.9, 0.9, size=(frames, ch)).astype(np.float32), sr, fmt)
+                if plan in ("none", "hann"):
+                    x = ingest.load_audio(data, 16000)[0]
+                else:                                            # load_audio's pieces, under a plan it does not make
+                    raw, _, _, code = ingest.parse_wav(data)
+                    x = (kaiser if plan == "kaiser" else interp)(ingest.to_device_mono(raw, ch, code))
+                arrays[f"ingest.{plan}.f{fmt}.c{ch}.file"] = x.cpu().numpy()
+                tags += [f"ingest.{plan}.f{fmt}.c{ch}"] * 2
+                clips += [data, data]
+                starts += [333, x.numel() - 400]                 # a window from inside the clip, and one the clip's end cuts short: padding
+        if plan == "kaiser":                                     # load_batch has no argument for a Kaiser sinc plan: it finds this one, for this call
+            ingest._BATCH_RESAMPLERS[sr, 16000, None] = kaiser
+        wav, mask, lengths = ingest.load_batch(clips, 16000, T, starts=starts, res_type=res_type)
+        if plan == "kaiser":
+            del ingest._BATCH_RESAMPLERS[sr, 16000, None]
+        for b, tag in enumerate(tags):
+            arrays[f"{tag}.batch{b % 2}"] = np.concatenate([wav[b].cpu().numpy(), mask[b].cpu().numpy().astype(np.float32), [float(lengths[b])]])
+    bad = rng.uniform(-0.5, 0.5, size=(2, 4000)).astype(np.float32)
+    bad[1, 1234] = np.nan                                        # a float clip that holds a NaN: a NaN per file, a zero row in the batch
+    arrays["ingest.nan.file"] = ingest.to_device_mono(np.ascontiguousarray(bad.T), 2, 0).cpu().numpy()
+    wav, mask, _ = ingest.load_batch([bad, bad[0]], 16000, T)
+    arrays["ingest.nan.batch"], arrays["ingest.nan.mask"] = wav.cpu().numpy(), mask.cpu().numpy()
+
+    # ---- recordings of 40 000 and 700 samples in one buffer, one NaN sample; as RecordingWindows lays them out (bases 0 and 40 000) and
+    # one sample further (odd bases: stage_span's lead-in, the single loads of windows.hip) ----
+    a = (0.05 * rng.standard_normal(40000)).astype(np.float32)
+    a[8000:12000] = 0.0
+    a[39001] = np.nan                                            # in the last segment at both hops
+    b = (0.05 * rng.standard_normal(700)).astype(np.float32)
+    ws0 = recordings.RecordingWindows([torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()], 16000, 8000, 4000)
+    ws1 = recordings.RecordingWindows([torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()], 16000, 8000, 4000)
+    ws1.wav = torch.cat([torch.zeros(1, device="cuda"), ws1.wav])
+    ws1._table["base"] += 1
+    ws1._table_pinned = torch.from_numpy(ws1._table.view(np.uint8).reshape(-1)).pin_memory()
+    ws1._table_dev = ws1._table_pinned.cuda()
+    check(lib().avexhip_window_stats(ws1.wav.data_ptr(), ws1.wav.numel(), ws1._table.ctypes.data, ws1._table_dev.data_ptr(), ws1.n_windows, ws1.window_len,
+                                     ws1.energy.data_ptr(), ws1.peak.data_ptr(), torch.cuda.current_stream().cuda_stream), "window_stats")
+    for tag, ws in (("rec.base0", ws0), ("rec.base1", ws1)):
+        rows, mask = ws.batch(torch.arange(ws.n_windows - 1, -1, -1))
+        arrays.update({f"{tag}.energy": ws.energy.cpu().numpy(), f"{tag}.peak": ws.peak.cpu().numpy(), f"{tag}.rows": rows.cpu().numpy(),
+                       f"{tag}.mask": mask.cpu().numpy(), f"{tag}.range": ws.batch(1, 3)[0].cpu().numpy(), f"{tag}.kept": ws.select(-40.0, -30.0).cpu().numpy()})
+        for hop in (160, 512):                                   # the span of a workgroup at its shortest and its longest
+            act = activity.band_activity(ws, activity.ActivityGate([(500, 2000), (2000, 8000)], hop=hop))
+            for k in ("frame_energy", "floor", "nonfinite_frames", "n_frames", "active_frames", "max_energy"):
+                arrays[f"{tag}.activity.h{hop}.{k}"] = getattr(act, k).cpu().numpy()
+            arrays[f"{tag}.activity.h{hop}.kept"] = act.select().cpu().numpy()
+        for hop in (256, 512):                                   # 2.24 s: 140 / 70 frames a segment (three / two runs), a partial last segment
+            ix = soundscape.acoustic_indices(ws, soundscape.IndexSpec(hop=hop, segment_s=2.24))
+            for k in ("mean_power", "mean_amplitude", "abs_diff", "count_above", "frame_power", "nonfinite_frames"):
+                arrays[f"{tag}.soundscape.h{hop}.{k}"] = getattr(ix.stats, k).cpu().numpy()
+            arrays[f"{tag}.soundscape.h{hop}.indices"] = ix.values.cpu().numpy()
+    torch.cuda.synchronize()
+    np.savez(out_path, **arrays)
+    with open(out_path + ".json", "w") as f:
+        json.dump(dict(lib=_capi.LIB_PATH, profiles={}, nodes={}), f)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("lib_a")
     ap.add_argument("lib_b")
-    ap.add_argument("--set", choices=("forwards", "analytics"), default="forwards", help="which fixed set to run")
+    ap.add_argument("--set", choices=("forwards", "analytics", "audio"), default="forwards", help="which fixed set to run")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--child", metavar="OUT", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        (child if a.set == "forwards" else child_analytics)(a.child)
+        {"forwards": child, "analytics": child_analytics, "audio": child_audio}[a.set](a.child)
         return 0
     import numpy as np
     res = []
