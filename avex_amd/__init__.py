@@ -17,6 +17,7 @@ from .density import dbscan, k_distance
 from .activity import ActivityGate, band_activity
 from .annotations import Annotations, score_events, sweep_thresholds
 from .soundscape import IndexSpec, acoustic_indices, spectral_stats
+from .measurements import MeasureSpec, measure_boxes, measure_events, noise_spectrum, write_raven
 
 __version__ = "0.1.0"
 
@@ -27,4 +28,5 @@ __all__ = [
     "decode_events", "detect_events", "ExampleBank", "detect_events_by_example", "dbscan", "k_distance",
     "ActivityGate", "band_activity", "Annotations", "score_events", "sweep_thresholds",
     "IndexSpec", "acoustic_indices", "spectral_stats",
+    "MeasureSpec", "measure_boxes", "measure_events", "noise_spectrum", "write_raven",
 ]

@@ -335,6 +335,10 @@ SYMBOLS = {
     "avexhip_soundscape_frames": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P, _P]),
     "avexhip_soundscape_reduce": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
     "avexhip_soundscape_indices": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "avexhip_measure_partials_bytes": (C.c_size_t, [C.c_int64]),
+    "avexhip_measure_frames": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P, _P]),
+    "avexhip_measure_reduce": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P,
+                                         _P, _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

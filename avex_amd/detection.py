@@ -234,15 +234,19 @@ def detect_events(model: Any, probe: Callable[[torch.Tensor], torch.Tensor], sou
                   layers: Optional[Sequence[Any]] = None, aggregation: str = "mean", batch_size: int = 256, min_rms_db: Optional[float] = None,
                   min_peak_db: Optional[float] = None, tail: str = "pad", batch_invariant: Optional[bool] = None, sr: int = 16000,
                   res_type: Optional[str] = None, device: Any = None, max_resident_samples: Optional[int] = None,
-                  activity: Optional[Any] = None) -> Dict[str, Any]:
+                  measure: Optional[Any] = None, activity: Optional[Any] = None) -> Dict[str, Any]:
     """Files to events: the windows of ``sources`` are embedded (:func:`avex_amd.recordings.embed_recordings`, whose gate and model
     arguments this takes), ``probe(emb[lo:hi])`` scores them ``probe_batch_size`` at a time -- any callable from ``[n, D]`` to ``[n, C]``:
     an :mod:`avex_amd.probes` head in ``feature_mode``, or a torch module -- and :func:`decode_events` (whose rule arguments this takes)
     turns the scores into events.  A window the gate dropped has no score: it takes no part in smoothing and clears the state.
 
     Returns the event dict with ``recording`` / ``start_s`` / ``end_s`` / ``peak_s``, plus ``names`` (the recordings in order: a path
-    where the source is one, else its number) and, with ``return_scores``, ``scores [n_kept, C]`` and ``row_of_window [N]``."""
-    from . import recordings
+    where the source is one, else its number) and, with ``return_scores``, ``scores [n_kept, C]`` and ``row_of_window [N]``.  With
+    ``measure`` (a :class:`avex_amd.measurements.MeasureSpec`) the result gains ``measurements``:
+    :func:`avex_amd.measurements.measure_events` of the events over the windows they were decoded with, which the caller never sees."""
+    from . import measurements, recordings
+    if measure is not None and not isinstance(measure, measurements.MeasureSpec):
+        raise TypeError(f"measure: a MeasureSpec expected, not {type(measure).__name__}")
     _check_rules(smooth, smooth_mode, merge_gap, min_windows, max_events, activation)
     _thresholds(on, off, None, activation)
     _int_in(probe_batch_size, 1, 1 << 31, "probe_batch_size")
@@ -280,6 +284,8 @@ def detect_events(model: Any, probe: Callable[[torch.Tensor], torch.Tensor], sou
         else:                                         # the gate kept nothing: no score, no event
             scores = torch.empty((0, 0), dtype=torch.float32, device=dev)
             out = _empty(dev, 0 if max_events is None else int(max_events), activation, ws)
+        if measure is not None:
+            out["measurements"] = measurements.measure_events(out, ws, measure)
     out["names"] = names
     if return_scores:
         out["scores"], out["row_of_window"] = scores, row_of_window

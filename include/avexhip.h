@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 23
+#define AVEXHIP_ABI_VERSION 24
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -1055,6 +1055,79 @@ int avexhip_soundscape_indices(const avexhip_soundscape_recording* rec_host, con
                                const float* mean_power_dev, const float* mean_amplitude_dev, const float* abs_diff_dev,
                                const int32_t* count_above_dev, const int32_t* nonfinite_dev, const float* frame_power_dev, double* indices_dev,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Event measurements (ABI 24): the time and frequency extent of each event -- what a selection table carries beside the class -- from
+ * the resident waveforms above and the frames of the acoustic indices.
+ *   boxes      an event is a box on one recording: the samples [s0, s1) counted from the recording's first, and the bins [lo, hi),
+ *              0 <= lo < hi <= 257.  `recording` is its row of noise_dev.
+ *   frames     as avexhip_soundscape_frames, on the recording's own grid: 512 samples every hop, the periodic Hann table of
+ *              tables_dev, one frame per transform, so P[f, k] is the same function of the frame's 512 samples (+0 in every bin for a
+ *              frame of zeros, NaN in every bin for one holding a NaN or an Inf).  The event's frames are those wholly inside
+ *              [s0, s1): f0 = ceil(s0 / hop), f1 = min((s1 - 512) / hop + 1, F_r) when s1 >= 512, else 0, n = max(f1 - f0, 0).
+ *   runs       (avexhip_measure_frames) one workgroup per run of up to AVEXHIP_MEASURE_RUN_FRAMES consecutive frames of one event,
+ *              counted from f0 (first_run): a row of per-bin sums in frame order and the run's non-finite frames in partials_dev
+ *              (avexhip_measure_partials_bytes(runs), runs = the sum over events of ceil(n / 64)), and envelope_dev[env_offset + t] =
+ *              the sum of P[f0 + t, k] over lo <= k < hi, formed as avexhip_soundscape_frames forms frame_power (a lane adds its bins
+ *              in increasing order, then the wave butterfly; a bin outside the band adds +0).
+ *   reduce     (avexhip_measure_reduce) one workgroup per event.  spectrum_dev[e, k] (fp32, [E, 257]) = the runs' sums added in run
+ *              order for lo <= k < hi, +0 outside the band, NaN in every band bin when the event holds a non-finite frame.  Then fp64:
+ *                S'[k] = max(spectrum[k] - n noise[recording, k], 0), e'[t] = max(envelope[t] - sum of noise[recording, lo .. hi - 1], 0)
+ *                        (the noise sum in bin order; noise_dev = NULL: S' = spectrum, e' = envelope; a NaN noise stays NaN)
+ *                the quantile index of level q over v: the smallest i with cumsum(v)[i] >= q sum(v)
+ *                n_frames, nonfinite          int32
+ *                energy                       sum S'
+ *                low_bin centre_bin high_bin  the quantile bins of S' at q_lo, q_c, q_hi;  peak_bin: the lowest bin attaining max S'
+ *                low_frame centre_frame high_frame   the quantile frames of e', numbered on the recording's grid (f0 + t);
+ *                                             peak_frame: the lowest frame attaining max e'
+ *                snr_db                       10 log10(sum S' / (n sum of noise over the band)); NaN without noise or when that is 0
+ *              n = 0 or a non-finite frame: -1 in the eight index columns, NaN in energy and snr_db.  sum S' = 0 (or NaN): -1 in the
+ *              bin columns; sum e' = 0 (or NaN): -1 in the frame columns.
+ * Sums run in one fixed order and nothing is atomic: an event's numbers depend on its recording's samples, its box, hop, the levels
+ * and its noise row alone -- the same bits in any company, in any order of the events (which may overlap and repeat) and on every run.
+ * ev_host / ev_dev: the same table on the host (read for the argument checks) and on the device.  Both entry points refuse with
+ * AVEXHIP_ERR_INVALID before anything is launched: null or misaligned pointers, hop outside 32 .. 512, a recording that leaves wav_dev,
+ * a box outside its recording or with s1 < s0, n_frames / first_run / env_offset / total_frames / total_runs that do not follow from
+ * the boxes and hop, bins outside 0 <= lo < hi <= 257, an event of more than AVEXHIP_MEASURE_MAX_EVENT_FRAMES frames, a recording
+ * outside 0 .. n_rec - 1 (with noise), levels outside 0 < q_lo <= q_c <= q_hi < 1; a partials buffer that is too small gives
+ * AVEXHIP_ERR_WORKSPACE.  n_events = 0: success, nothing launched.  Nothing here allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_MEASURE_RUN_FRAMES 64
+#define AVEXHIP_MEASURE_MAX_EVENT_FRAMES 16777216          /* 2^24 */
+typedef struct {
+    int64_t base;            /* first sample of the event's recording in wav_dev, counted in floats */
+    int64_t n_samples;       /* samples of that recording */
+    int64_t s0;              /* the box's samples [s0, s1), counted from the recording's first */
+    int64_t s1;
+    int64_t env_offset;      /* frames of the events in front of it */
+    int32_t n_frames;        /* n, as it follows from s0, s1, hop and n_samples */
+    int32_t first_run;       /* runs of the events in front of it */
+    int32_t lo;              /* bins lo .. hi - 1 */
+    int32_t hi;
+    int32_t recording;       /* row of noise_dev */
+    int32_t reserved;
+} avexhip_measure_event;
+typedef struct {             /* device columns of n_events rows each, written by avexhip_measure_reduce */
+    int32_t* n_frames;
+    int32_t* nonfinite;
+    double* energy;
+    int32_t* low_bin;
+    int32_t* centre_bin;
+    int32_t* high_bin;
+    int32_t* peak_bin;
+    int32_t* low_frame;
+    int32_t* centre_frame;
+    int32_t* high_frame;
+    int32_t* peak_frame;
+    double* snr_db;
+} avexhip_measure_result;
+size_t avexhip_measure_partials_bytes(int64_t n_runs);         /* 0: a count it refuses */
+int avexhip_measure_frames(const float* wav_dev, int64_t wav_samples, const avexhip_measure_event* ev_host, const avexhip_measure_event* ev_dev,
+                           int n_events, int hop, const float* tables_dev, int64_t total_frames, int64_t total_runs, void* partials_dev,
+                           size_t partials_bytes, float* envelope_dev, void* stream);
+int avexhip_measure_reduce(const avexhip_measure_event* ev_host, const avexhip_measure_event* ev_dev, int n_events, int hop, int64_t total_frames,
+                           int64_t total_runs, const void* partials_dev, size_t partials_bytes, const float* envelope_dev, const float* noise_dev,
+                           int n_rec, double q_lo, double q_c, double q_hi, float* spectrum_dev, const avexhip_measure_result* out, void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
