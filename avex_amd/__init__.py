@@ -18,6 +18,7 @@ from .activity import ActivityGate, band_activity
 from .annotations import Annotations, score_events, sweep_thresholds
 from .soundscape import IndexSpec, acoustic_indices, spectral_stats
 from .measurements import MeasureSpec, measure_boxes, measure_events, noise_spectrum, write_raven
+from .regions import RegionSpec, find_regions, label_cells
 
 __version__ = "0.1.0"
 
@@ -29,4 +30,5 @@ __all__ = [
     "ActivityGate", "band_activity", "Annotations", "score_events", "sweep_thresholds",
     "IndexSpec", "acoustic_indices", "spectral_stats",
     "MeasureSpec", "measure_boxes", "measure_events", "noise_spectrum", "write_raven",
+    "RegionSpec", "find_regions", "label_cells",
 ]

@@ -339,6 +339,12 @@ SYMBOLS = {
     "avexhip_measure_frames": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P, _P]),
     "avexhip_measure_reduce": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P,
                                          _P, _P]),
+    "avexhip_regions_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "avexhip_regions_cells": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64, _P, _P, _P]),
+    "avexhip_regions_pack": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "avexhip_regions_count": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, _P, _P]),
+    "avexhip_regions_label": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),
+    "avexhip_regions_rows": (C.c_int, [C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P, _P, _P]),
     "avexhip_clustering_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "avexhip_clustering_max_k": (C.c_int, []),
     "avexhip_clustering_trials": (C.c_int, [C.c_int]),

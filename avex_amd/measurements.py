@@ -177,10 +177,12 @@ class Measurements(dict):
 
 
 def measure_boxes(ws: Any, recording: Any, start_sample: Any, end_sample: Any, spec: Optional[MeasureSpec] = None, *, class_id: Any = None,
-                  noise_power: Optional[torch.Tensor] = None) -> "Measurements":
+                  noise_power: Optional[torch.Tensor] = None, bins: Any = None) -> "Measurements":
     """The measurements of the boxes ``[start_sample, end_sample)`` (counted from the recording's first sample) of the recordings
     ``recording`` behind the windows ``ws`` (its window plan plays no part).  The three arrays are host integers (``[E]``); a row with
-    ``recording == -1`` is a padded row.  ``class_id [E]`` picks each box's band when ``spec.band`` holds one per class.
+    ``recording == -1`` is a padded row.  ``class_id [E]`` picks each box's band when ``spec.band`` holds one per class.  ``bins [E, 2]``
+    (host integers): each box's own bins ``lo <= k < hi``, ``0 <= lo < hi <= 257``, in place of ``spec.band`` and ``class_id`` (a padded
+    row's pair is not read) -- the boxes of :meth:`avex_amd.regions.Regions.boxes`.
     ``noise_power [R, 257]``: a device tensor, e.g. :func:`noise_spectrum`.  Two launches, device tensors, no host synchronisation.
     See the module docstring for the columns; ``first_frame [E]`` (``f0``), ``recording`` and the box's own span ``box_begin_s`` /
     ``box_end_s`` come with them."""
@@ -203,7 +205,15 @@ def measure_boxes(ws: Any, recording: Any, start_sample: Any, end_sample: Any, s
     if ((a_ < 0) | (b_ < a_) | (b_ > n_samples[r_])).any():
         e = int(idx[np.argmax((a_ < 0) | (b_ < a_) | (b_ > n_samples[r_]))])
         raise ValueError(f"box {e}: samples {int(s0[e])}..{int(s1[e])} outside recording {int(rec[e])} of {int(n_samples[rec[e]])} samples")
-    if spec.per_class:
+    if bins is not None:
+        own = np.asarray(bins.detach().cpu() if isinstance(bins, torch.Tensor) else bins)
+        if own.shape != (E, 2) or (own.size and own.dtype.kind not in "iu"):
+            raise ValueError(f"bins: an integer [{E}, 2] array expected")
+        lo_hi = own.astype(np.int64)[idx]
+        if ((lo_hi[:, 0] < 0) | (lo_hi[:, 0] >= lo_hi[:, 1]) | (lo_hi[:, 1] > N_BINS)).any():
+            e = int(idx[np.argmax((lo_hi[:, 0] < 0) | (lo_hi[:, 0] >= lo_hi[:, 1]) | (lo_hi[:, 1] > N_BINS))])
+            raise ValueError(f"box {e}: bins {int(own[e, 0])}..{int(own[e, 1])} outside 0 <= lo < hi <= {N_BINS}")
+    elif spec.per_class:
         if class_id is None:
             raise ValueError("spec.band holds one band per class: class_id expected")
         cls = _host_ints(class_id, "class_id")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVEXHIP_ABI_VERSION 24
+#define AVEXHIP_ABI_VERSION 25
 
 enum { AVEXHIP_F16 = 0, AVEXHIP_BF16 = 1 };
 
@@ -1128,6 +1128,76 @@ int avexhip_measure_frames(const float* wav_dev, int64_t wav_samples, const avex
 int avexhip_measure_reduce(const avexhip_measure_event* ev_host, const avexhip_measure_event* ev_dev, int n_events, int hop, int64_t total_frames,
                            int64_t total_runs, const void* partials_dev, size_t partials_bytes, const float* envelope_dev, const float* noise_dev,
                            int n_rec, double q_lo, double q_c, double q_hi, float* spectrum_dev, const avexhip_measure_result* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Sound-event regions (ABI 25): model-free segmentation -- the spectrogram cells that stand out of a per-recording threshold spectrum,
+ * joined into connected regions, one time-frequency box per region -- from the resident waveforms above and the frames of the
+ * acoustic indices.  The [frames, 257] spectrogram is never stored: 9 words of cell bits per frame are.
+ *   frames     as avexhip_soundscape_frames, on the recording's own grid: 512 samples every hop, the periodic Hann table of
+ *              tables_dev, one frame per transform, so P[f, k] is the same function of the frame's 512 samples (+0 in every bin for a
+ *              frame of zeros, NaN in every bin for one holding a NaN or an Inf).
+ *   cells      (avexhip_regions_cells) one workgroup per run of up to AVEXHIP_REGIONS_RUN_FRAMES consecutive frames of one recording
+ *              (first_run).  Cell (f, k) is set iff lo <= k < hi and P[f, k] > thr_dev[r, k] (thr_dev: [n_rec, 257] fp32; one strict
+ *              compare, false for a NaN on either side).  cells_dev [total_frames, 9] int32: bit k % 32 of word k / 32 of row
+ *              first_frame + f; bits 1 .. 31 of word 8 are 0.  nonfinite_dev[r] = the recording's NaN frames.
+ *              avexhip_regions_pack makes the same words from a [total_frames, 257] mask of bytes (non-zero: set).
+ *   count      (avexhip_regions_count) the exclusive prefix of the frames' set cells into the frame workspace; counts_dev[0] = the
+ *              number of set cells (int64).  The compact number of a set cell is offset[f] + popcount(the frame's bits below k): it
+ *              grows with (recording, frame, bin).
+ *   label      (avexhip_regions_label, n_cells = counts_dev[0] as the host read it) two set cells of one recording are neighbours when
+ *              |df| <= rt and |dk| <= rk; regions are the connected components, numbered in the order of their smallest cell by
+ *              (recording, frame, bin).  A region never crosses from one recording into the next and a frame's bins do not wrap into
+ *              the next frame's.  Union-find over the compact cells with integer atomicMin hooks, a flatten pass, the roots ranked by
+ *              counting; per region by integer atomics: last_frame, low_bin, high_bin, n_cells (first_frame and recording are its
+ *              smallest cell's).  The rule's filters drop a region with n_cells < min_cells, n_frames < min_frames, n_bins < min_bins
+ *              or (max_frames >= 1) n_frames > max_frames; counts_dev[1] = the regions found, counts_dev[2] = the regions kept.
+ *              The number of launches does not depend on the mask.
+ *   rows       (avexhip_regions_rows, n_kept = counts_dev[2] as the host read it) rows_dev [8, n_kept] int32, the kept regions in
+ *              order: recording, first_frame, last_frame (on the recording's grid, inclusive), low_bin, high_bin (inclusive), n_cells,
+ *              n_frames = last_frame - first_frame + 1, n_bins = high_bin - low_bin + 1.
+ * Everything after the compare is integer arithmetic and every atomic an integer min, max or add on global memory: a region's row
+ * depends on its recording's samples, that recording's thr row, hop, the band and the reach alone -- the same bits on every run, in any
+ * company and order of recordings, up to the recording column.  Working memory: avexhip_regions_workspace_bytes(total_frames, 0) for the
+ * frame workspace (one integer per frame), avexhip_regions_workspace_bytes(0, n_cells) for the cell workspace (nine per set cell).
+ * Every entry point refuses with AVEXHIP_ERR_INVALID before anything is launched: null or misaligned pointers, hop outside 32 .. 512, a
+ * recording that leaves wav_dev, first_frame / first_run / total_frames that do not follow from the samples and hop, frame offsets that
+ * are not in order, bins outside 0 <= lo < hi <= 257, rt outside 0 .. 4, rk outside 0 .. 8, a filter < 1, 2^31 frames or more, 2^31
+ * set cells or more (raise the threshold); a workspace that is too small gives AVEXHIP_ERR_WORKSPACE.  No frame, no set cell or no
+ * kept region: success, nothing launched.  Nothing here allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define AVEXHIP_REGIONS_RUN_FRAMES 64
+#define AVEXHIP_REGIONS_WORDS 9
+#define AVEXHIP_REGIONS_MAX_RT 4
+#define AVEXHIP_REGIONS_MAX_RK 8
+#define AVEXHIP_REGIONS_COLUMNS 8
+typedef struct {
+    int64_t base;            /* first sample of the recording in wav_dev, counted in floats */
+    int64_t n_samples;       /* samples of the recording */
+    int64_t first_frame;     /* frames of the recordings in front of it */
+    int32_t first_run;       /* runs of the recordings in front of it */
+    int32_t reserved;
+} avexhip_regions_recording;
+typedef struct {
+    int32_t rt;              /* reach in frames, 0 .. 4 */
+    int32_t rk;              /* reach in bins, 0 .. 8 */
+    int32_t min_cells;       /* >= 1 */
+    int32_t min_frames;      /* >= 1 */
+    int32_t min_bins;        /* >= 1 */
+    int32_t max_frames;      /* >= 1, or -1: no upper bound */
+} avexhip_regions_rule;
+size_t avexhip_regions_workspace_bytes(int64_t total_frames, int64_t n_cells);      /* 0: counts it refuses (or both 0) */
+int avexhip_regions_cells(const float* wav_dev, int64_t wav_samples, const avexhip_regions_recording* rec_host,
+                          const avexhip_regions_recording* rec_dev, int n_rec, int hop, int lo, int hi, const float* thr_dev,
+                          const float* tables_dev, int64_t total_frames, int32_t* cells_dev, int32_t* nonfinite_dev, void* stream);
+int avexhip_regions_pack(const uint8_t* mask_dev, int64_t total_frames, int32_t* cells_dev, void* stream);
+int avexhip_regions_count(const int32_t* cells_dev, int64_t total_frames, void* frame_ws_dev, size_t frame_ws_bytes, int64_t* counts_dev,
+                          void* stream);
+/* frame_offsets: [n_rec + 1] int64, the first frame of each recording and total_frames, on the host (checked) and on the device */
+int avexhip_regions_label(const int32_t* cells_dev, const int64_t* frame_offsets_host, const int64_t* frame_offsets_dev, int n_rec,
+                          int64_t total_frames, int64_t n_cells, const avexhip_regions_rule* rule, const void* frame_ws_dev,
+                          size_t frame_ws_bytes, void* cell_ws_dev, size_t cell_ws_bytes, int64_t* counts_dev, void* stream);
+int avexhip_regions_rows(int64_t n_cells, int64_t n_kept, const avexhip_regions_rule* rule, const void* cell_ws_dev, size_t cell_ws_bytes,
+                         const int64_t* counts_dev, int32_t* rows_dev, void* stream);
 
 /* T5 bidirectional bucket of a relative position (backbone.py:438-473).  Pure host function. */
 int avexhip_rel_bucket(int rel, int num_buckets, int max_distance);
