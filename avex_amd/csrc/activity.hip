@@ -6,10 +6,10 @@
 //   activity_count_kernel    per (window, band) the frames with E > max(floor, floor_min) * ratio, and the largest energy
 //   activity_select_kernel   window_select_kernel's condition and one more on those counts, through the same block_compact (block_prims.h)
 // The transform is shared with fbank.hip (fft512.h): one wave64 per PAIR of frames packed as z = a + i b.  The walk over the frames is
-// shared with soundscape.hip (rec_frames.h: the frame count, the workgroup's recording, the span and twiddle staging, the refusals of
-// a recording, a hop and a bin band): a workgroup takes eight consecutive frames of ONE recording and stages their span ((8 - 1) hop +
-// 512 samples) in LDS once, so overlapping frames cost one HBM read per sample; pairs are (2 i, 2 i + 1) of the recording, so a frame's
-// energies depend on its recording and the hop alone.
+// shared with soundscape.hip, measure.hip and regions.hip (rec_frames.h: the frame count, the workgroup's recording, the span and
+// twiddle staging, the refusals of a table, a recording, a hop and a bin band): a workgroup takes eight consecutive frames of ONE
+// recording and stages their span ((8 - 1) hop + 512 samples) in LDS once, so overlapping frames cost one HBM read per sample; pairs
+// are (2 i, 2 i + 1) of the recording, so a frame's energies depend on its recording and the hop alone.
 #include <math.h>
 
 #include "block_prims.h"
@@ -242,10 +242,7 @@ __global__ __launch_bounds__(kActSelectThreads) void activity_select_kernel(cons
 // What every entry point refuses in the recording table; *blocks_out = the workgroups of the frames kernel.  wav_samples < 0: no buffer to check.
 int activity_recordings_check(const char* what, const avexhip_activity_recording* rec_host, const avexhip_activity_recording* rec_dev, int n_rec, int hop,
                               int64_t wav_samples, int64_t total_frames, int64_t* blocks_out) {
-    AVX_REQUIRE(rec_host && rec_dev, "%s: null argument", what);
-    AVX_REQUIRE(((uintptr_t)rec_dev & 7) == 0, "%s: rec_dev must be 8-byte aligned", what);
-    AVX_REQUIRE(n_rec >= 1, "%s: n_rec=%d", what, n_rec);
-    AVXH_TRY(hop_check(what, hop));
+    AVXH_TRY(table_check(what, rec_host, rec_dev, "rec_dev", n_rec, true, hop));
     int64_t frames = 0, blocks = 0;
     for (int r = 0; r < n_rec; ++r) {
         const avexhip_activity_recording& it = rec_host[r];
@@ -275,7 +272,7 @@ extern "C" int avexhip_activity_frames(const float* wav_dev, int64_t wav_samples
                                        const avexhip_activity_recording* rec_dev, int n_rec, int hop, const int32_t* bands_host, int n_bands,
                                        const float* tables_dev, int64_t total_frames, float* energy_dev, void* stream) {
     AVX_REQUIRE(wav_dev && bands_host && tables_dev, "activity_frames: null argument");
-    AVX_REQUIRE(((uintptr_t)wav_dev & 15) == 0 && ((uintptr_t)tables_dev & 15) == 0 && ((uintptr_t)energy_dev & 3) == 0,
+    AVX_REQUIRE(aligned(wav_dev, 16) && aligned(tables_dev, 16) && aligned(energy_dev, 4),
                 "activity_frames: wav_dev and tables_dev must be 16-byte aligned, energy_dev 4-byte aligned");
     AVX_REQUIRE(wav_samples >= 1, "activity_frames: wav_samples=%lld", (long long)wav_samples);
     AVXH_TRY(activity_bands_check("activity_frames", n_bands));
@@ -301,7 +298,7 @@ extern "C" int avexhip_activity_floor(const float* energy_dev, int64_t total_fra
                                       const avexhip_activity_recording* rec_dev, int n_rec, int hop, int n_bands, float* floor_dev, int32_t* nonfinite_dev,
                                       void* stream) {
     AVX_REQUIRE(floor_dev && nonfinite_dev, "activity_floor: null argument");
-    AVX_REQUIRE(((uintptr_t)energy_dev & 3) == 0 && ((uintptr_t)floor_dev & 3) == 0 && ((uintptr_t)nonfinite_dev & 3) == 0,
+    AVX_REQUIRE(aligned(energy_dev, 4) && aligned(floor_dev, 4) && aligned(nonfinite_dev, 4),
                 "activity_floor: energy_dev, floor_dev and nonfinite_dev must be 4-byte aligned");
     AVXH_TRY(activity_bands_check("activity_floor", n_bands));
     AVXH_TRY(activity_recordings_check("activity_floor", rec_host, rec_dev, n_rec, hop, -1, total_frames, nullptr));
@@ -317,8 +314,8 @@ extern "C" int avexhip_activity_count(const avexhip_window* win_host, const avex
                                       const float* energy_dev, int64_t total_frames, const float* floor_dev, int n_bands, float floor_min, float ratio,
                                       int32_t* n_frames_dev, int32_t* active_dev, float* max_energy_dev, void* stream) {
     AVX_REQUIRE(win_host && win_dev && win_rec_host && win_rec_dev && floor_dev && n_frames_dev && active_dev && max_energy_dev, "activity_count: null argument");
-    AVX_REQUIRE(((uintptr_t)win_dev & 7) == 0 && ((uintptr_t)win_rec_dev & 3) == 0 && ((uintptr_t)energy_dev & 3) == 0 && ((uintptr_t)floor_dev & 3) == 0 &&
-                    ((uintptr_t)n_frames_dev & 3) == 0 && ((uintptr_t)active_dev & 3) == 0 && ((uintptr_t)max_energy_dev & 3) == 0,
+    AVX_REQUIRE(aligned(win_dev, 8) && aligned(win_rec_dev, 4) && aligned(energy_dev, 4) && aligned(floor_dev, 4) && aligned(n_frames_dev, 4) &&
+                    aligned(active_dev, 4) && aligned(max_energy_dev, 4),
                 "activity_count: win_dev must be 8-byte aligned, the other device arrays 4-byte aligned");
     AVX_REQUIRE(n_win >= 1, "activity_count: n_win=%d", n_win);
     AVX_REQUIRE(!(floor_min != floor_min) && !(ratio != ratio) && floor_min >= 0.f && ratio >= 0.f, "activity_count: floor_min=%g ratio=%g: numbers >= 0 expected (not NaN)",
@@ -344,8 +341,8 @@ extern "C" int avexhip_activity_select(const avexhip_window* win_dev, const doub
                                        int n_bands, int min_active_frames, int mode, double thr_energy, float thr_peak, int32_t* kept_dev, int32_t* count_dev,
                                        void* stream) {
     AVX_REQUIRE(win_dev && energy_dev && peak_dev && active_dev && kept_dev && count_dev, "activity_select: null argument");
-    AVX_REQUIRE(((uintptr_t)win_dev & 7) == 0 && ((uintptr_t)energy_dev & 7) == 0 && ((uintptr_t)peak_dev & 3) == 0 && ((uintptr_t)active_dev & 3) == 0 &&
-                    ((uintptr_t)kept_dev & 3) == 0 && ((uintptr_t)count_dev & 3) == 0,
+    AVX_REQUIRE(aligned(win_dev, 8) && aligned(energy_dev, 8) && aligned(peak_dev, 4) && aligned(active_dev, 4) && aligned(kept_dev, 4) &&
+                    aligned(count_dev, 4),
                 "activity_select: win_dev and energy_dev must be 8-byte aligned, the other device arrays 4-byte aligned");
     AVX_REQUIRE(n_win >= 1, "activity_select: n_win=%d", n_win);
     AVXH_TRY(activity_bands_check("activity_select", n_bands));

@@ -1,7 +1,8 @@
 // The workgroup primitives of the kernels that walk, count and order things -- events, annotations, density, windows, activity,
 // soundscape; retrieval, search, clustering, silhouette: scan, compaction, reductions, the bitonic sort in LDS and the unordered append.
 // Ballots, shuffles and LDS words in a fixed order: no result depends on timing, except the positions wave_append hands out (below).
-// Every thread of the workgroup must make a block_* call (barriers inside).
+// Every thread of the workgroup must make a block_* call (barriers inside).  The prefix over more items than a workgroup holds, with its
+// three kernels and their launcher, is prefix_count.h.
 #pragma once
 #include "common.h"
 

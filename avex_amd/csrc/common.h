@@ -288,6 +288,9 @@ struct BlockSum {
 struct BlockMax {
     template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; }
 };
+struct BlockMin {
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; }
+};
 // The xor butterfly 32 .. 1 over the 64 lanes of a wave, v = op(v, the partner lane's v) at every step: every lane ends with the same
 // value when op(a, b) == op(b, a) bit for bit (sums, maxima).  Every lane of the wave must make the call.
 template <typename T, typename Op> static __device__ __forceinline__ T wave_reduce(T v, Op op) {
@@ -347,6 +350,9 @@ template <typename T> static inline T* take(char*& p, size_t count, size_t step 
     p += (count * sizeof(T) + step - 1) & ~(step - 1);
     return r;
 }
+
+// p lies on a multiple of a bytes (a power of two); a null pointer does
+static inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 #define AVX_LAUNCH_CHECK()                                                             \
     do {                                                                                     \

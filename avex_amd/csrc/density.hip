@@ -22,8 +22,8 @@
 //   dens_apply_kernel     core rows: label = min(label, next), the changed flag
 //   dens_compress_kernel  pointer jumping to the fixed point: every core row follows label[label[..]] down to the row that points at
 //                         itself and takes it.  Labels only decrease and a label is never larger than its row, so the chains end.
-//   dens_root_count / dens_block_scan / dens_number   roots (label == own row) counted per 1 024 rows, an exclusive prefix over the
-//                         blocks, then the rank inside the block: cluster numbers in the order of the lowest core row, by counting
+//   prefix_count          (prefix_count.h, shared with regions.hip) roots (label == own row) counted per 1 024 rows, an exclusive prefix
+//                         over the blocks, then the rank inside the block: cluster numbers in the order of the lowest core row, by counting
 //   dens_labels_kernel    core row: the number of its root; other row: the number of next[row], the smallest root among its core
 //                         neighbours as the last (unchanged) round left it, or -1
 //   dens_sizes_kernel     per cluster its size (atomicAdd) and the key (n_neighbors << 32) | (0xFFFFFFFF - row) of its best core row
@@ -38,6 +38,7 @@
 // Limits: n <= 2^31 - 1 rows, dpad % 32 == 0, a block of at most 2^22 rows.
 #include "block_prims.h"
 #include "f32_tile.h"
+#include "prefix_count.h"
 
 namespace {
 
@@ -45,14 +46,13 @@ constexpr int DN_NONE = 0x7fffffff;                              // "no label": 
 constexpr int64_t DN_MAX_N = 0x7fffffffll;
 constexpr int DN_MAX_BLOCK = 1 << 22;                            // rows of one block: 32 768 row tiles, the second grid dimension
 constexpr int DN_LDS_BYTES = FT_LDS_BYTES + 2 * FT_BM * 4;       // the operand buffers, and behind them one integer per (column wave, row)
-constexpr int DN_SCAN_ROWS = 1024;                               // rows per block of the prefix count
 constexpr float DN_FLT_MAX = 3.4028234663852886e38f;
 
 struct Workspace {
     float* nrm;                  // [n] squared norm from the diagonal; not finite: the row is outside the graph
     int32_t *count, *label, *next, *cid;      // [n] each
     unsigned long long* keys;    // [n] exemplar keys, by cluster
-    int32_t* block;              // [ceil(n / 1024)] roots per block, then their exclusive prefix
+    int32_t* block;              // [prefix_count_blocks(n)] roots per block, then their exclusive prefix
     int32_t* flags;              // [0] rows outside the graph, [1] clusters
     size_t bytes;
 };
@@ -66,7 +66,7 @@ static Workspace carve(void* ws, int64_t n) {
     w.next = take<int32_t>(p, (size_t)n);
     w.cid = take<int32_t>(p, (size_t)n);
     w.keys = take<unsigned long long>(p, (size_t)n);
-    w.block = take<int32_t>(p, (size_t)((n + DN_SCAN_ROWS - 1) / DN_SCAN_ROWS));
+    w.block = take<int32_t>(p, (size_t)prefix_count_blocks(n));
     w.flags = take<int32_t>(p, 4);
     w.bytes = (size_t)(p - (char*)ws);
     return w;
@@ -248,68 +248,15 @@ __global__ __launch_bounds__(256) void dens_compress_kernel(int64_t n, int32_t* 
     if (r != l) __atomic_store_n(label + i, r, __ATOMIC_RELAXED);
 }
 
-__global__ __launch_bounds__(256) void dens_root_count_kernel(int64_t n, const int32_t* __restrict__ label, int32_t* __restrict__ block) {
-    const int64_t b0 = (int64_t)blockIdx.x * DN_SCAN_ROWS + 4 * threadIdx.x;
-    int c = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (b0 + e < n && label[b0 + e] == b0 + e) ++c;
-    __shared__ int wt[4];
-    int before, all;
-    block_scan<4>(c, 0, BlockSum(), wt, &before, &all);
-    if (threadIdx.x == 0) block[blockIdx.x] = all;
-}
-
-// one workgroup: block[b] -> the number of roots in the blocks before b; flags[1] = all of them
-__global__ __launch_bounds__(256) void dens_block_scan_kernel(int64_t n_blocks, int32_t* __restrict__ block, int32_t* __restrict__ flags) {
-    __shared__ int part[256];
-    const int tid = threadIdx.x;
-    const int64_t per = (n_blocks + 255) / 256;
-    const int64_t lo = per * tid, hi = lo + per < n_blocks ? lo + per : n_blocks;
-    int s = 0;
-    for (int64_t b = lo; b < hi; ++b) s += block[b];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int k = 0; k < 256; ++k) {
-            const int v = part[k];
-            part[k] = run;
-            run += v;
-        }
-        flags[1] = run;
-    }
-    __syncthreads();
-    int run = part[tid];
-    for (int64_t b = lo; b < hi; ++b) {
-        const int v = block[b];
-        block[b] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(256) void dens_number_kernel(int64_t n, const int32_t* __restrict__ label, const int32_t* __restrict__ block,
-                                                          int32_t* __restrict__ cid) {
-    __shared__ int wt[4];
-    const int tid = threadIdx.x;
-    const int64_t b0 = (int64_t)blockIdx.x * DN_SCAN_ROWS + 4 * tid;
-    bool root[4];
-    int c = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        root[e] = b0 + e < n && label[b0 + e] == b0 + e;
-        c += root[e] ? 1 : 0;
-    }
-    int before, all;
-    block_scan<4>(c, 0, BlockSum(), wt, &before, &all);      // the roots of the threads below this one
-    int run = block[blockIdx.x] + before;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (b0 + e < n) {
-            cid[b0 + e] = root[e] ? run : -1;
-            run += root[e] ? 1 : 0;
-        }
-}
+// the cluster numbers by counting (prefix_count.h): a root counts 1, takes its rank; every other row takes -1
+struct DnIsRoot {
+    const int32_t* label;
+    __device__ __forceinline__ bool operator()(int64_t i) const { return label[i] == i; }
+};
+struct DnStoreCid {
+    int32_t* cid;
+    __device__ __forceinline__ void operator()(int64_t i, int rank, bool root) const { cid[i] = root ? rank : -1; }
+};
 
 __global__ __launch_bounds__(256) void dens_labels_kernel(int64_t n, const int32_t* __restrict__ label, const int32_t* __restrict__ next,
                                                           const int32_t* __restrict__ cid, const int32_t* __restrict__ count, const int32_t* __restrict__ flags,
@@ -501,13 +448,7 @@ extern "C" int avexhip_density_labels(const avexhip_density_args* a, int32_t* la
     AVXH_TRY(check_args(a, "density_labels", &w));
     AVX_REQUIRE(labels_out_dev && core_out_dev && n_neighbors_out_dev && summary_out_dev, "density_labels: null output");
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n_blocks = (a->n + DN_SCAN_ROWS - 1) / DN_SCAN_ROWS;
-    dens_root_count_kernel<<<dim3((unsigned)n_blocks), dim3(256), 0, s>>>(a->n, w.label, w.block);
-    AVX_LAUNCH_CHECK();
-    dens_block_scan_kernel<<<dim3(1), dim3(256), 0, s>>>(n_blocks, w.block, w.flags);
-    AVX_LAUNCH_CHECK();
-    dens_number_kernel<<<dim3((unsigned)n_blocks), dim3(256), 0, s>>>(a->n, w.label, w.block, w.cid);
-    AVX_LAUNCH_CHECK();
+    AVXH_TRY(prefix_count<int32_t>(a->n, PrefixHostN{a->n}, DnIsRoot{w.label}, w.block, w.flags + 1, DnStoreCid{w.cid}, s));
     dens_labels_kernel<<<dim3(blocks256(a->n)), dim3(256), 0, s>>>(a->n, w.label, w.next, w.cid, w.count, w.flags, labels_out_dev, core_out_dev,
                                                                   n_neighbors_out_dev, summary_out_dev);
     AVX_LAUNCH_CHECK();

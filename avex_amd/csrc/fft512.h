@@ -1,4 +1,5 @@
-// The 512-point complex FFT of one wave64, shared by fbank_kernel (fbank.hip) and activity_frames_kernel (activity.hip).
+// The 512-point complex FFT of one wave64, shared by fbank_kernel (fbank.hip), activity_frames_kernel (activity.hip) and
+// wave_frame_power (frame_power.h).
 //
 // CONDITION: every translation unit that includes this header must be listed in avex_amd/build.py's EXTRA_FLAGS with
 // -fno-slp-vectorize.  hipcc's SLP vectoriser turns the float2 arithmetic below into packed-fp32 instructions whose second source swaps

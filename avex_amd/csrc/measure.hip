@@ -1,6 +1,6 @@
 // Event measurements (ABI 24): the time and frequency extent of each event, from the resident waveform of windows.hip and the frames of
-// soundscape.hip (512 samples every `hop`, periodic Hann, no padding, ONE frame per transform through fft512_wave: P[f, k] is the same
-// function of the frame's 512 samples as in soundscape_stats_kernel).  An event is a box: the samples [s0, s1) of one recording and the
+// soundscape.hip (512 samples every `hop`, periodic Hann, no padding, ONE frame per transform: P[f, k] comes from wave_frame_power of
+// frame_power.h, the text soundscape_stats_kernel runs, so it is the same bits).  An event is a box: the samples [s0, s1) of one recording and the
 // bins [lo, hi); its frames are those that lie wholly inside [s0, s1).
 //   measure_frames_kernel   a run of up to 64 consecutive frames of ONE event per workgroup: |X|^2 per frame and bin, per bin the sum
 //                           over the run in frame order (one partial row per run, with the run's non-finite frames), and per frame
@@ -11,21 +11,17 @@
 //                           envelope in chunks of 256 frames with a carry (the total, then the quantile frames) and its peak
 // No atomics, sums in one fixed order: an event's numbers depend on its recording's samples, its box, hop, the quantile levels and
 // its noise row alone -- the same bits in any company, in any order of the events and on every run.  The walk over the frames is
-// rec_frames.h's (the frame count, the event of a run, the span and twiddle staging, the refusals of a recording, a hop and a bin
-// band); every partial row, envelope value and frame index follows from the checked table.
+// rec_frames.h's (the frame count, the event of a run, the span and twiddle staging, the refusals of a table, a recording, a hop, a bin
+// band and a short buffer of partials); every partial row, envelope value and frame index follows from the checked table.
 #include <math.h>
 
 #include "block_prims.h"
 #include "common.h"
-#include "fft512.h"
-#include "rec_frames.h"
+#include "frame_power.h"
 
 namespace {
 
 constexpr int kMsRun = AVEXHIP_MEASURE_RUN_FRAMES;               // frames per workgroup of the frames kernel
-constexpr int kMsStep = 4;                                       // frames per step: one per wave
-constexpr int kMsSpan = (kMsStep - 1) * 512 + kRecFrame + 8;      // floats of LDS for a step's span at hop 512, up to 3 lead-in samples, a whole last chunk
-constexpr int kMsPRow = 260;
 // a partial row, in 4-byte words: the 257 sums, the run's non-finite frames
 constexpr int kMsPartBad = kRecBins, kMsPartWords = kRecBins + 1;
 constexpr int kMsNone = 0x7fffffff;                              // "no index": the identity of the minimum over indices
@@ -43,11 +39,9 @@ __host__ __device__ __forceinline__ int64_t ms_frames(int64_t s0, int64_t s1, in
 // (cos, -sin)(2 pi k / 512).  LDS: 8 224 + 18 432 + 4 096 + 4 160 + 16 bytes = 34 928.
 __global__ __launch_bounds__(256) void measure_frames_kernel(const float* __restrict__ wav, const avexhip_measure_event* __restrict__ ev, int n_ev, int hop,
                                                              const float* __restrict__ tables, float* __restrict__ partials, float* __restrict__ envelope) {
-    __shared__ __attribute__((aligned(16))) float span[kMsSpan];
-    __shared__ float2 zbuf[kMsStep][8 * ZROW];
-    __shared__ float2 tw[512];
-    __shared__ float prow[kMsStep][kMsPRow];
-    __shared__ int bad_of[kMsStep];
+    const FramePowerLds lds = frame_power_lds();
+    __shared__ float prow[kFpStep][kFpPRow];
+    __shared__ int bad_of[kFpStep];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int e = last_at_most(n_ev, (int)blockIdx.x, [&](int i) { return ev[i].first_run; });
     const avexhip_measure_event it = ev[e];
@@ -57,7 +51,7 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(const float* __rest
     const int64_t f0 = ms_first_frame(it.s0, hop) + in_ev;       // the run's first frame, counted inside its recording
     const int lo = it.lo, hi = it.hi;
 
-    stage_twiddles(tw, tables);
+    stage_twiddles(lds.tw, tables);
 
     // thread t owns bin t; thread 0 bin 256 as well
     const int n_own = tid == 0 ? 2 : 1;
@@ -65,39 +59,21 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(const float* __rest
     int n_bad = 0;
 
     const int64_t r_lo = it.base, r_hi = it.base + it.n_samples;
-    for (int st = 0; st < nf; st += kMsStep) {                   // (block-uniform trip count)
-        const int ns = nf - st < kMsStep ? nf - st : kMsStep;
+    for (int st = 0; st < nf; st += kFpStep) {                   // (block-uniform trip count)
+        const int ns = nf - st < kFpStep ? nf - st : kFpStep;
         __syncthreads();                                         // the step before has read span and prow
         // ---- the span of the step's frames -> LDS: lead <= 3, (ns - 1) hop + 512 <= 3 * 512 + 512 ---------------------------------------
-        const int lead = stage_span(span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
+        const int lead = stage_span(lds.span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
         __syncthreads();
 
         if (wave < ns) {                                         // (wave-uniform; only wave syncs inside)
-            const float* src = span + lead + wave * hop;
-            float2 x[8];
-            bool nonfin = false;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float v = src[lane + 64 * q];
-                nonfin |= non_finite(v);
-                x[q] = make_float2(v * tables[lane + 64 * q], 0.f);
-            }
-            const bool bad = __any(nonfin);
-            float2* z = zbuf[wave];
-            fft512_wave(x, z, tw, lane);                         // X[k] at z[k]
             // A lane adds its bins in increasing order, the wave its lanes by a butterfly: a fixed order, the same for every launch.
             // A bin outside the band adds +0, which changes no bit of the sum.
             float total = 0.f;
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const int k = lane + 64 * q;
-                if (k < kRecBins) {
-                    const float2 zk = z[k];
-                    const float p = bad ? NAN : zk.x * zk.x + zk.y * zk.y;
-                    prow[wave][k] = p;
-                    total += (k >= lo && k < hi) ? p : 0.f;
-                }
-            }
+            const bool bad = wave_frame_power(lds.span + lead + wave * hop, tables, lds.zbuf[wave], lds.tw, lane, [&](int, int k, float p) {
+                prow[wave][k] = p;
+                total += (k >= lo && k < hi) ? p : 0.f;
+            });
             total = wave_sum(total);
             if (lane == 0) {
                 envelope[it.env_offset + in_ev + st + wave] = total;
@@ -122,10 +98,6 @@ __global__ __launch_bounds__(256) void measure_frames_kernel(const float* __rest
         ((int*)part)[kMsPartBad] = n_bad;
     }
 }
-
-struct BlockMin {
-    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; }
-};
 
 // d = a value minus its noise: what is left of it, never below 0; a NaN (from a NaN noise row) stays one
 __device__ __forceinline__ double ms_left(double d) { return d <= 0.0 ? 0.0 : d; }
@@ -257,9 +229,7 @@ __global__ __launch_bounds__(256) void measure_reduce_kernel(const avexhip_measu
 // What both entry points refuse in the event table.  wav_samples < 0: no buffer to check; n_rec < 0: no noise rows to index.
 int measure_events_check(const char* what, const avexhip_measure_event* ev_host, const avexhip_measure_event* ev_dev, int n_ev, int hop, int64_t wav_samples,
                          int n_rec, int64_t total_frames, int64_t total_runs) {
-    AVX_REQUIRE(ev_host && ev_dev, "%s: null argument", what);
-    AVX_REQUIRE(((uintptr_t)ev_dev & 7) == 0, "%s: ev_dev must be 8-byte aligned", what);
-    AVXH_TRY(hop_check(what, hop));
+    AVXH_TRY(table_check(what, ev_host, ev_dev, "ev_dev", n_ev, false, hop));      // (the entry points return before this for n_ev == 0)
     int64_t frames = 0, runs = 0;
     for (int e = 0; e < n_ev; ++e) {
         const avexhip_measure_event& it = ev_host[e];
@@ -283,8 +253,6 @@ int measure_events_check(const char* what, const avexhip_measure_event* ev_host,
     return AVEXHIP_OK;
 }
 
-bool ms_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" size_t avexhip_measure_partials_bytes(int64_t n_runs) {
@@ -298,16 +266,13 @@ extern "C" int avexhip_measure_frames(const float* wav_dev, int64_t wav_samples,
     AVX_REQUIRE(n_events >= 0, "measure_frames: n_events=%d", n_events);
     if (n_events == 0) return AVEXHIP_OK;                        // no event at all
     AVX_REQUIRE(wav_dev && tables_dev, "measure_frames: null argument");
-    AVX_REQUIRE(ms_aligned(wav_dev, 16) && ms_aligned(tables_dev, 16) && ms_aligned(partials_dev, 4) && ms_aligned(envelope_dev, 4),
+    AVX_REQUIRE(aligned(wav_dev, 16) && aligned(tables_dev, 16) && aligned(partials_dev, 4) && aligned(envelope_dev, 4),
                 "measure_frames: wav_dev and tables_dev must be 16-byte aligned, partials_dev and envelope_dev 4-byte aligned");
     AVX_REQUIRE(wav_samples >= 1, "measure_frames: wav_samples=%lld", (long long)wav_samples);
     AVXH_TRY(measure_events_check("measure_frames", ev_host, ev_dev, n_events, hop, wav_samples, -1, total_frames, total_runs));
     if (total_runs == 0) return AVEXHIP_OK;                      // no event holds a frame
     AVX_REQUIRE(partials_dev && envelope_dev, "measure_frames: null argument");
-    if (partials_bytes < avexhip_measure_partials_bytes(total_runs)) {
-        avexhip_set_error("measure_frames: partials_bytes=%zu, %lld runs need %zu", partials_bytes, (long long)total_runs, avexhip_measure_partials_bytes(total_runs));
-        return AVEXHIP_ERR_WORKSPACE;
-    }
+    AVXH_TRY(partials_check("measure_frames", partials_bytes, total_runs, avexhip_measure_partials_bytes(total_runs)));
     hipLaunchKernelGGL(measure_frames_kernel, dim3((unsigned)total_runs), dim3(256), 0, (hipStream_t)stream, wav_dev, ev_dev, n_events, hop, tables_dev,
                        (float*)partials_dev, envelope_dev);
     AVX_LAUNCH_CHECK();
@@ -325,16 +290,13 @@ extern "C" int avexhip_measure_reduce(const avexhip_measure_event* ev_host, cons
     AVX_REQUIRE(noise_dev ? n_rec >= 1 : true, "measure_reduce: n_rec=%d rows of noise", n_rec);
     const void* cols4[] = {out->n_frames, out->nonfinite, out->low_bin, out->centre_bin, out->high_bin, out->peak_bin, out->low_frame, out->centre_frame,
                            out->high_frame, out->peak_frame};
-    for (const void* p : cols4) AVX_REQUIRE(p && ms_aligned(p, 4), "measure_reduce: a null or misaligned result column");
-    AVX_REQUIRE(out->energy && out->snr_db && ms_aligned(out->energy, 8) && ms_aligned(out->snr_db, 8), "measure_reduce: a null or misaligned result column");
-    AVX_REQUIRE(ms_aligned(partials_dev, 4) && ms_aligned(envelope_dev, 4) && ms_aligned(noise_dev, 4) && ms_aligned(spectrum_dev, 4),
+    for (const void* p : cols4) AVX_REQUIRE(p && aligned(p, 4), "measure_reduce: a null or misaligned result column");
+    AVX_REQUIRE(out->energy && out->snr_db && aligned(out->energy, 8) && aligned(out->snr_db, 8), "measure_reduce: a null or misaligned result column");
+    AVX_REQUIRE(aligned(partials_dev, 4) && aligned(envelope_dev, 4) && aligned(noise_dev, 4) && aligned(spectrum_dev, 4),
                 "measure_reduce: the device arrays must be 4-byte aligned");
     AVXH_TRY(measure_events_check("measure_reduce", ev_host, ev_dev, n_events, hop, -1, noise_dev ? n_rec : -1, total_frames, total_runs));
     AVX_REQUIRE(total_runs == 0 || (partials_dev && envelope_dev), "measure_reduce: null argument");
-    if (partials_bytes < avexhip_measure_partials_bytes(total_runs)) {
-        avexhip_set_error("measure_reduce: partials_bytes=%zu, %lld runs need %zu", partials_bytes, (long long)total_runs, avexhip_measure_partials_bytes(total_runs));
-        return AVEXHIP_ERR_WORKSPACE;
-    }
+    AVXH_TRY(partials_check("measure_reduce", partials_bytes, total_runs, avexhip_measure_partials_bytes(total_runs)));
     hipLaunchKernelGGL(measure_reduce_kernel, dim3((unsigned)n_events), dim3(256), 0, (hipStream_t)stream, ev_dev, hop, (const float*)partials_dev, envelope_dev,
                        noise_dev, q_lo, q_c, q_hi, spectrum_dev, *out);
     AVX_LAUNCH_CHECK();

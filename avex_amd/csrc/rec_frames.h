@@ -1,5 +1,5 @@
-// The walk over the 512-sample frames of resident recordings, shared by activity_frames_kernel (activity.hip) and the three kernels of
-// soundscape.hip; windows.hip takes the recording refusal alone.
+// The walk over the 512-sample frames of resident recordings, shared by activity_frames_kernel (activity.hip) and, through
+// frame_power.h, the kernels of soundscape.hip, measure.hip and regions.hip; windows.hip takes the recording refusal alone.
 //
 // CONTRACT.  A recording is `n_samples` samples of one 16-byte aligned fp32 buffer from sample `base` on; it has frames_of(n_samples,
 // hop) frames, frame f its samples [f hop, f hop + 512), no padding.  The frames, and whatever a kernel counts in them (workgroups,
@@ -10,7 +10,9 @@
 // caller places its own before the span or the twiddles are read (and before a span that is still being read is staged again).
 //
 // Nothing here includes fft512.h, so a file that needs the walk or the refusals alone stays out of build.py's EXTRA_FLAGS.  Windowing,
-// packing (a pair of frames per wave, or one), power and sums belong to each kernel.
+// the transform and the power of ONE frame per wave are frame_power.h's; activity_frames_kernel packs a pair and keeps its own.  The
+// host side also holds what the table checks of the four files open with (table_check) and the refusal of a short buffer of run
+// partials (partials_check): one text each.
 #pragma once
 #include "common.h"
 
@@ -79,6 +81,23 @@ inline int recording_check(const char* what, int row, int64_t n_samples, int64_t
 inline int hop_check(const char* what, int hop) {
     AVX_REQUIRE(hop >= AVEXHIP_ACTIVITY_MIN_HOP && hop <= kRecFrame, "%s: hop=%d outside %d..%d", what, hop, AVEXHIP_ACTIVITY_MIN_HOP, kRecFrame);
     return AVEXHIP_OK;
+}
+
+// The first refusals of every table check, in this order: a null table, a device table off its 8 bytes (`dev_name` names it), fewer than
+// one row (`need_rows`: false where the caller has returned for an empty table before), a hop outside its range.  The walk over the
+// rows stays with the caller: what it counts differs (blocks, segments and runs, runs, events).
+inline int table_check(const char* what, const void* host, const void* dev, const char* dev_name, int n_rec, bool need_rows, int hop) {
+    AVX_REQUIRE(host && dev, "%s: null argument", what);
+    AVX_REQUIRE(aligned(dev, 8), "%s: %s must be 8-byte aligned", what, dev_name);
+    AVX_REQUIRE(!need_rows || n_rec >= 1, "%s: n_rec=%d", what, n_rec);
+    return hop_check(what, hop);
+}
+
+// a buffer of run partials that is too small for the table's runs
+inline int partials_check(const char* what, size_t have, int64_t runs, size_t need) {
+    if (have >= need) return AVEXHIP_OK;
+    avexhip_set_error("%s: partials_bytes=%zu, %lld runs need %zu", what, have, (long long)runs, need);
+    return AVEXHIP_ERR_WORKSPACE;
 }
 
 // bins lo .. hi - 1 of the band `name`, or `name number` with number >= 0

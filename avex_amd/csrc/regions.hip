@@ -1,17 +1,16 @@
 // Sound-event regions (ABI 25): the spectrogram cells that stand out of a per-recording threshold spectrum, joined into connected
 // regions, one time-frequency box per region -- from the resident waveform of windows.hip and the frames of soundscape.hip.  The
 // [frames, 257] spectrogram is never written: 9 words of cell bits per frame are, one integer per frame and nine per set cell.
-//   regions_cells_kernel    a run of up to 64 consecutive frames of ONE recording per workgroup, the walk, span staging and
-//                           one-frame-per-wave transform of soundscape_stats_kernel (the same P[f, k], bit for bit); the recording's
-//                           threshold row in registers, one strict compare per (frame, bin) inside the band, five wave ballots -> the 9
-//                           words of the frame; the recording's non-finite frames by one integer atomicAdd per wave
+//   regions_cells_kernel    a run of up to 64 consecutive frames of ONE recording per workgroup; the walk and span staging of
+//                           rec_frames.h and wave_frame_power (frame_power.h), the text soundscape_stats_kernel runs: the same P[f, k],
+//                           bit for bit; the recording's threshold row in registers, one strict compare per (frame, bin) inside the
+//                           band, five wave ballots -> the 9 words of the frame; the recording's non-finite frames by one integer
+//                           atomicAdd per wave
 //   regions_pack_kernel     the same words from a [frames, 257] mask of bytes (label_cells: a mask from anywhere)
-//   rg_scan_count / rg_scan_blocks / rg_scan_apply   an exclusive prefix of one small integer per item by counting: per 1 024 items a
-//                           sum, one workgroup over the sums (the total in 64 bits), then the rank inside the block -- the scheme of
-//                           dens_root_count / dens_block_scan / dens_number.  Used three times: the set cells of each frame (the compact
-//                           number of a set cell is offset[f] + popcount(the frame's bits below k), monotone in (recording, frame, bin)),
-//                           the roots (region numbers in the order of the smallest cell, no sort), the kept regions (a compaction that
-//                           keeps order)
+//   prefix_count            (prefix_count.h, shared with density.hip) an exclusive prefix of one small integer per item by counting,
+//                           the total in 64 bits.  Used three times: the set cells of each frame (the compact number of a set cell
+//                           is offset[f] + popcount(the frame's bits below k), monotone in (recording, frame, bin)), the roots (region
+//                           numbers in the order of the smallest cell, no sort), the kept regions (a compaction that keeps order)
 //   regions_init_kernel     parent[i] = i; the region accumulators' identities
 //   regions_union_kernel    one wave per frame.  A set cell looks at its FORWARD half-neighbourhood inside its recording -- the same
 //                           frame at dk = 1 .. rk, the frames f + 1 .. f + rt at dk = -rk .. rk -- in the bit words, and unites itself
@@ -34,31 +33,22 @@
 // Limits: < 2^31 frames, < 2^31 set cells.
 #include "block_prims.h"
 #include "common.h"
-#include "fft512.h"
-#include "rec_frames.h"
+#include "frame_power.h"
+#include "prefix_count.h"
 
 namespace {
 
 constexpr int kRgRun = AVEXHIP_REGIONS_RUN_FRAMES;               // frames per workgroup of the cells kernel
-constexpr int kRgStep = 4;                                       // frames per step: one per wave
-constexpr int kRgSpan = (kRgStep - 1) * 512 + kRecFrame + 8;      // as soundscape.hip's kSsSpan
 constexpr int kRgWords = AVEXHIP_REGIONS_WORDS;
-constexpr int kRgScan = 1024;                                    // items per block of a prefix count
 constexpr int64_t kRgMax = 0x7fffffffll;
 constexpr int kRgNone = 0x7fffffff;
-
-struct RgMin {
-    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; }
-};
 
 // grid: one workgroup per run (avexhip_regions_recording::first_run numbers them), 256 threads.  LDS: 8 224 + 18 432 + 4 096 bytes.
 __global__ __launch_bounds__(256) void regions_cells_kernel(const float* __restrict__ wav, const avexhip_regions_recording* __restrict__ rec, int n_rec, int hop,
                                                             int lo, int hi, const float* __restrict__ thr, const float* __restrict__ tables,
                                                             int32_t* __restrict__ cells, int32_t* __restrict__ nonfinite) {
-    __shared__ __attribute__((aligned(16))) float span[kRgSpan];
-    __shared__ float2 zbuf[kRgStep][8 * ZROW];
-    __shared__ float2 tw[512];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const FramePowerLds lds = frame_power_lds();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = last_at_most(n_rec, (int)blockIdx.x, [&](int i) { return rec[i].first_run; });
     const avexhip_regions_recording it = rec[r];
     const int64_t F = frames_of(it.n_samples, hop);
@@ -66,7 +56,7 @@ __global__ __launch_bounds__(256) void regions_cells_kernel(const float* __restr
     if (f0 >= F) return;                                         // (block-uniform; the entry point launches no such workgroup)
     const int nf = F - f0 < kRgRun ? (int)(F - f0) : kRgRun;
 
-    stage_twiddles(tw, tables);
+    stage_twiddles(lds.tw, tables);
 
     // lane l owns the bins l + 64 q; lane 0 bin 256 as well
     float t[5];
@@ -80,36 +70,20 @@ __global__ __launch_bounds__(256) void regions_cells_kernel(const float* __restr
     int n_bad = 0;                                               // (lane 0 of each wave counts its frames)
 
     const int64_t r_lo = it.base, r_hi = it.base + it.n_samples;
-    for (int st = 0; st < nf; st += kRgStep) {                   // (block-uniform trip count)
-        const int ns = nf - st < kRgStep ? nf - st : kRgStep;
+    for (int st = 0; st < nf; st += kFpStep) {                   // (block-uniform trip count)
+        const int ns = nf - st < kFpStep ? nf - st : kFpStep;
         __syncthreads();                                         // the step before has read span
-        const int lead = stage_span(span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
+        // ---- the span of the step's frames -> LDS: lead <= 3, (ns - 1) hop + 512 <= 3 * 512 + 512 ---------------------------------------
+        const int lead = stage_span(lds.span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
         __syncthreads();
 
         if (wave < ns) {                                         // (wave-uniform; only wave syncs and ballots inside)
-            const float* src = span + lead + wave * hop;
-            float2 x[8];
-            bool nonfin = false;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float v = src[lane + 64 * q];
-                nonfin |= non_finite(v);
-                x[q] = make_float2(v * tables[lane + 64 * q], 0.f);
-            }
-            const bool bad = __any(nonfin);
-            float2* z = zbuf[wave];
-            fft512_wave(x, z, tw, lane);                         // X[k] at z[k]
+            float p[5] = {0.f, 0.f, 0.f, 0.f, 0.f};              // (in_band is false where the lane has no bin)
+            const bool bad = wave_frame_power(lds.span + lead + wave * hop, tables, lds.zbuf[wave], lds.tw, lane, [&](int q, int, float pk) { p[q] = pk; });
             unsigned mine = 0u;                                  // lane w < 9: word w of the frame
 #pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const int k = lane + 64 * q;
-                bool set = false;
-                if (k < kRecBins) {
-                    const float2 zk = z[k];
-                    const float p = bad ? NAN : zk.x * zk.x + zk.y * zk.y;      // soundscape_stats_kernel's expression
-                    set = in_band[q] && p > t[q];                // false for a NaN on either side
-                }
-                const unsigned long long m = __ballot(set);
+            for (int q = 0; q < 5; ++q) {                        // (every lane takes part in the ballots: lanes 1 .. 63 have no fifth bin)
+                const unsigned long long m = __ballot(in_band[q] && p[q] > t[q]);      // false for a NaN on either side
                 if (lane == 2 * q) mine = (unsigned)m;
                 if (lane == 2 * q + 1) mine = (unsigned)(m >> 32);
             }
@@ -137,14 +111,7 @@ __global__ __launch_bounds__(256) void regions_pack_kernel(const uint8_t* __rest
     if (lane < kRgWords) cells[f * kRgWords + lane] = (int32_t)mine;
 }
 
-// ---- the exclusive prefix of val(i), i = 0 .. n - 1, by counting ------------------------------------------------------------------------
-// n = min(n_host, *n_dev) where the count lives on the device alone (the regions found); the grid follows n_host.
-__device__ __forceinline__ int64_t rg_n(int64_t n_host, const int64_t* n_dev) {
-    if (!n_dev) return n_host;
-    const int64_t n = *n_dev;
-    return n < n_host ? n : n_host;
-}
-
+// ---- what the prefix counts (prefix_count.h) -----------------------------------------------------------------------------------------------
 struct RgFrameCells {            // the set cells of frame i
     const int32_t* cells;
     __device__ __forceinline__ int operator()(int64_t i) const {
@@ -167,71 +134,6 @@ struct RgKept {                  // region i passes the filters
     }
 };
 
-template <typename V>
-__global__ __launch_bounds__(256) void rg_scan_count_kernel(int64_t n_host, const int64_t* __restrict__ n_dev, V val, int32_t* __restrict__ block) {
-    __shared__ int wt[4];
-    const int64_t n = rg_n(n_host, n_dev);
-    const int64_t b0 = (int64_t)blockIdx.x * kRgScan + 4 * threadIdx.x;
-    int c = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (b0 + e < n) c += val(b0 + e);
-    int before, all;
-    block_scan<4>(c, 0, BlockSum(), wt, &before, &all);
-    if (threadIdx.x == 0) block[blockIdx.x] = all;
-}
-
-// one workgroup: block[b] -> the sum of the blocks before b (its low 32 bits: the caller refuses a total of 2^31 or more), *total = all
-__global__ __launch_bounds__(256) void rg_scan_blocks_kernel(int64_t n_blocks, int32_t* __restrict__ block, int64_t* __restrict__ total) {
-    __shared__ int64_t part[256];
-    const int tid = threadIdx.x;
-    const int64_t per = (n_blocks + 255) / 256;
-    const int64_t lo = per * tid < n_blocks ? per * tid : n_blocks, hi = lo + per < n_blocks ? lo + per : n_blocks;
-    int64_t s = 0;
-    for (int64_t b = lo; b < hi; ++b) s += block[b];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int k = 0; k < 256; ++k) {
-            const int64_t v = part[k];
-            part[k] = run;
-            run += v;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    int64_t run = part[tid];
-    for (int64_t b = lo; b < hi; ++b) {
-        const int v = block[b];
-        block[b] = (int32_t)(uint32_t)(uint64_t)run;
-        run += v;
-    }
-}
-
-template <typename V>
-__global__ __launch_bounds__(256) void rg_scan_apply_kernel(int64_t n_host, const int64_t* __restrict__ n_dev, V val, const int32_t* __restrict__ block,
-                                                            int32_t* __restrict__ out) {
-    __shared__ int wt[4];
-    const int64_t n = rg_n(n_host, n_dev);
-    const int64_t b0 = (int64_t)blockIdx.x * kRgScan + 4 * threadIdx.x;
-    int v[4], c = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        v[e] = b0 + e < n ? val(b0 + e) : 0;
-        c += v[e];
-    }
-    int before, all;
-    block_scan<4>(c, 0, BlockSum(), wt, &before, &all);
-    int run = (int)((unsigned)block[blockIdx.x] + (unsigned)before);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (b0 + e < n) {
-            out[b0 + e] = run;
-            run = (int)((unsigned)run + (unsigned)v[e]);
-        }
-}
-
 // ---- union-find over the compact cells ---------------------------------------------------------------------------------------------------
 struct CellWs {
     int32_t *parent, *rank, *cnt, *firstf, *lastf, *lowb, *highb, *recof, *pos;      // [n] each; from cnt on by region
@@ -249,7 +151,7 @@ static CellWs carve_cells(void* ws, int64_t n) {
     char* p = (char*)ws;
     int32_t** const arrays[9] = {&w.parent, &w.rank, &w.cnt, &w.firstf, &w.lastf, &w.lowb, &w.highb, &w.recof, &w.pos};
     for (int32_t** a : arrays) *a = take<int32_t>(p, (size_t)n);
-    w.block = take<int32_t>(p, (size_t)((n + kRgScan - 1) / kRgScan));
+    w.block = take<int32_t>(p, (size_t)prefix_count_blocks(n));
     w.bytes = (size_t)(p - (char*)ws);
     return w;
 }
@@ -258,7 +160,7 @@ static FrameWs carve_frames(void* ws, int64_t F) {
     FrameWs w;
     char* p = (char*)ws;
     w.offset = take<int32_t>(p, (size_t)F);
-    w.block = take<int32_t>(p, (size_t)((F + kRgScan - 1) / kRgScan));
+    w.block = take<int32_t>(p, (size_t)prefix_count_blocks(F));
     w.bytes = (size_t)(p - (char*)ws);
     return w;
 }
@@ -418,7 +320,7 @@ __global__ __launch_bounds__(256) void regions_boxes_kernel(const int32_t* __res
             const int lg = __shfl(g, leader);
             const bool same = set && g == lg;
             const unsigned long long m = __ballot(same);
-            const int k_lo = wave_reduce(same ? k : kRgNone, RgMin()), k_hi = wave_reduce(same ? k : -1, BlockMax());
+            const int k_lo = wave_reduce(same ? k : kRgNone, BlockMin()), k_hi = wave_reduce(same ? k : -1, BlockMax());
             if (lane == leader) {
                 atomicAdd(w.cnt + lg, (int)__popcll(m));
                 atomicMin(w.lowb + lg, k_lo);
@@ -434,7 +336,7 @@ __global__ __launch_bounds__(256) void regions_boxes_kernel(const int32_t* __res
 __global__ __launch_bounds__(256) void regions_rows_kernel(int64_t n_host, const int64_t* __restrict__ n_dev, RgKept kept, const int32_t* __restrict__ recof,
                                                            const int32_t* __restrict__ pos, int64_t n_kept, int32_t* __restrict__ rows) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rg_n(n_host, n_dev) || !kept(i)) return;
+    if (i >= prefix_n(n_host, n_dev) || !kept(i)) return;
     const int64_t o = pos[i];
     if (o < 0 || o >= n_kept) return;
     const int first = kept.firstf[i], last = kept.lastf[i], low = kept.lowb[i], high = kept.highb[i];
@@ -444,14 +346,9 @@ __global__ __launch_bounds__(256) void regions_rows_kernel(int64_t n_host, const
 }
 
 // ---- what the entry points refuse ----------------------------------------------------------------------------------------------------------
-bool rg_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int rg_recordings_check(const char* what, const avexhip_regions_recording* rec_host, const avexhip_regions_recording* rec_dev, int n_rec, int hop,
                         int64_t wav_samples, int64_t total_frames, int64_t* runs_out) {
-    AVX_REQUIRE(rec_host && rec_dev, "%s: null argument", what);
-    AVX_REQUIRE(rg_aligned(rec_dev, 8), "%s: rec_dev must be 8-byte aligned", what);
-    AVX_REQUIRE(n_rec >= 1, "%s: n_rec=%d", what, n_rec);
-    AVXH_TRY(hop_check(what, hop));
+    AVXH_TRY(table_check(what, rec_host, rec_dev, "rec_dev", n_rec, true, hop));
     int64_t frames = 0, runs = 0;
     for (int r = 0; r < n_rec; ++r) {
         const avexhip_regions_recording& it = rec_host[r];
@@ -487,7 +384,7 @@ int rg_cells_count_check(const char* what, int64_t n_cells, int64_t total_frames
 }
 
 int rg_workspace_check(const char* what, const char* name, const void* ws, size_t have, size_t need) {
-    AVX_REQUIRE(ws && rg_aligned(ws, 8), "%s: %s must be 8-byte aligned and not null", what, name);
+    AVX_REQUIRE(ws && aligned(ws, 8), "%s: %s must be 8-byte aligned and not null", what, name);
     if (have < need) {
         avexhip_set_error("%s: %s %zu B < %zu B", what, name, have, need);
         return AVEXHIP_ERR_WORKSPACE;
@@ -496,18 +393,6 @@ int rg_workspace_check(const char* what, const char* name, const void* ws, size_
 }
 
 unsigned rg_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-// out[i] = the sum of val over the items below i, *total = over all of them: three launches
-template <typename V> int rg_scan(int64_t n_host, const int64_t* n_dev, V val, int32_t* block, int32_t* out, int64_t* total, hipStream_t s) {
-    const int64_t n_blocks = (n_host + kRgScan - 1) / kRgScan;
-    rg_scan_count_kernel<V><<<dim3((unsigned)n_blocks), dim3(256), 0, s>>>(n_host, n_dev, val, block);
-    AVX_LAUNCH_CHECK();
-    rg_scan_blocks_kernel<<<dim3(1), dim3(256), 0, s>>>(n_blocks, block, total);
-    AVX_LAUNCH_CHECK();
-    rg_scan_apply_kernel<V><<<dim3((unsigned)n_blocks), dim3(256), 0, s>>>(n_host, n_dev, val, block, out);
-    AVX_LAUNCH_CHECK();
-    return AVEXHIP_OK;
-}
 
 }  // namespace
 
@@ -520,7 +405,7 @@ extern "C" int avexhip_regions_cells(const float* wav_dev, int64_t wav_samples, 
                                      const avexhip_regions_recording* rec_dev, int n_rec, int hop, int lo, int hi, const float* thr_dev,
                                      const float* tables_dev, int64_t total_frames, int32_t* cells_dev, int32_t* nonfinite_dev, void* stream) {
     AVX_REQUIRE(wav_dev && tables_dev && thr_dev && nonfinite_dev, "regions_cells: null argument");
-    AVX_REQUIRE(rg_aligned(wav_dev, 16) && rg_aligned(tables_dev, 16) && rg_aligned(thr_dev, 4) && rg_aligned(cells_dev, 4) && rg_aligned(nonfinite_dev, 4),
+    AVX_REQUIRE(aligned(wav_dev, 16) && aligned(tables_dev, 16) && aligned(thr_dev, 4) && aligned(cells_dev, 4) && aligned(nonfinite_dev, 4),
                 "regions_cells: wav_dev and tables_dev must be 16-byte aligned, thr_dev, cells_dev and nonfinite_dev 4-byte aligned");
     AVX_REQUIRE(wav_samples >= 1, "regions_cells: wav_samples=%lld", (long long)wav_samples);
     AVXH_TRY(bin_band_check("regions_cells", "band", -1, lo, hi));
@@ -539,7 +424,7 @@ extern "C" int avexhip_regions_cells(const float* wav_dev, int64_t wav_samples, 
 extern "C" int avexhip_regions_pack(const uint8_t* mask_dev, int64_t total_frames, int32_t* cells_dev, void* stream) {
     AVX_REQUIRE(total_frames >= 0 && total_frames <= kRgMax, "regions_pack: total_frames=%lld outside 0..2^31 - 1", (long long)total_frames);
     if (total_frames == 0) return AVEXHIP_OK;
-    AVX_REQUIRE(mask_dev && cells_dev && rg_aligned(cells_dev, 4), "regions_pack: null argument, or cells_dev not 4-byte aligned");
+    AVX_REQUIRE(mask_dev && cells_dev && aligned(cells_dev, 4), "regions_pack: null argument, or cells_dev not 4-byte aligned");
     regions_pack_kernel<<<dim3(rg_blocks(total_frames, 4)), dim3(256), 0, (hipStream_t)stream>>>(mask_dev, total_frames, cells_dev);
     AVX_LAUNCH_CHECK();
     return AVEXHIP_OK;
@@ -548,23 +433,23 @@ extern "C" int avexhip_regions_pack(const uint8_t* mask_dev, int64_t total_frame
 extern "C" int avexhip_regions_count(const int32_t* cells_dev, int64_t total_frames, void* frame_ws_dev, size_t frame_ws_bytes, int64_t* counts_dev,
                                      void* stream) {
     AVX_REQUIRE(total_frames >= 0 && total_frames <= kRgMax, "regions_count: total_frames=%lld outside 0..2^31 - 1", (long long)total_frames);
-    AVX_REQUIRE(counts_dev && rg_aligned(counts_dev, 8), "regions_count: counts_dev must be 8-byte aligned and not null");
+    AVX_REQUIRE(counts_dev && aligned(counts_dev, 8), "regions_count: counts_dev must be 8-byte aligned and not null");
     hipStream_t s = (hipStream_t)stream;
     if (total_frames == 0) {
         AVX_HIP_CHECK(hipMemsetAsync(counts_dev, 0, 8, s));
         return AVEXHIP_OK;
     }
-    AVX_REQUIRE(cells_dev && rg_aligned(cells_dev, 4), "regions_count: cells_dev must be 4-byte aligned and not null");
+    AVX_REQUIRE(cells_dev && aligned(cells_dev, 4), "regions_count: cells_dev must be 4-byte aligned and not null");
     const FrameWs fw = carve_frames(frame_ws_dev, total_frames);
     AVXH_TRY(rg_workspace_check("regions_count", "frame workspace", frame_ws_dev, frame_ws_bytes, fw.bytes));
-    return rg_scan(total_frames, nullptr, RgFrameCells{cells_dev}, fw.block, fw.offset, counts_dev, s);
+    return prefix_count<int64_t>(total_frames, PrefixDevN{total_frames, nullptr}, RgFrameCells{cells_dev}, fw.block, counts_dev, PrefixStoreRank{fw.offset}, s);
 }
 
 extern "C" int avexhip_regions_label(const int32_t* cells_dev, const int64_t* frame_offsets_host, const int64_t* frame_offsets_dev, int n_rec,
                                      int64_t total_frames, int64_t n_cells, const avexhip_regions_rule* rule, const void* frame_ws_dev,
                                      size_t frame_ws_bytes, void* cell_ws_dev, size_t cell_ws_bytes, int64_t* counts_dev, void* stream) {
-    AVX_REQUIRE(frame_offsets_host && frame_offsets_dev && rg_aligned(frame_offsets_dev, 8), "regions_label: frame_offsets must be 8-byte aligned and not null");
-    AVX_REQUIRE(counts_dev && rg_aligned(counts_dev, 8), "regions_label: counts_dev must be 8-byte aligned and not null");
+    AVX_REQUIRE(frame_offsets_host && frame_offsets_dev && aligned(frame_offsets_dev, 8), "regions_label: frame_offsets must be 8-byte aligned and not null");
+    AVX_REQUIRE(counts_dev && aligned(counts_dev, 8), "regions_label: counts_dev must be 8-byte aligned and not null");
     AVX_REQUIRE(n_rec >= 1, "regions_label: n_rec=%d", n_rec);
     AVXH_TRY(rg_rule_check("regions_label", rule));
     AVX_REQUIRE(frame_offsets_host[0] == 0, "regions_label: frame_offsets[0]=%lld, 0 expected", (long long)frame_offsets_host[0]);
@@ -581,7 +466,7 @@ extern "C" int avexhip_regions_label(const int32_t* cells_dev, const int64_t* fr
         AVX_HIP_CHECK(hipMemsetAsync(counts_dev + 1, 0, 16, s));
         return AVEXHIP_OK;
     }
-    AVX_REQUIRE(cells_dev && rg_aligned(cells_dev, 4), "regions_label: cells_dev must be 4-byte aligned and not null");
+    AVX_REQUIRE(cells_dev && aligned(cells_dev, 4), "regions_label: cells_dev must be 4-byte aligned and not null");
     const FrameWs fw = carve_frames((void*)frame_ws_dev, total_frames);
     AVXH_TRY(rg_workspace_check("regions_label", "frame workspace", frame_ws_dev, frame_ws_bytes, fw.bytes));
     const CellWs cw = carve_cells(cell_ws_dev, n_cells);
@@ -594,10 +479,11 @@ extern "C" int avexhip_regions_label(const int32_t* cells_dev, const int64_t* fr
     AVX_LAUNCH_CHECK();
     regions_flatten_kernel<<<per_cell, dim3(256), 0, s>>>(n_cells, cw.parent);
     AVX_LAUNCH_CHECK();
-    AVXH_TRY(rg_scan(n_cells, nullptr, RgIsRoot{cw.parent}, cw.block, cw.rank, counts_dev + 1, s));
+    AVXH_TRY(prefix_count<int64_t>(n_cells, PrefixDevN{n_cells, nullptr}, RgIsRoot{cw.parent}, cw.block, counts_dev + 1, PrefixStoreRank{cw.rank}, s));
     regions_boxes_kernel<<<per_frame, dim3(256), 0, s>>>(cells_dev, fw.offset, frame_offsets_dev, n_rec, total_frames, cw);
     AVX_LAUNCH_CHECK();
-    return rg_scan(n_cells, counts_dev + 1, RgKept{cw.cnt, cw.firstf, cw.lastf, cw.lowb, cw.highb, *rule}, cw.block, cw.pos, counts_dev + 2, s);
+    return prefix_count<int64_t>(n_cells, PrefixDevN{n_cells, counts_dev + 1}, RgKept{cw.cnt, cw.firstf, cw.lastf, cw.lowb, cw.highb, *rule}, cw.block, counts_dev + 2,
+                                 PrefixStoreRank{cw.pos}, s);
 }
 
 extern "C" int avexhip_regions_rows(int64_t n_cells, int64_t n_kept, const avexhip_regions_rule* rule, const void* cell_ws_dev, size_t cell_ws_bytes,
@@ -606,7 +492,7 @@ extern "C" int avexhip_regions_rows(int64_t n_cells, int64_t n_kept, const avexh
     AVXH_TRY(rg_cells_count_check("regions_rows", n_cells, -1));
     AVX_REQUIRE(n_kept >= 0 && n_kept <= n_cells, "regions_rows: n_kept=%lld outside 0..%lld, the set cells", (long long)n_kept, (long long)n_cells);
     if (n_kept == 0) return AVEXHIP_OK;
-    AVX_REQUIRE(counts_dev && rg_aligned(counts_dev, 8) && rows_dev && rg_aligned(rows_dev, 4),
+    AVX_REQUIRE(counts_dev && aligned(counts_dev, 8) && rows_dev && aligned(rows_dev, 4),
                 "regions_rows: counts_dev must be 8-byte aligned, rows_dev 4-byte aligned, neither null");
     const CellWs cw = carve_cells((void*)cell_ws_dev, n_cells);
     AVXH_TRY(rg_workspace_check("regions_rows", "cell workspace", cell_ws_dev, cell_ws_bytes, cw.bytes));

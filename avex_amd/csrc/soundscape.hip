@@ -7,26 +7,23 @@
 //   soundscape_reduce_kernel   per (segment, bin) the runs' partials in run order, |first A of a run - last A of the run before| between
 //                              them (the same bits the runs computed), the divisions -> mean_power, mean_amplitude, abs_diff, count_above
 //   soundscape_indices_kernel  one workgroup per segment, fp64: ACI, ADI, AEI, BI, NDSI, Hf, Ht, H from those fp32 statistics
-// The transform is fft512_wave (fft512.h) with ONE frame per wave and a zero imaginary part, not activity_frames_kernel's pair packing: a
-// frame's P[t, :] is then a function of its own 512 samples (packed beside a loud frame, a quiet one's bins carry the partner's rounding
-// noise, eps * |X_loud|; for per-bin amplitudes that is not tolerable).  A frame of zeros gives +0 in every bin by arithmetic alone; a
-// frame that holds a NaN or an Inf is set to NaN in every bin (an Inf alone would leave +Inf in some).  No atomics, sums in one fixed
-// order: the same bits on every run and in any company.  The walk over the frames is activity.hip's (rec_frames.h: the frame count, the
-// recording of a run or a segment, the span and twiddle staging, the refusals of a recording, a hop and a bin band); every partial row,
-// statistic row and frame index follows from the checked table.
+// The power row is wave_frame_power (frame_power.h, shared with measure.hip and regions.hip): fft512_wave with ONE frame per wave and a
+// zero imaginary part, not activity_frames_kernel's pair packing: a frame's P[t, :] is then a function of its own 512 samples (packed
+// beside a loud frame, a quiet one's bins carry the partner's rounding noise, eps * |X_loud|; for per-bin amplitudes that is not
+// tolerable).  A frame of zeros gives +0 in every bin by arithmetic alone; a frame that holds a NaN or an Inf is set to NaN in every bin.
+// No atomics, sums in one fixed order: the same bits on every run and in any company.  The walk over the frames is activity.hip's
+// (rec_frames.h: the frame count, the recording of a run or a segment, the span and twiddle staging, the refusals of a table, a
+// recording, a hop, a bin band and a short buffer of partials); every partial row, statistic row and frame index follows from the
+// checked table.
 #include <math.h>
 
 #include "block_prims.h"
 #include "common.h"
-#include "fft512.h"
-#include "rec_frames.h"
+#include "frame_power.h"
 
 namespace {
 
 constexpr int kSsRun = AVEXHIP_SOUNDSCAPE_RUN_FRAMES;            // frames per workgroup of the stats kernel
-constexpr int kSsStep = 4;                                       // frames per step: one per wave
-constexpr int kSsSpan = (kSsStep - 1) * 512 + kRecFrame + 8;      // floats of LDS for a step's span at hop 512, up to 3 lead-in samples, a whole last chunk
-constexpr int kSsPRow = 260;
 // a partial row, in 4-byte words: the four sums, the first and the last amplitude row of the run, the run's non-finite frames
 constexpr int kPartPow = 0, kPartAmp = kRecBins, kPartDiff = 2 * kRecBins, kPartCount = 3 * kRecBins, kPartFirst = 4 * kRecBins, kPartLast = 5 * kRecBins,
               kPartBad = 6 * kRecBins, kPartWords = 6 * kRecBins + 2;
@@ -38,11 +35,9 @@ __host__ __device__ __forceinline__ int ss_runs_per_segment(int S) { return (S +
 __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __restrict__ wav, const avexhip_soundscape_recording* __restrict__ rec, int n_rec,
                                                                int hop, int S, float thr, const float* __restrict__ tables, float* __restrict__ partials,
                                                                float* __restrict__ frame_power) {
-    __shared__ __attribute__((aligned(16))) float span[kSsSpan];
-    __shared__ float2 zbuf[kSsStep][8 * ZROW];
-    __shared__ float2 tw[512];
-    __shared__ float prow[kSsStep][kSsPRow];
-    __shared__ int bad_of[kSsStep];
+    const FramePowerLds lds = frame_power_lds();
+    __shared__ float prow[kFpStep][kFpPRow];
+    __shared__ int bad_of[kFpStep];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = last_at_most(n_rec, (int)blockIdx.x, [&](int i) { return rec[i].first_run; });
     const avexhip_soundscape_recording it = rec[r];
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __re
     const int nf = seg_n - in_seg < kSsRun ? (int)(seg_n - in_seg) : kSsRun;
     const int64_t f0 = seg * S + in_seg;                         // the run's first frame, counted inside its recording
 
-    stage_twiddles(tw, tables);
+    stage_twiddles(lds.tw, tables);
 
     // thread t owns bin t; thread 0 bin 256 as well
     const int n_own = tid == 0 ? 2 : 1;
@@ -65,38 +60,20 @@ __global__ __launch_bounds__(256) void soundscape_stats_kernel(const float* __re
     int s_cnt[2] = {0, 0}, n_bad = 0;
 
     const int64_t r_lo = it.base, r_hi = it.base + it.n_samples;
-    for (int st = 0; st < nf; st += kSsStep) {                   // (block-uniform trip count)
-        const int ns = nf - st < kSsStep ? nf - st : kSsStep;
+    for (int st = 0; st < nf; st += kFpStep) {                   // (block-uniform trip count)
+        const int ns = nf - st < kFpStep ? nf - st : kFpStep;
         __syncthreads();                                         // the step before has read span and prow
         // ---- the span of the step's frames -> LDS: lead <= 3, (ns - 1) hop + 512 <= 3 * 512 + 512 ---------------------------------------
-        const int lead = stage_span(span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
+        const int lead = stage_span(lds.span, wav, it.base + (f0 + st) * hop, (ns - 1) * hop + kRecFrame, r_lo, r_hi);
         __syncthreads();
 
         if (wave < ns) {                                         // (wave-uniform; only wave syncs inside)
-            const float* src = span + lead + wave * hop;
-            float2 x[8];
-            bool nonfin = false;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float v = src[lane + 64 * q];
-                nonfin |= non_finite(v);
-                x[q] = make_float2(v * tables[lane + 64 * q], 0.f);
-            }
-            const bool bad = __any(nonfin);
-            float2* z = zbuf[wave];
-            fft512_wave(x, z, tw, lane);                         // X[k] at z[k]
             // A lane adds its bins in increasing order, the wave its lanes by a butterfly: a fixed order, the same for every launch.
             float total = 0.f;
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const int k = lane + 64 * q;
-                if (k < kRecBins) {
-                    const float2 zk = z[k];
-                    const float p = bad ? NAN : zk.x * zk.x + zk.y * zk.y;
-                    prow[wave][k] = p;
-                    total += p;
-                }
-            }
+            const bool bad = wave_frame_power(lds.span + lead + wave * hop, tables, lds.zbuf[wave], lds.tw, lane, [&](int, int k, float p) {
+                prow[wave][k] = p;
+                total += p;
+            });
             total = wave_sum(total);
             if (lane == 0) {
                 frame_power[it.first_frame + f0 + st + wave] = total;
@@ -190,10 +167,6 @@ __global__ __launch_bounds__(256) void soundscape_reduce_kernel(const avexhip_so
         count_above[o] = cnt;
     }
 }
-
-struct BlockMin {
-    __device__ __forceinline__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
 
 // grid: one workgroup per segment, 256 threads.  Every sum: a thread adds its own terms in increasing order, block_scan the threads in
 // thread order.  out: [G, 8] fp64 in the order of AVEXHIP_SOUNDSCAPE_INDICES.
@@ -314,10 +287,7 @@ __global__ __launch_bounds__(256) void soundscape_indices_kernel(const avexhip_s
 // What every entry point refuses in the recording table; *runs_out = the workgroups of the stats kernel.  wav_samples < 0: no buffer to check.
 int soundscape_recordings_check(const char* what, const avexhip_soundscape_recording* rec_host, const avexhip_soundscape_recording* rec_dev, int n_rec, int hop,
                                 int S, int64_t wav_samples, int64_t total_frames, int64_t total_segments, int64_t* runs_out) {
-    AVX_REQUIRE(rec_host && rec_dev, "%s: null argument", what);
-    AVX_REQUIRE(((uintptr_t)rec_dev & 7) == 0, "%s: rec_dev must be 8-byte aligned", what);
-    AVX_REQUIRE(n_rec >= 1, "%s: n_rec=%d", what, n_rec);
-    AVXH_TRY(hop_check(what, hop));
+    AVXH_TRY(table_check(what, rec_host, rec_dev, "rec_dev", n_rec, true, hop));
     AVX_REQUIRE(S >= 1 && S <= AVEXHIP_SOUNDSCAPE_MAX_SEGMENT_FRAMES, "%s: segment_frames=%d outside 1..%d", what, S, AVEXHIP_SOUNDSCAPE_MAX_SEGMENT_FRAMES);
     int64_t frames = 0, segments = 0, runs = 0;
     for (int r = 0; r < n_rec; ++r) {
@@ -339,8 +309,6 @@ int soundscape_recordings_check(const char* what, const avexhip_soundscape_recor
     return AVEXHIP_OK;
 }
 
-bool ss_aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 }  // namespace
 
 extern "C" size_t avexhip_soundscape_partials_bytes(int64_t n_runs) {
@@ -353,7 +321,7 @@ extern "C" int avexhip_soundscape_frames(const float* wav_dev, int64_t wav_sampl
                                          const float* tables_dev, int64_t total_frames, int64_t total_segments, void* partials_dev, size_t partials_bytes,
                                          float* frame_power_dev, void* stream) {
     AVX_REQUIRE(wav_dev && tables_dev, "soundscape_frames: null argument");
-    AVX_REQUIRE(((uintptr_t)wav_dev & 15) == 0 && ((uintptr_t)tables_dev & 15) == 0 && ss_aligned4(partials_dev) && ss_aligned4(frame_power_dev),
+    AVX_REQUIRE(aligned(wav_dev, 16) && aligned(tables_dev, 16) && aligned(partials_dev, 4) && aligned(frame_power_dev, 4),
                 "soundscape_frames: wav_dev and tables_dev must be 16-byte aligned, partials_dev and frame_power_dev 4-byte aligned");
     AVX_REQUIRE(wav_samples >= 1, "soundscape_frames: wav_samples=%lld", (long long)wav_samples);
     AVX_REQUIRE(!(threshold != threshold) && threshold >= 0.f, "soundscape_frames: threshold=%g: a power >= 0 expected (not NaN; +inf counts no cell)", (double)threshold);
@@ -361,10 +329,7 @@ extern "C" int avexhip_soundscape_frames(const float* wav_dev, int64_t wav_sampl
     AVXH_TRY(soundscape_recordings_check("soundscape_frames", rec_host, rec_dev, n_rec, hop, segment_frames, wav_samples, total_frames, total_segments, &runs));
     if (runs == 0) return AVEXHIP_OK;                            // no recording holds a frame
     AVX_REQUIRE(partials_dev && frame_power_dev, "soundscape_frames: null argument");
-    if (partials_bytes < avexhip_soundscape_partials_bytes(runs)) {
-        avexhip_set_error("soundscape_frames: partials_bytes=%zu, %lld runs need %zu", partials_bytes, (long long)runs, avexhip_soundscape_partials_bytes(runs));
-        return AVEXHIP_ERR_WORKSPACE;
-    }
+    AVXH_TRY(partials_check("soundscape_frames", partials_bytes, runs, avexhip_soundscape_partials_bytes(runs)));
     hipLaunchKernelGGL(soundscape_stats_kernel, dim3((unsigned)runs), dim3(256), 0, (hipStream_t)stream, wav_dev, rec_dev, n_rec, hop, segment_frames, threshold,
                        tables_dev, (float*)partials_dev, frame_power_dev);
     AVX_LAUNCH_CHECK();
@@ -375,17 +340,14 @@ extern "C" int avexhip_soundscape_reduce(const avexhip_soundscape_recording* rec
                                          int segment_frames, int64_t total_frames, int64_t total_segments, const void* partials_dev, size_t partials_bytes,
                                          float* mean_power_dev, float* mean_amplitude_dev, float* abs_diff_dev, int32_t* count_above_dev,
                                          int32_t* nonfinite_dev, void* stream) {
-    AVX_REQUIRE(ss_aligned4(partials_dev) && ss_aligned4(mean_power_dev) && ss_aligned4(mean_amplitude_dev) && ss_aligned4(abs_diff_dev) &&
-                    ss_aligned4(count_above_dev) && ss_aligned4(nonfinite_dev),
+    AVX_REQUIRE(aligned(partials_dev, 4) && aligned(mean_power_dev, 4) && aligned(mean_amplitude_dev, 4) && aligned(abs_diff_dev, 4) &&
+                    aligned(count_above_dev, 4) && aligned(nonfinite_dev, 4),
                 "soundscape_reduce: the device arrays must be 4-byte aligned");
     int64_t runs = 0;
     AVXH_TRY(soundscape_recordings_check("soundscape_reduce", rec_host, rec_dev, n_rec, hop, segment_frames, -1, total_frames, total_segments, &runs));
     if (total_segments == 0) return AVEXHIP_OK;
     AVX_REQUIRE(partials_dev && mean_power_dev && mean_amplitude_dev && abs_diff_dev && count_above_dev && nonfinite_dev, "soundscape_reduce: null argument");
-    if (partials_bytes < avexhip_soundscape_partials_bytes(runs)) {
-        avexhip_set_error("soundscape_reduce: partials_bytes=%zu, %lld runs need %zu", partials_bytes, (long long)runs, avexhip_soundscape_partials_bytes(runs));
-        return AVEXHIP_ERR_WORKSPACE;
-    }
+    AVXH_TRY(partials_check("soundscape_reduce", partials_bytes, runs, avexhip_soundscape_partials_bytes(runs)));
     hipLaunchKernelGGL(soundscape_reduce_kernel, dim3((unsigned)total_segments), dim3(256), 0, (hipStream_t)stream, rec_dev, n_rec, hop, segment_frames,
                        (const float*)partials_dev, mean_power_dev, mean_amplitude_dev, abs_diff_dev, count_above_dev, nonfinite_dev);
     AVX_LAUNCH_CHECK();
@@ -398,8 +360,8 @@ extern "C" int avexhip_soundscape_indices(const avexhip_soundscape_recording* re
                                           const int32_t* count_above_dev, const int32_t* nonfinite_dev, const float* frame_power_dev, double* indices_dev,
                                           void* stream) {
     AVX_REQUIRE(spec, "soundscape_indices: null argument");
-    AVX_REQUIRE(ss_aligned4(mean_power_dev) && ss_aligned4(mean_amplitude_dev) && ss_aligned4(abs_diff_dev) && ss_aligned4(count_above_dev) &&
-                    ss_aligned4(nonfinite_dev) && ss_aligned4(frame_power_dev) && ((uintptr_t)indices_dev & 7) == 0,
+    AVX_REQUIRE(aligned(mean_power_dev, 4) && aligned(mean_amplitude_dev, 4) && aligned(abs_diff_dev, 4) && aligned(count_above_dev, 4) &&
+                    aligned(nonfinite_dev, 4) && aligned(frame_power_dev, 4) && aligned(indices_dev, 8),
                 "soundscape_indices: indices_dev must be 8-byte aligned, the other device arrays 4-byte aligned");
     const struct { const char* name; const int32_t* b; } named[3] = {{"band", spec->band}, {"bio_band", spec->bio}, {"anthro_band", spec->anthro}};
     for (const auto& it : named) AVXH_TRY(bin_band_check("soundscape_indices", it.name, -1, it.b[0], it.b[1]));

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kWinThreads) void window_gather_kernel(const float*
 int windows_check(const char* what, const float* wav_dev, int64_t wav_samples, const avexhip_window* win_host, const avexhip_window* win_dev, int n_win,
                   int window_len, int lo, int hi) {
     AVX_REQUIRE(wav_dev && win_host && win_dev, "%s: null argument", what);
-    AVX_REQUIRE(((uintptr_t)wav_dev & 15) == 0 && ((uintptr_t)win_dev & 7) == 0, "%s: wav_dev must be 16-byte aligned, win_dev 8-byte aligned", what);
+    AVX_REQUIRE(aligned(wav_dev, 16) && aligned(win_dev, 8), "%s: wav_dev must be 16-byte aligned, win_dev 8-byte aligned", what);
     AVX_REQUIRE(n_win >= 1, "%s: n_win=%d", what, n_win);
     AVX_REQUIRE(window_len >= 1 && window_len <= (1 << 30), "%s: window_len=%d outside 1..2^30", what, window_len);
     AVX_REQUIRE(wav_samples >= 1, "%s: wav_samples=%lld", what, (long long)wav_samples);
@@ -176,7 +176,7 @@ extern "C" int avexhip_window_stats(const float* wav_dev, int64_t wav_samples, c
 extern "C" int avexhip_window_select(const avexhip_window* win_dev, const double* energy_dev, const float* peak_dev, int n_win, double thr_energy,
                                      float thr_peak, int32_t* kept_dev, int32_t* count_dev, void* stream) {
     AVX_REQUIRE(win_dev && energy_dev && peak_dev && kept_dev && count_dev, "window_select: null argument");
-    AVX_REQUIRE(((uintptr_t)win_dev & 7) == 0, "window_select: win_dev must be 8-byte aligned");
+    AVX_REQUIRE(aligned(win_dev, 8), "window_select: win_dev must be 8-byte aligned");
     AVX_REQUIRE(n_win >= 1, "window_select: n_win=%d", n_win);
     AVX_REQUIRE(!(thr_energy != thr_energy) && !(thr_peak != thr_peak), "window_select: a threshold is NaN (-inf turns one off)");
     hipLaunchKernelGGL(window_select_kernel, dim3(1), dim3(kSelectThreads), 0, (hipStream_t)stream, win_dev, energy_dev, peak_dev, n_win, thr_energy, thr_peak,
@@ -194,8 +194,8 @@ extern "C" int avexhip_window_gather(const float* wav_dev, int64_t wav_samples, 
     AVXH_TRY(windows_check("window_gather", wav_dev, wav_samples, win_host, win_dev, n_win, window_len, index_dev ? 0 : first, index_dev ? n_win : first + B));
     if (out_stride <= 0) out_stride = window_len;
     AVX_REQUIRE(out_stride >= window_len, "window_gather: out_stride %lld < window_len %d", (long long)out_stride, window_len);
-    const int wide_out = ((uintptr_t)out_dev & 15) == 0 && out_stride % 4 == 0;
-    const int wide_mask = ((uintptr_t)mask_dev & 3) == 0 && window_len % 4 == 0;
+    const int wide_out = aligned(out_dev, 16) && out_stride % 4 == 0;
+    const int wide_mask = aligned(mask_dev, 4) && window_len % 4 == 0;
     hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)((window_len + kWinStep - 1) / kWinStep), B), dim3(kWinThreads), 0, (hipStream_t)stream, wav_dev,
                        win_dev, n_win, index_dev, first, window_len, out_dev, out_stride, mask_dev, wide_out, wide_mask);
     AVX_LAUNCH_CHECK();

@@ -23,7 +23,10 @@ The audio set does the same for ingest, recordings, activity and soundscape (the
 every sample format, mono and stereo, without a plan and under a Hann sinc, a Kaiser sinc and an interpolating plan, per file and as
 batch rows from inside the clip and padded; a float clip with a NaN; two recordings (40 000 and 700 samples, one NaN sample) in one
 buffer at bases that are and are not multiples of 4: window statistics, gathers, a select, the activity gate at hops 160 and 512, the
-acoustic indices at hops 256 and 512 with segments of several runs and a partial last one.
+acoustic indices at hops 256 and 512 with segments of several runs and a partial last one; and for measure, regions (the power row of
+frame_power.h, the prefix count of prefix_count.h) over the same buffers: measure_boxes of one frame, 64 and 65 frames, banded boxes and
+the NaN frames, with and without a noise spectrum; find_regions at hops 128 and 512 under the noise spectrum of spectral_stats;
+label_cells of a random mask of 3 000 frames (three blocks of the prefix count).
 """
 import argparse
 import json
@@ -225,7 +228,7 @@ def child_audio(out_path: str) -> None:
     import torch
     import struct
     sys.path.insert(0, ROOT)
-    from avex_amd import _capi, activity, ingest, recordings, soundscape
+    from avex_amd import _capi, activity, ingest, measurements, recordings, regions, soundscape
     from avex_amd._capi import check, lib
 
     def _wav(x, sr, fmt):
@@ -306,6 +309,23 @@ def child_audio(out_path: str) -> None:
             for k in ("mean_power", "mean_amplitude", "abs_diff", "count_above", "frame_power", "nonfinite_frames"):
                 arrays[f"{tag}.soundscape.h{hop}.{k}"] = getattr(ix.stats, k).cpu().numpy()
             arrays[f"{tag}.soundscape.h{hop}.indices"] = ix.values.cpu().numpy()
+        # boxes of recording 0 at hop 256: one frame, 64 and 65 frames (a run and a run plus one), two banded ones, the frames around the
+        # NaN sample; the one frame of recording 1
+        rec, s0, s1 = [0, 0, 0, 0, 0, 0, 1], [0, 0, 0, 1000, 20000, 38400, 0], [512, 16640, 16896, 9000, 30001, 40000, 700]
+        bins = [[0, 257], [0, 257], [0, 257], [40, 120], [255, 257], [0, 257], [3, 200]]
+        noise = measurements.noise_spectrum(soundscape.spectral_stats(ws, soundscape.IndexSpec(hop=256, segment_s=0.5)))
+        for name, np_ in (("plain", None), ("noise", noise)):
+            m = measurements.measure_boxes(ws, rec, s0, s1, measurements.MeasureSpec(hop=256), noise_power=np_, bins=bins)
+            arrays.update({f"{tag}.measure.{name}.{k}": v.cpu().numpy() for k, v in m.items()})
+        for hop in (128, 512):
+            noise = measurements.noise_spectrum(soundscape.spectral_stats(ws, soundscape.IndexSpec(hop=hop, segment_s=0.5)))
+            r = regions.find_regions(ws, regions.RegionSpec(hop=hop, snr_db=6.0, min_db=-80.0), noise_power=noise)
+            arrays.update({f"{tag}.regions.h{hop}.{k}": v.cpu().numpy() for k, v in r.items()})
+            arrays.update({f"{tag}.regions.h{hop}.{k}": getattr(r, k).cpu().numpy() for k in ("cells", "nonfinite_frames", "n_found")})
+    # ---- label_cells: 3 000 frames of a fixed random mask, more than two blocks of the prefix count, as two recordings ----
+    r = regions.label_cells(torch.from_numpy(rng.random((3000, 257)) < 0.01).cuda(), [1900, 1100], (2, 2), min_cells=2)
+    arrays.update({f"label_cells.{k}": v.cpu().numpy() for k, v in r.items()})
+    arrays.update({f"label_cells.{k}": getattr(r, k).cpu().numpy() for k in ("cells", "n_found")})
     torch.cuda.synchronize()
     np.savez(out_path, **arrays)
     with open(out_path + ".json", "w") as f:

@@ -322,6 +322,27 @@ def test_band_and_min_db_alone(built_lib, synth):
         regions.find_regions(ws, RegionSpec(hop=hop), noise_power=torch.zeros(2, 257, device="cuda"))
 
 
+@pytest.mark.parametrize("hop", [32, 160, 512])
+def test_cells_are_the_soundscape_kernels_bits(built_lib, synth, hop):
+    """regions_cells_kernel and soundscape_stats_kernel run one text for P[f, k] (frame_power.h) and both apply the strict P > thr with
+    thr = fl32(16384 * 10^(d / 10)): with one frame per segment, count_above IS the mask, cell for cell, and a frame that holds a NaN
+    is all clear in both."""
+    d = -60.0                                                           # the float32 CPU chain sets 42.9 % / 43.2 % / 42.1 % of the cells at hops 32 / 160 / 512
+    x = synth[15000:31001].copy()                                       # 1 s: 485 / 97 / 31 frames
+    x[7000] = np.nan
+    ws = _ws([x])
+    r = regions.find_regions(ws, RegionSpec(hop=hop, min_db=d))
+    stats = soundscape.spectral_stats(ws, IndexSpec(hop=hop, segment_s=hop / SR, db_threshold=d))
+    assert np.float32(RegionSpec(hop=hop, min_db=d).floor) == np.float32(IndexSpec(hop=hop, segment_s=hop / SR, db_threshold=d).threshold)
+    mask, count = R.unpack(r.cells.cpu().numpy()), stats.count_above.cpu().numpy()
+    F = A.n_frames_of(len(x), hop)
+    assert mask.shape == count.shape == (F, 257) and np.array_equal(mask, count == 1) and np.isin(count, (0, 1)).all()
+    bad = [f for f in range(F) if f * hop <= 7000 < f * hop + 512]
+    assert len(bad) == {32: 16, 160: 3, 512: 1}[hop] and not mask[bad].any() and not count[bad].any()
+    assert r.nonfinite_frames.cpu().tolist() == [len(bad)] and np.flatnonzero(stats.nonfinite_frames.cpu().numpy()).tolist() == bad
+    assert 0.05 <= mask.mean() <= 0.95
+
+
 def test_find_regions_in_company(built_lib, synth):
     """A recording's rows are the same bits alone and with two others, in both orders, apart from the recording column."""
     hop = 128
